@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X SIR executor (vcf2prot step 6) -- driver contract in the task brief.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--samples S] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--samples S] [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path -- v2p_batch_execute through the C ABI: the stitch kernel's phases (K0 fill + K1 in-chunk
 scan + K2 gather / scatter) over this rank's whole shard, inputs resident in HBM.  The workload at every N is the north star's
@@ -75,7 +75,13 @@ def parse_args():
     ap.add_argument("--collectives", default="nccl", choices=["nccl", "gloo"], help="nccl (= RCCL; the product) or gloo: a TEST mode in which ranks may share a GPU "
                     "(device = local rank mod devices present) and the size exchange runs on CPU tensors")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercise launch, sharding and the size all-gather over gloo (CPU test of the N-rank path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                    "<= 64 MB): every haplotype's result length and digest, and the residues of a fixed, seeded sample of windows of the arena (rank 0's shard)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.dry_run:
+        ap.error("--dump-outputs needs the GPU path: a dry run computes nothing")
     if a.no_verify or a.dry_run:
         a.verify = "none"
     return a
@@ -291,6 +297,51 @@ def image_stats(desc, chunks, proteome_bytes, out_bytes):
     return hbm_min, n_fused, n_imm
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 6
+DUMP_WINDOWS, DUMP_WINDOW_BYTES = 1024, 8192
+DUMP_HAPS = 1 << 19             # per-haplotype records: 32 B each, so at most 16 MiB; the windows' residues at most 32 MiB
+
+
+def dump_outputs(batch, h0, out_dir):
+    """--dump-outputs: what the timed path hands its caller -- the result arena as the last timed step left it -- as out_dir/<name>.npy, so
+    that two builds can be compared output for output.  A whole arena (36 GB for C3) does not fit, so:
+      haplotypes              float64 [m]     the haplotypes with a record below: all of them, or DUMP_HAPS drawn with DUMP_SEED
+      haplotype_result_bytes  float64 [m]     their result bytes
+      haplotype_digests       float64 [m, 2]  their digests of their result bytes (v2p_batch_digests), high and low 32 bits
+      sample_windows          float64 [k, 3]  (haplotype, offset in it, length) of k <= DUMP_WINDOWS windows, one per haplotype of a
+                                              sample drawn with DUMP_SEED
+      sample_residues         float32 [sum]   the residue bytes of those windows, one after the other
+    The draws depend on the number of haplotypes only, never on the data; the files stay under DUMP_LIMIT_BYTES by construction.
+    Haplotype indices are the cohort's (h0 = the first haplotype of this batch).  Returns {name: shape} and the bytes written."""
+    import numpy as np
+    n = batch.counts()["n_haps"]
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(n, DUMP_WINDOWS)
+    haps = np.sort(rng.choice(n, size=k, replace=False)) if k else np.zeros(0, dtype=np.int64)
+    frac = rng.random(k)
+    windows, parts = np.zeros((k, 3), dtype=np.float64), []
+    for i, h in enumerate(haps.tolist()):
+        begin, length = batch.hap_range(h)
+        w = min(length, DUMP_WINDOW_BYTES)
+        off = int(frac[i] * (length - w + 1))
+        windows[i] = (h0 + h, off, w)
+        parts.append(batch.download(begin + off, w) if w else np.zeros(0, dtype=np.uint8))
+    recs = np.arange(n, dtype=np.int64) if n <= DUMP_HAPS else np.sort(rng.choice(n, size=DUMP_HAPS, replace=False))
+    dig = batch.digests()[recs]
+    arrays = {"haplotypes": (h0 + recs).astype(np.float64),
+              "haplotype_result_bytes": np.array([batch.hap_range(h)[1] for h in recs.tolist()], dtype=np.float64),
+              "haplotype_digests": np.stack([(dig >> np.uint64(32)).astype(np.float64), (dig & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1),
+              "sample_windows": windows,
+              "sample_residues": (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)).astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {name: list(a.shape) for name, a in arrays.items()}, "bytes": total}
+
+
 class Timed:
     """A finalized batch on a context whose launches go to a torch stream: execute() timed with HIP events on that stream."""
 
@@ -374,7 +425,7 @@ def box_fill_GBps(n_bytes=8 << 30, reps=4):
 
 
 def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verify, temporal=False, host_packed=True, time_host_image=False, label="", barrier=lambda: None,
-               settle_ms=0.0):
+               settle_ms=0.0, dump_dir=""):
     """One GPU (this rank's), haplotypes [h0, h1) of the cohort.  The transcript stream is made RESIDENT (v2p_stream_upload), then the
     product's one call -- v2p_batch_build_and_execute: image built on the device, executed -- gives the one-shot numbers and the batch
     every step re-executes; every haplotype's digest is checked against the oracle before anything is timed; optionally the
@@ -512,6 +563,8 @@ def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verif
                 raise RuntimeError(f"PARITY FAILURE: the arena after the timed steps differs from the verified one ({int((after != dig).sum())} haplotypes of {workload})")
             res["digests_equal_after_timed_steps"] = True
             res["image_form_timed"] = b.image_form()
+        if dump_dir:
+            res["dump_outputs"] = dump_outputs(timed.b, h0, dump_dir)
         if hbatch is not None:
             hbatch.close()
         b.close()
@@ -697,7 +750,8 @@ def main():
     else:
         leg = cohort_leg(args.workload, cohort_samples, h0, h1, args.steps, args.warmup, n_threads, args.verify, temporal=args.temporal,
                          host_packed=not args.no_host_packed and world == 1, time_host_image=args.host_image,
-                         barrier=(dist.barrier if dist_on else (lambda: None)), settle_ms=args.clock_settle_ms)
+                         barrier=(dist.barrier if dist_on else (lambda: None)), settle_ms=args.clock_settle_ms,
+                         dump_dir=args.dump_outputs if rank == 0 else "")
     n_haps, out_bytes, A, NT = leg["haplotypes"], leg["result_bytes"], leg["aa"], leg["tasks"]
 
     # ---- the path's only exchange: {haplotypes, result bytes} of every rank, ONCE per image (sizes do not change between steps) ----
@@ -798,7 +852,7 @@ def main():
             "kernel_only_aa_per_s_rank0": A / (avg_ms * 1e-3),
             "verified": leg["verified"], "stream_generation_s": leg.get("stream_generation_s"),
         }
-        for k in ("one_shot", "host_packed", "digests_equal_after_timed_steps", "image_form_timed"):
+        for k in ("one_shot", "host_packed", "digests_equal_after_timed_steps", "image_form_timed", "dump_outputs"):
             if k in leg:
                 line[k] = leg[k]
         if per_rank:

@@ -75,3 +75,69 @@ def test_child_failure_is_propagated(built):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", "2", "--workload", "C9"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode != 0
+
+
+def test_zero_steps_and_a_dry_dump_are_refused():
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    for extra, why in ((["--steps", "0"], "--steps must be at least 1"), (["--dump-outputs", "out"], "a dry run computes nothing")):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", *extra], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+        assert p.returncode == 2 and why in p.stderr, (extra, p.stderr)
+
+
+class _FakeBatch:
+    """The part of engine.Batch that bench.dump_outputs reads, over an arena whose byte at address a is a * 7 % 251."""
+
+    def __init__(self, lengths):
+        import numpy as np
+        self.lengths = np.array(lengths, dtype=np.int64)
+        self.begins = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+
+    def counts(self):
+        return {"n_haps": int(self.lengths.size)}
+
+    def hap_range(self, h):
+        return int(self.begins[h]), int(self.lengths[h])
+
+    def digests(self):
+        import numpy as np
+        return np.arange(self.lengths.size, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+
+    def download(self, begin, length):
+        import numpy as np
+        return (np.arange(begin, begin + length) * 7 % 251).astype(np.uint8)
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_arena(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays only, under the size cap whatever the cohort, the same records and windows on every call, each window
+    the arena's bytes, the digests exact in their two 32-bit halves -- for a cohort of C3's shape (20 000 haplotypes of up to 2 MB), a
+    shard past the per-haplotype cap (the cap lowered here: a sample of records), a small shard and an empty one."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 32 * bench.DUMP_HAPS + bench.DUMP_WINDOWS * (24 + 4 * bench.DUMP_WINDOW_BYTES) <= bench.DUMP_LIMIT_BYTES
+    rng = np.random.default_rng(1)
+    for lengths, h0, cap in ((rng.integers(0, 2_000_000, 20000), 0, bench.DUMP_HAPS), (rng.integers(0, 3000, 5000), 7, 1000),
+                             ([0, 5, 100000, 3], 10, bench.DUMP_HAPS), ([], 0, bench.DUMP_HAPS)):
+        monkeypatch.setattr(bench, "DUMP_HAPS", cap)
+        fb = _FakeBatch(lengths)
+        got = []
+        for d in ("a", "b"):
+            r = bench.dump_outputs(fb, h0, str(tmp_path / d))
+            assert r["bytes"] <= bench.DUMP_LIMIT_BYTES
+            got.append({name: np.load(tmp_path / d / (name + ".npy")) for name in r["files"]})
+        a, b = got
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        assert all(np.array_equal(a[k], b[k]) for k in a)
+        recs = a["haplotypes"].astype(np.int64) - h0
+        assert recs.size == min(fb.lengths.size, cap) and np.all(np.diff(recs) > 0) and (recs.size == 0 or 0 <= recs[0] <= recs[-1] < fb.lengths.size)
+        assert np.array_equal(a["haplotype_result_bytes"], fb.lengths[recs])
+        dig = (a["haplotype_digests"][:, 0].astype(np.uint64) << np.uint64(32)) | a["haplotype_digests"][:, 1].astype(np.uint64)
+        assert np.array_equal(dig, fb.digests()[recs])
+        assert len(a["sample_windows"]) == min(fb.lengths.size, bench.DUMP_WINDOWS)
+        pos = 0
+        for h, off, w in a["sample_windows"].astype(np.int64):
+            begin, length = fb.hap_range(h - h0)
+            assert 0 <= off and off + w <= length and w == min(length, bench.DUMP_WINDOW_BYTES)
+            assert np.array_equal(a["sample_residues"][pos:pos + w], fb.download(begin + off, w))
+            pos += w
+        assert pos == a["sample_residues"].size

@@ -179,10 +179,9 @@ def test_a_refused_cut_in_recycled_memory_falls_back(built, one):
 def test_no_room_for_the_one_pass_scratch_falls_back_inside_the_call(built, one, coracle):
     """hipErrorOutOfMemory for the one call's scratch (its padded descriptor array is up to 2 KiB per tile): nothing has been launched yet,
     the scratch is released and the call builds in one piece -- whose builder has a two-pass form without that array -- and executes.
-    The development library's variant 29 plays the full device."""
+    The development library's variant 29 plays the full device.  The product library has no such switch and refuses it; there the same
+    call, after the refusal, builds in one slice again with the same bytes."""
     gpu_ctx, dev = one
-    if not dev:
-        pytest.skip("the A/B switches exist in the development library only")
     from vcf2prot_amd.cohort import Cohort
     c = Cohort.preset("C3")
     gpu_ctx.upload_proteome(c.proteome())
@@ -194,12 +193,16 @@ def test_no_room_for_the_one_pass_scratch_falls_back_inside_the_call(built, one,
     assert b.oneshot_info()["n_slices"] == 1
     dig = b.digests()
     b.reset()
-    gpu_ctx.set_launch_opts(variant=29)
     try:
+        if dev:
+            gpu_ctx.set_launch_opts(variant=29)
+        else:
+            with pytest.raises(ValueError):
+                gpu_ctx.set_launch_opts(variant=29)
         b.build_and_execute(rs, 0, 0); b.sync()
     finally:
         gpu_ctx.set_launch_opts()
-    assert b.oneshot_info()["n_slices"] == 0                # the one-piece builder ran
+    assert b.oneshot_info()["n_slices"] == (0 if dev else 1)    # development: the one-piece builder ran
     assert np.array_equal(b.digests(), dig)
     assert np.array_equal(b.download_hap(7), oracle_hap(c, coracle, 47))
     b.scribble(); b.execute(); b.sync()
@@ -333,8 +336,6 @@ def test_degenerate_streams_in_one_call(built, one, kernel):
     """No haplotypes; haplotypes without transcripts; transcripts without Tasks (start-lost: an empty GIR, transcript_instructions.rs:338-343)
     and with nothing but cells no Task covers ('.', haplotype_instruction.rs:78); one Task."""
     gpu_ctx, dev = one
-    if kernel == 8 and not dev:
-        pytest.skip("PATCH images exist in the development library only")
     from stream_util import Stream
     prot = np.frombuffer(b"MEDLGENTMVLSTLRSLNNFISQRVEGGSGLEELERGGAKLMNPQRSTVWYACDEFGHIK", dtype=np.uint8)
     gpu_ctx.upload_proteome(prot)
@@ -350,8 +351,9 @@ def test_degenerate_streams_in_one_call(built, one, kernel):
         b = gpu_ctx.batch()
         try:
             b.build_and_execute(rs, kernel, 0)
-        except Exception as e:                              # (a tile image asked for by number refuses a stream without transcripts; the rule builds a rows image)
-            assert kernel == 9 and getattr(e, "code", 0) == -9 and s.struct.n_tx == 0, e
+        except Exception as e:                              # (a tile image asked for by number refuses a stream without transcripts; the product library
+            # refuses a PATCH image by number, whatever the stream -- they live in the development library; either way the rule builds it)
+            assert (kernel == 9 and getattr(e, "code", 0) == -9 and s.struct.n_tx == 0) or (kernel == 8 and not dev and getattr(e, "code", 0) == -1), e
             b.reset()
             b.build_and_execute(rs, 0, 0)
         b.sync()
@@ -369,19 +371,42 @@ def test_degenerate_streams_in_one_call(built, one, kernel):
 def test_padded_wave_image_is_the_dense_one(built, one, preset, h0, n, slices):
     """A padded wave image (v2p_set_launch_opts variant 24 forces it, 22 forces the compaction; the rule: rich streams): the one call leaves
     the descriptors in their tiles' slots, the chunk records address slots, the launcher stages them phase by phase (variant 23: read in
-    place); the arena, the digests and the image a download hands out (dense form) are the compacted build's, chunk order included."""
+    place); the arena, the digests and the image a download hands out (dense form) are the compacted build's, chunk order included.
+    The product library has no switches and refuses them: there the image is in the form the rule picks, re-executed as the product does,
+    and arena, digests and downloaded image are the one-piece builder's."""
     gpu_ctx, dev = one
-    if not dev:
-        pytest.skip("the A/B switches exist in the development library only")
     from vcf2prot_amd.cohort import Cohort
     c = Cohort.preset(preset)
     gpu_ctx.upload_proteome(c.proteome())
     stream = c.txstream(h0, h0 + n, n_threads=4)
     rs = gpu_ctx.upload_stream(stream)
     stream.close()
+    small = dict(phase_min_chunks=16, phase_bytes=1 << 16)       # (phases, hence staging, also on these small images)
+    if not dev:
+        try:
+            for var in (22, 24, 26, 23):
+                with pytest.raises(ValueError):
+                    gpu_ctx.set_launch_opts(variant=var, **small)
+            gpu_ctx.set_launch_opts(**small)
+            (desc1, ch1, hb1), dig1 = _one_piece(gpu_ctx, rs, 6)
+            b = gpu_ctx.batch()
+            b.build_and_execute(rs, 6, min(slices, 1))
+            b.sync()
+            d1 = b.digests()
+            assert np.array_equal(d1, dig1)
+            for _ in range(2):                                  # made dense at the first re-execute, if the rule left it padded
+                b.scribble(); b.execute(); b.sync()
+                assert np.array_equal(b.digests(), d1)
+            desc, ch, hb = b.download_image()
+            assert np.array_equal(desc, desc1) and np.array_equal(hb, hb1)
+            assert ch.shape == ch1.shape and np.array_equal(_sorted_chunks(ch), _sorted_chunks(ch1))
+            b.close()
+        finally:
+            gpu_ctx.set_launch_opts()
+        rs.close()
+        return
     try:
         imgs = {}
-        small = dict(phase_min_chunks=16, phase_bytes=1 << 16)   # (phases, hence staging, also on these small images)
         for var in (22, 24):
             gpu_ctx.set_launch_opts(variant=var, **small)
             b = gpu_ctx.batch()
