@@ -153,6 +153,17 @@ void v2p_packed_free(v2p_packed_image* img);
  * tools and CPU tests need neither hipcc nor a HIP runtime to look at an image */
 int  v2p_cohort_launch_bits(const v2p_chunk* chunks, uint64_t n_chunks);
 
+/* BGZF (bgzip's multi-member gzip: members of at most 65 280 input bytes, each with the BC extra field) of every range
+ * [range_begin[r], range_begin[r + 1]) of `in`, on the host: the emulation of v2p_bgzf_launch (include/vcf2prot_hip.h), byte for byte.
+ * A range is cut into blocks of 65 280 bytes (the last shorter; an empty range has none, no block crosses a range boundary); each block
+ * is one member holding one dynamic-Huffman deflate block of literals, or a stored block where that is not smaller
+ * (vcf2prot_amd/csrc/bgzf_format.hpp).  out_begin [n_ranges + 1]: where each range's members start in `out`, and the total.  No EOF
+ * block is written.  V2P_ERR_INVALID_ARG if out_capacity is short (v2p_bgzf_bound suffices) or the ranges descend. */
+int  v2p_bgzf_compress_host(const uint8_t* in, const uint64_t* range_begin, uint64_t n_ranges, uint8_t* out, uint64_t out_capacity,
+                            uint64_t* out_begin);
+/* worst-case output of n_bytes cut into n_ranges ranges (every member at most its input + 31 bytes) */
+uint64_t v2p_bgzf_bound(uint64_t n_bytes, uint64_t n_ranges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -359,6 +359,21 @@ void* v2p_batch_device_out(v2p_batch* b);
  * every test, fuzzer and bench leg that verifies a re-execute scribbles first. */
 int v2p_batch_scribble(v2p_batch* b, int byte);
 
+/* ---- BGZF output: the arena compressed on the device (vcf2prot_amd/csrc/bgzf_kernels.hip) ----------------------------------
+ * bgzip's format: every haplotype's range is cut into blocks of V2P_BGZF_BLOCK bytes (the last shorter; an empty haplotype has none),
+ * each block one gzip member with the BC extra field holding one dynamic-Huffman deflate block of literals (or a stored block where
+ * that is not smaller: a member is at most 65 311 bytes).  A haplotype's members are a BGZF stream on their own; a file is the members
+ * of its haplotypes back to back, then the 28-byte EOF block.  Bytes equal v2p_bgzf_compress_host (include/v2p_cohort.h). */
+#define V2P_BGZF_BLOCK 65280u
+/* compress every haplotype of the executed arena on the context's stream and wait; *z_bytes (optional): the members' total.
+ * V2P_ERR_STATE before an execute.  The call holds a workspace as large as the arena while it runs; the members (at most
+ * v2p_bgzf_bound bytes) stay on the device until the next v2p_batch_bgzf, v2p_batch_scribble or v2p_batch_reset, which frees them. */
+int v2p_batch_bgzf(v2p_batch* b, uint64_t* z_bytes);
+/* where haplotype h's members sit among the batch's members */
+int v2p_batch_bgzf_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len);
+/* copy member bytes [begin, begin+len) to the host */
+int v2p_batch_bgzf_download(v2p_batch* b, uint64_t begin, uint64_t len, uint8_t* out);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.
@@ -380,6 +395,11 @@ int v2p_batch_scribble(v2p_batch* b, int byte);
  * resident reference instead. */
 typedef struct v2p_pipeline v2p_pipeline;
 #define V2P_SUBMIT_DIGESTS 1u
+/* the slice's haplotypes come back as BGZF members (V2P_BGZF_BLOCK below): the runner compresses the arena on the device, v2p_pipeline_wait's
+ * *result / *n are the members of the slice's haplotypes back to back (v2p_pipeline_bgzf_info: where each starts); result_info's hap_out_begin
+ * keeps the uncompressed offsets, V2P_SUBMIT_DIGESTS digests the uncompressed arena.  The slot's batch keeps a workspace as large as the
+ * slice's arena and an output of v2p_bgzf_bound (include/v2p_cohort.h) bytes. */
+#define V2P_SUBMIT_BGZF 2u
 typedef struct { double stage_ms; double runner_ms; } v2p_slice_times;   /* the submitter's check + staging copy; the runner's one call (enqueue + its looks at the counts) */
 int  v2p_pipeline_create(v2p_ctx* ctx, uint32_t n_slots, v2p_pipeline** out);
 void v2p_pipeline_destroy(v2p_pipeline* p);
@@ -398,6 +418,8 @@ int  v2p_pipeline_wait(v2p_pipeline* p, uint32_t ticket, const uint8_t** result,
  * haplotype_instruction.rs:90,132), its digests (NULL without V2P_SUBMIT_DIGESTS), its host-side times; any pointer may be NULL */
 int  v2p_pipeline_result_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** hap_out_begin, uint64_t* n_haps, const uint64_t** digests, v2p_slice_times* times);
 int  v2p_pipeline_release(v2p_pipeline* p, uint32_t ticket);
+/* a V2P_SUBMIT_BGZF slice that has been waited for: where each haplotype's members start inside *result ([n_haps + 1]) */
+int  v2p_pipeline_bgzf_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** hap_z_begin, uint64_t* n_haps);
 
 /* ---- raw launchers on caller-owned device memory (torch tensors, other runtimes) ----- */
 /* How a launch is done.  Zero-initialise, set what is needed: every 0 (store_sc1: -1) means "the library's choice". */
@@ -456,6 +478,13 @@ int v2p_order_chunks_for_xcds(v2p_chunk* chunks, uint64_t n_chunks, const uint64
                               uint64_t proteome_len);
 int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_hap_begin, uint64_t n_haps,
                       uint64_t out_bytes, uint64_t* d_digests);
+/* BGZF members of the ranges [d_range_begin[r], d_range_begin[r + 1]) of d_in (ascending; n_bytes = their span) on caller-owned device
+ * memory, enqueued on hip_stream with no host wait: d_workspace (256-byte aligned) holds v2p_bgzf_workspace_bytes(n_bytes, n_ranges);
+ * d_out_begin [n_ranges + 1] receives where each range's members start in d_out and their total.  d_out needs the total
+ * (v2p_bgzf_bound of include/v2p_cohort.h suffices): if d_out_begin[n_ranges] > out_capacity nothing is copied. */
+uint64_t v2p_bgzf_workspace_bytes(uint64_t n_bytes, uint64_t n_ranges);
+int v2p_bgzf_launch(void* hip_stream, const uint8_t* d_in, const uint64_t* d_range_begin, uint64_t n_ranges, uint8_t* d_workspace,
+                    uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_begin);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -82,4 +82,6 @@ COHORT_API = {
     "v2p_patch_image_free": (None, [POINTER(PatchImage)]),
     "v2p_patch_interpret": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64]),
     "v2p_cohort_pack_grid": (c_int, [c_void_p, c_uint64, c_uint64, c_uint32, c_int, POINTER(PackedImage)]),
+    "v2p_bgzf_compress_host": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
+    "v2p_bgzf_bound": (c_uint64, [c_uint64, c_uint64]),
 }

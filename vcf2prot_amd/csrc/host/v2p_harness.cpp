@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            steps 4-5 produce slices of probands that stream through v2p_pipeline_submit_stream while the next are made
 //   v2p_harness sharded <preset> <samples> --devices N [--oversubscribe] [--threads T] [--streamed [--slice-mb M]]
 //                                            the cohort over N devices in THIS process (ppgg::execute_sharded): N contexts, N worker
@@ -236,7 +236,50 @@ static std::map<std::string, std::string> read_fasta(const std::string& text)
     return rec;
 }
 
-static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes)
+// an executed batch's haplotypes as the writer takes them: the arena and its haplotype offsets, or (bgzf) the BGZF members compressed on the
+// device (v2p_batch_bgzf) and where each haplotype's members start
+template <class Chk>
+static void batch_result(Chk chk, v2p_batch* b, uint64_t n_haps, bool bgzf, std::vector<uint8_t>& bytes, std::vector<uint64_t>& hob)
+{
+    hob.assign(n_haps + 1, 0);
+    uint64_t total = 0;
+    if (bgzf) chk(v2p_batch_bgzf(b, &total));
+    for (uint64_t h = 0; h < n_haps; ++h) {
+        uint64_t begin, len;
+        chk(bgzf ? v2p_batch_bgzf_hap_range(b, h, &begin, &len) : v2p_batch_hap_range(b, h, &begin, &len));
+        hob[h] = begin; hob[h + 1] = begin + len;
+    }
+    bytes.resize(hob.back());
+    if (!bytes.empty()) chk(bgzf ? v2p_batch_bgzf_download(b, 0, bytes.size(), bytes.data()) : v2p_batch_download(b, 0, bytes.size(), bytes.data()));
+}
+
+// bgzip's .gzi of a BGZF file made of `parts` (members back to back) and the EOF block: u64 count, then u64 (compressed, uncompressed)
+// offsets of every member start after the first
+static std::string bgzf_gzi(const std::vector<std::pair<const uint8_t*, uint64_t>>& parts)
+{
+    std::vector<uint64_t> pairs;
+    uint64_t c = 0, u = 0;
+    bool first = true;
+    for (const auto& pt : parts)
+        for (uint64_t o = 0; o < pt.second;) {
+            const uint8_t* m = pt.first + o;
+            const uint64_t size = uint64_t(m[16] | m[17] << 8) + 1;
+            if (!first) { pairs.push_back(c); pairs.push_back(u); }
+            first = false;
+            u += uint64_t(m[size - 4]) | uint64_t(m[size - 3]) << 8 | uint64_t(m[size - 2]) << 16 | uint64_t(m[size - 1]) << 24;
+            c += size; o += size;
+        }
+    std::string out(8 * (1 + pairs.size()), '\0');
+    const uint64_t n = pairs.size() / 2;
+    std::memcpy(&out[0], &n, 8);
+    if (!pairs.empty()) std::memcpy(&out[8], pairs.data(), 8 * pairs.size());
+    return out;
+}
+
+static const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
+                    bool bgzf)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -349,6 +392,21 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         for (uint64_t s = s0; s < s1; ++s) {
             uint64_t nb, nl;
             v2p_vcf_index_sample(idx, s, &nb, &nl);
+            if (bgzf) {
+                // --bgzf: bytes are BGZF members compressed on the device -- the proband's two haplotypes' members, the EOF block, and the .gzi
+                const std::string path = std::string(outdir) + "/" + vcf.substr(nb, nl) + ".fasta.gz";
+                const uint64_t k = 2 * (s - s0), begin = hob[k], len = hob[k + 2] - hob[k];
+                std::ofstream f(path, std::ios::binary), fi(path + ".gzi", std::ios::binary);
+                if (!f || !fi) { std::fprintf(stderr, "Could not create %s\n", path.c_str()); return false; }
+                f.write(reinterpret_cast<const char*>(bytes + begin), std::streamsize(len));
+                f.write(reinterpret_cast<const char*>(BGZF_EOF), sizeof BGZF_EOF);
+                const std::string gzi = bgzf_gzi({{bytes + hob[k], hob[k + 1] - hob[k]}, {bytes + hob[k + 1], hob[k + 2] - hob[k + 1]}});
+                fi.write(gzi.data(), std::streamsize(gzi.size()));
+                f.close(); fi.close();
+                if (!f || !fi) { std::fprintf(stderr, "Could not write %s\n", path.c_str()); return false; }
+                written += len + sizeof BGZF_EOF;
+                continue;
+            }
             const std::string path = std::string(outdir) + "/" + vcf.substr(nb, nl) + (compressed ? ".fasta.gz" : ".fasta");   // personalized_genome.rs:76-80
             std::ofstream f;
             gzFile gz = nullptr;
@@ -397,10 +455,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         chk(v2p_batch_finalize(fb));
         chk(v2p_batch_execute(fb));
         chk(v2p_batch_sync(fb));
-        hob.assign(st.n_haps + 1, 0);
-        for (uint64_t h = 0; h < st.n_haps; ++h) { uint64_t begin, len; chk(v2p_batch_hap_range(fb, h, &begin, &len)); hob[h] = begin; hob[h + 1] = begin + len; }
-        bytes.resize(hob.back());
-        if (!bytes.empty()) chk(v2p_batch_download(fb, 0, bytes.size(), bytes.data()));
+        batch_result(chk, fb, st.n_haps, bgzf, bytes, hob);
         v2p_batch_destroy(fb);
     };
     // ---- the pipeline ----
@@ -425,7 +480,8 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
             return write_probands(j.s0, j.s1, fb_bytes.data(), fb_hob.data());
         }
         chk(rc);
-        chk(v2p_pipeline_result_info(pipe, j.ticket, &hob, &nh, nullptr, nullptr));
+        if (bgzf) chk(v2p_pipeline_bgzf_info(pipe, j.ticket, &hob, &nh));
+        else chk(v2p_pipeline_result_info(pipe, j.ticket, &hob, &nh, nullptr, nullptr));
         if (nh != 2 * (j.s1 - j.s0)) { std::fprintf(stderr, "panicked: a slice came back with another number of haplotypes\n"); std::exit(101); }
         const bool ok = write_probands(j.s0, j.s1, bytes, hob);
         chk(v2p_pipeline_release(pipe, j.ticket));
@@ -437,7 +493,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         if (inflight.size() == SLOTS) { if (!finish(inflight.front())) return false; inflight.erase(inflight.begin()); }
         v2p_txstream st = txs_p->view();
         uint32_t t = 0;
-        chk(v2p_pipeline_submit_stream(pipe, &st, 0, 0, &t));
+        chk(v2p_pipeline_submit_stream(pipe, &st, 0, bgzf ? V2P_SUBMIT_BGZF : 0u, &t));
         inflight.push_back(Job{t, slice_s0, s1, std::move(txs_p)});
         txs_p.reset(new TxStreamHost());
         slice_s0 = s1; ++n_slices;
@@ -515,10 +571,9 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         chk(v2p_batch_execute(b));
         chk(v2p_batch_sync(b));
         t_exec = since(t0); t0 = clk::now();
-        std::vector<uint64_t> hob(2 * S + 1, 0);
-        for (uint64_t h = 0; h < 2 * S; ++h) { uint64_t begin, len; chk(v2p_batch_hap_range(b, h, &begin, &len)); hob[h] = begin; hob[h + 1] = begin + len; }
-        std::vector<uint8_t> bytes(hob.back());
-        if (!bytes.empty()) chk(v2p_batch_download(b, 0, bytes.size(), bytes.data()));
+        std::vector<uint64_t> hob;
+        std::vector<uint8_t> bytes;
+        batch_result(chk, b, 2 * S, bgzf, bytes, hob);
         if (!write_probands(0, S, bytes.data(), hob.data())) return 101;
     } else {
         const double w0 = t_write_acc;
@@ -639,7 +694,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -647,8 +702,10 @@ int main(int argc, char** argv)
             host_build |= !std::strcmp(argv[i], "--host-build");
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
+            bgzf |= !std::strcmp(argv[i], "--bgzf");
         }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1)); }
+        if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

@@ -29,6 +29,8 @@
 #include "bench/v2p_bench.h"
 #endif
 #include "v2p_ctx_internal.h"
+#include "bgzf_kernels.h"
+#include "bgzf_format.hpp"
 
 using namespace v2p;
 
@@ -216,6 +218,11 @@ struct v2p_batch {
     uint64_t n_desc = 0, n_chunks = 0, n_payload = 0, out_bytes = 0, n_haps = 0;
     uint32_t max_chunk_tasks = 0;
     int launch_hint = 0;           // stitch_launch_bits() of the chunk table
+    // v2p_batch_bgzf: the arena's haplotypes as BGZF members (bgzf_kernels.hip) -- the encoder's workspace, the members back to back,
+    // where each haplotype's members start (device and host copies); z_ready until the next reset
+    DevBuf d_zws, d_z, d_zbegin;
+    std::vector<uint64_t> z_begin;
+    bool z_ready = false;
     bool grow = false;             // the one call sizes its buffers with slack and never shrinks them (a pipeline slot's batch: slice after slice of
                                    // about one size -- an exact-size buffer would be freed and allocated again, and hipFree waits for the device)
 };
@@ -1046,6 +1053,7 @@ void v2p_batch_destroy(v2p_batch* b)
     b->d_desc.release(); b->d_chunks.release(); b->d_payload.release(); b->d_out.release();
     b->d_hap.release(); b->d_digest.release(); b->d_status.release(); b->d_build.release();
     b->d_tiles.release(); b->d_cover.release(); b->d_pad.release(); b->d_order.release(); b->d_patch.release(); b->d_stage.release(); b->d_pieces.release(); b->d_chunks2.release(); b->h_sum.release();
+    b->d_zws.release(); b->d_z.release(); b->d_zbegin.release();
     for (hipEvent_t e : b->ev_os) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : b->ev_aux) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : b->ev_par) if (e) (void)hipEventDestroy(e);
@@ -2170,6 +2178,7 @@ static int batch_reset_locked(v2p_batch* b, bool wait)
     b->payload_dev = nullptr; b->n_slices = 0; b->launch_hint = 0; b->is_patch = false; b->patch_segs = b->patch_patches = 0;
     b->is_tiles = false; b->tile_slots = 0; b->tiles_n = 0; b->tiles_count = nullptr; b->tiles_res_base = nullptr;
     b->pad_image = false; b->desc_slots = 0; b->pad_tdbase = nullptr; b->pieces_state = 0; b->executed = false;
+    b->z_ready = false; b->z_begin.clear();
     b->os_kernel = 0; b->os_build_ms = 0.f; b->os_wall_ms = 0.0; b->os_ahead = false;      // (v2p_batch_oneshot_info: no call to report on)
     stream_detach(b); b->orphaned = false;
     if (b->desc_swapped) { std::swap(b->d_desc, b->d_pad); b->desc_swapped = false; }     // (the large allocation is the padded array's again)
@@ -2180,7 +2189,9 @@ int v2p_batch_reset(v2p_batch* b)
 {
     if (!b) return V2P_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->ctx->mu);
-    return batch_reset_locked(b, true);
+    const int rc = batch_reset_locked(b, true);
+    b->d_z.release(); b->d_zws.release(); b->d_zbegin.release();      // (the BGZF members: up to the arena's size again)
+    return rc;
 }
 
 int v2p_batch_build_from_stream(v2p_batch* b, const v2p_stream* st, int kernel, float* build_ms)
@@ -3054,6 +3065,56 @@ int v2p_batch_digests(v2p_batch* b, uint64_t* digests, uint64_t n_haps)
     return V2P_OK;
 }
 
+int v2p_batch_bgzf(v2p_batch* b, uint64_t* z_bytes)
+{
+    if (!b) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = b->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!b->finalized || !b->executed) return c->fail(V2P_ERR_STATE, "v2p_batch_bgzf: the batch has not been executed");
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    b->z_ready = false;
+    const uint64_t n = b->n_haps;
+    HIP_TRY(c, b->d_zws.ensure(v2p_bgzf_workspace_bytes(b->out_bytes, n)), "hipMalloc(bgzf workspace)");
+    HIP_TRY(c, b->d_zbegin.ensure(8 * (n + 1)), "hipMalloc(bgzf offsets)");
+    uint64_t* zb = reinterpret_cast<uint64_t*>(b->d_zbegin.ptr());
+    HIP_TRY(c, bgzf_encode(c->stream, b->d_out.ptr(), reinterpret_cast<const uint64_t*>(b->d_hap.ptr()), n, b->d_zws.ptr(), zb), "launch(bgzf)");
+    b->z_begin.assign(n + 1, 0);
+    HIP_TRY(c, hipMemcpyAsync(b->z_begin.data(), zb, 8 * (n + 1), hipMemcpyDeviceToHost, c->stream), "D2H(bgzf offsets)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    const uint64_t total = b->z_begin[n];
+    if (total > bgzf::bound(b->out_bytes, n)) return c->fail(V2P_ERR_HIP, "v2p_batch_bgzf: the members exceed their bound");
+    HIP_TRY(c, b->d_z.ensure(total), "hipMalloc(bgzf members)");
+    HIP_TRY(c, bgzf_compact(c->stream, zb, n, b->d_zws.ptr(), b->d_z.ptr(), total), "launch(bgzf compact)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    b->d_zws.release();            // (as large as the arena: held for the call only)
+    b->z_ready = true;
+    if (z_bytes) *z_bytes = total;
+    return V2P_OK;
+}
+
+int v2p_batch_bgzf_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len)
+{
+    if (!b || !begin || !len) return V2P_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(b->ctx->mu);
+    if (!b->z_ready) return b->ctx->fail(V2P_ERR_STATE, "no BGZF members: v2p_batch_bgzf first");
+    if (h + 1 >= b->z_begin.size()) return V2P_ERR_INVALID_ARG;
+    *begin = b->z_begin[h]; *len = b->z_begin[h + 1] - b->z_begin[h];
+    return V2P_OK;
+}
+
+int v2p_batch_bgzf_download(v2p_batch* b, uint64_t begin, uint64_t len, uint8_t* out)
+{
+    if (!b || (len && !out)) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = b->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!b->z_ready) return c->fail(V2P_ERR_STATE, "no BGZF members: v2p_batch_bgzf first");
+    if (begin > b->z_begin.back() || len > b->z_begin.back() - begin) return c->fail(V2P_ERR_INVALID_ARG, "range outside the BGZF members");
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    if (len) HIP_TRY(c, hipMemcpyAsync(out, b->d_z.ptr() + begin, len, hipMemcpyDeviceToHost, c->stream), "D2H(bgzf)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    return V2P_OK;
+}
+
 void* v2p_batch_device_out(v2p_batch* b) { return (b && b->finalized) ? b->d_out.ptr() : nullptr; }
 
 int v2p_batch_scribble(v2p_batch* b, int byte)
@@ -3064,6 +3125,10 @@ int v2p_batch_scribble(v2p_batch* b, int byte)
     if (!b->finalized) return c->fail(V2P_ERR_STATE, "batch not finalized");
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     if (b->out_bytes) HIP_TRY(c, hipMemsetAsync(b->d_out.ptr(), byte & 0xFF, b->out_bytes, c->stream), "hipMemset(arena)");
+    // ... and what v2p_batch_bgzf left: the next one must not find its answer in place either
+    for (DevBuf* z : {&b->d_z, &b->d_zws, &b->d_zbegin})
+        if (z->base) HIP_TRY(c, hipMemsetAsync(z->base, byte & 0xFF, z->cap, c->stream), "hipMemset(bgzf)");
+    b->z_ready = false;
     return V2P_OK;
 }
 
@@ -3107,6 +3172,7 @@ struct PipeSlot {
     std::string err;
     int64_t err_index = -1;
     uint64_t o_status = 0, o_digests = 0;  // where the status word and the digests sit in h_out
+    uint64_t o_zbegin = 0, z_bytes = 0;    // V2P_SUBMIT_BGZF: where hap_z_begin sits in h_out; the members' total (known at the wait)
     double t_stage_ms = 0, t_queue_ms = 0, t_gpu_ms = 0;
 };
 
@@ -3265,7 +3331,7 @@ int v2p_pipeline_reserve(v2p_pipeline* p, uint64_t stream_bytes, uint64_t out_by
     for (PipeSlot& s : p->slots) {
         if (s.busy || s.in_flight) return c->fail(V2P_ERR_STATE, "v2p_pipeline_reserve: a slot is in use");
         if (stream_bytes) HIP_TRY(c, s.h_in.ensure(stream_bytes), "hipHostMalloc(in)");
-        if (out_bytes) HIP_TRY(c, s.h_out.ensure(out_bytes + 64), "hipHostMalloc(out)");
+        if (out_bytes) HIP_TRY(c, s.h_out.ensure(bgzf::bound(out_bytes, 0) + 64), "hipHostMalloc(out)");   // (room for V2P_SUBMIT_BGZF's members)
     }
     return V2P_OK;
 }
@@ -3339,9 +3405,13 @@ int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int k
     }
     if (crc != V2P_OK) { std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->fail(crc == V2P_OK ? V2P_ERR_INVALID_ARG : crc, cerr.msg, cerr.index)); }
     const uint64_t out_bytes = hob.back();
-    const uint64_t o_status = (out_bytes + 63) & ~63ull, o_dig = o_status + 64;
+    // V2P_SUBMIT_BGZF: the result buffer takes the members' worst case, and the table of where each haplotype's members start
+    const bool bgz = (flags & V2P_SUBMIT_BGZF) != 0;
+    const uint64_t res_cap = bgz ? bgzf::bound(out_bytes, slice->n_haps) : out_bytes;
+    const uint64_t o_status = (res_cap + 63) & ~63ull, o_dig = o_status + 64;
+    const uint64_t o_zb = (o_dig + ((flags & V2P_SUBMIT_DIGESTS) ? slice->n_haps * 8 : 0) + 63) & ~63ull;
     {
-        const hipError_t e = s.h_out.ensure(o_dig + ((flags & V2P_SUBMIT_DIGESTS) ? slice->n_haps * 8 : 0) + 64);
+        const hipError_t e = s.h_out.ensure(o_zb + (bgz ? (slice->n_haps + 1) * 8 : 0) + 64);
         if (e != hipSuccess) return hip_unclaim(e, "pipeline buffers");
     }
     s.lay = L; s.fasta = fasta; s.kernel = kernel; s.sflags = flags; s.n_haps = slice->n_haps;
@@ -3350,7 +3420,7 @@ int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int k
     s.shape.tx_alt_begin = nullptr; s.shape.code = nullptr; s.shape.start_pos = nullptr; s.shape.length = nullptr; s.shape.start_pos_res = nullptr; s.shape.alt = nullptr;
     s.shape.tx_header_off = nullptr; s.shape.tx_header_len = nullptr;
     s.hap_out_begin.swap(hob);
-    s.out_bytes = out_bytes; s.o_status = o_status; s.o_digests = o_dig;
+    s.out_bytes = out_bytes; s.o_status = o_status; s.o_digests = o_dig; s.o_zbegin = o_zb; s.z_bytes = 0;
     s.rc = V2P_OK; s.err.clear(); s.err_index = -1; s.is_stream = true;
     s.t_stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     // ---- H2D on the slot's stream: two copies from pinned memory, truly asynchronous ----
@@ -3432,11 +3502,26 @@ static void pipeline_runner(v2p_pipeline* p)
                     DigestArgs da{b->d_out.ptr(), reinterpret_cast<const uint64_t*>(b->d_hap.ptr()), b->n_haps, reinterpret_cast<uint64_t*>(b->d_digest.ptr())};
                     hip(launch_digest(da, b->out_bytes, c->stream), "launch(digest)");
                 }
+                uint64_t* zb = nullptr;
+                if (rc == V2P_OK && (s.sflags & V2P_SUBMIT_BGZF)) {
+                    // the arena's members into the batch's buffers, sized for the worst case so that nothing is read back here: the wait
+                    // reads hap_z_begin and copies only the members (v2p_pipeline_wait)
+                    b->z_ready = false;
+                    const uint64_t n = b->n_haps;
+                    if (hip(b->d_zws.ensure(v2p_bgzf_workspace_bytes(b->out_bytes, n)), "hipMalloc(bgzf workspace)") &&
+                        hip(b->d_zbegin.ensure(8 * (n + 1)), "hipMalloc(bgzf offsets)") &&
+                        hip(b->d_z.ensure(bgzf::bound(b->out_bytes, n)), "hipMalloc(bgzf members)")) {
+                        zb = reinterpret_cast<uint64_t*>(b->d_zbegin.ptr());
+                        if (hip(bgzf_encode(c->stream, b->d_out.ptr(), reinterpret_cast<const uint64_t*>(b->d_hap.ptr()), n, b->d_zws.ptr(), zb), "launch(bgzf)"))
+                            hip(bgzf_compact(c->stream, zb, n, b->d_zws.ptr(), b->d_z.ptr(), bgzf::bound(b->out_bytes, n)), "launch(bgzf compact)");
+                    }
+                }
                 hip(hipEventRecord(s.ev_exec, c->stream), "hipEventRecord");
                 hip(hipStreamWaitEvent(s.d2h, s.ev_exec, 0), "hipStreamWaitEvent");
                 // the way home: arena, status word, digests -- into pinned memory, on a stream of the slot's own (the next slice's H2D and its
                 // one call run beside it)
-                if (rc == V2P_OK && b->out_bytes) hip(hipMemcpyAsync(s.h_out.p, b->d_out.ptr(), b->out_bytes, hipMemcpyDeviceToHost, s.d2h), "D2H(out)");
+                if (rc == V2P_OK && zb) hip(hipMemcpyAsync(s.h_out.p + s.o_zbegin, zb, 8 * (b->n_haps + 1), hipMemcpyDeviceToHost, s.d2h), "D2H(bgzf offsets)");
+                else if (rc == V2P_OK && b->out_bytes) hip(hipMemcpyAsync(s.h_out.p, b->d_out.ptr(), b->out_bytes, hipMemcpyDeviceToHost, s.d2h), "D2H(out)");
                 if (rc == V2P_OK) hip(hipMemcpyAsync(s.h_out.p + s.o_status, b->d_status.ptr(), 8, hipMemcpyDeviceToHost, s.d2h), "D2H(status)");
                 if (rc == V2P_OK && (s.sflags & V2P_SUBMIT_DIGESTS) && b->n_haps) hip(hipMemcpyAsync(s.h_out.p + s.o_digests, b->d_digest.ptr(), b->n_haps * 8, hipMemcpyDeviceToHost, s.d2h), "D2H(digests)");
                 hip(hipEventRecord(s.done, s.d2h), "hipEventRecord");
@@ -3474,11 +3559,22 @@ int v2p_pipeline_wait(v2p_pipeline* p, uint32_t ticket, const uint8_t** result, 
     (void)hipSetDevice(c->device);
     const hipError_t e = hipEventSynchronize(s.done);
     if (e != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(e, "hipEventSynchronize"); }
-    s.in_flight = false;
     unsigned long long st;
     memcpy(&st, s.h_out.p + s.o_status, sizeof st);
+    uint64_t n_res = s.out_bytes;
+    if (s.is_stream && (s.sflags & V2P_SUBMIT_BGZF) && st == STATUS_CLEAN) {
+        // the members' size is known now: copy just them, on the slot's way home
+        const uint64_t* zb = reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_zbegin);
+        n_res = zb[s.n_haps];
+        hipError_t ze = n_res > s.o_status ? hipErrorInvalidValue : hipSuccess;
+        if (ze == hipSuccess && n_res) ze = hipMemcpyAsync(s.h_out.p, s.batch->d_z.ptr(), n_res, hipMemcpyDeviceToHost, s.d2h);
+        if (ze == hipSuccess) ze = hipStreamSynchronize(s.d2h);
+        if (ze != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(ze, "D2H(bgzf members)"); }
+        s.z_bytes = n_res;
+    }
+    s.in_flight = false;
     *result = s.h_out.p;
-    *n = s.out_bytes;
+    *n = n_res;
     if (st != STATUS_CLEAN) {
         const int code = reason_to_err(uint32_t(st & 0xFFu));
         std::lock_guard<std::mutex> lk(c->mu);
@@ -3498,6 +3594,21 @@ int v2p_pipeline_result_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** 
     if (n_haps) *n_haps = s.n_haps;
     if (digests) *digests = (s.sflags & V2P_SUBMIT_DIGESTS) ? reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_digests) : nullptr;
     if (times) { times->stage_ms = s.t_stage_ms; times->runner_ms = s.t_gpu_ms; }
+    return V2P_OK;
+}
+
+int v2p_pipeline_bgzf_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** hap_z_begin, uint64_t* n_haps)
+{
+    if (!p || ticket >= p->slots.size()) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = p->ctx;
+    PipeSlot& s = p->slots[ticket];
+    std::lock_guard<std::mutex> pl(p->pmu);
+    if (!s.busy || !s.is_stream || s.state != SLOT_LAUNCHED || s.in_flight || !(s.sflags & V2P_SUBMIT_BGZF)) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        return c->fail(V2P_ERR_STATE, "v2p_pipeline_bgzf_info: a V2P_SUBMIT_BGZF stream slice that has been waited for");
+    }
+    if (hap_z_begin) *hap_z_begin = reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_zbegin);
+    if (n_haps) *n_haps = s.n_haps;
     return V2P_OK;
 }
 

@@ -39,10 +39,17 @@ class BatchResult:
     out: np.ndarray              # pinned host view of the image's result arena (valid until the next batch is yielded)
     hap_out_begin: np.ndarray    # [h_end - h_begin + 1] offsets into `out`
     digests: object = None       # run_streamed(digests=True): the device digests of the slice's haplotypes
+    z_out: object = None         # run_streamed(bgzf=True): the haplotypes' BGZF members (pinned host view; `out` is None then)
+    hap_z_begin: object = None   # [h_end - h_begin + 1] offsets into `z_out`
 
     def haplotype(self, h: int) -> np.ndarray:
         i = h - self.h_begin
         return self.out[int(self.hap_out_begin[i]):int(self.hap_out_begin[i + 1])]
+
+    def haplotype_bgzf(self, h: int) -> np.ndarray:
+        """haplotype h's BGZF members (no EOF block)"""
+        i = h - self.h_begin
+        return self.z_out[int(self.hap_z_begin[i]):int(self.hap_z_begin[i + 1])]
 
 
 def run_batched(ctx: Context, pack: Callable[[int, int], object], result_bytes: Sequence[int], budget_bytes: int,
@@ -72,11 +79,12 @@ def run_batched(ctx: Context, pack: Callable[[int, int], object], result_bytes: 
 
 def run_streamed(ctx: Context, make_stream: Callable[[int, int], object], result_bytes: Sequence[int], budget_bytes: int,
                  h0: int = 0, slots: int = 3, kernel: int = 0, digests: bool = False, copy_threads: int = 0,
-                 reserve: Tuple[int, int] = (0, 0)) -> Iterator[BatchResult]:
+                 reserve: Tuple[int, int] = (0, 0), bgzf: bool = False) -> Iterator[BatchResult]:
     """Execute haplotypes h0 .. h0 + len(result_bytes) slice by slice from their TRANSCRIPT STREAM.  `make_stream(begin, end)` returns the
     v2p_txstream of that range (cohort.Cohort.txstream, txstream.TxStreamBuilder.finish: an object with `.struct`, optionally `.close()`);
     the resident reference must already be uploaded to `ctx`.  Yields one BatchResult per slice, in order; `out` is the slot's pinned
-    result buffer (FASTA text when the stream carries record headers) and `digests` the device digests when asked for."""
+    result buffer (FASTA text when the stream carries record headers) and `digests` the device digests when asked for.  bgzf: the slices are
+    compressed on the device and only their BGZF members cross the link -- `z_out` / `hap_z_begin` instead of `out`."""
     ranges = [(h0 + a, h0 + b) for a, b in cut_by_bytes(result_bytes, budget_bytes)]
     pipe = Pipeline(ctx, slots)
     try:
@@ -88,7 +96,7 @@ def run_streamed(ctx: Context, make_stream: Callable[[int, int], object], result
             while nxt < len(ranges) and len(inflight) < slots:
                 a, b = ranges[nxt]
                 st = make_stream(a, b)
-                t = pipe.submit_stream(st, kernel, digests)
+                t = pipe.submit_stream(st, kernel, digests, bgzf)
                 if hasattr(st, "close"):
                     st.close()                               # staged: the host copy may go
                 inflight.append((t, a, b))
@@ -96,8 +104,10 @@ def run_streamed(ctx: Context, make_stream: Callable[[int, int], object], result
             t, a, b = inflight.pop(0)
             out = pipe.wait(t)
             info = pipe.result_info(t)
-            r = BatchResult(a, b, out, info["hap_out_begin"])
+            r = BatchResult(a, b, None if bgzf else out, info["hap_out_begin"])
             r.digests = info["digests"]
+            if bgzf:
+                r.z_out, r.hap_z_begin = out, pipe.bgzf_info(t)
             yield r
             pipe.release(t)
     finally:

@@ -210,6 +210,39 @@ class Context:
     def batch(self) -> "Batch":
         return Batch(self)
 
+    def bgzf_launch(self, data, range_begin, stream=None):
+        """v2p_bgzf_launch on torch tensors of this context's device: BGZF members (bgzf.py) of the ranges [range_begin[r],
+        range_begin[r + 1]) of `data` (uint8), enqueued on `stream` (a torch stream; default: the current one) and waited for.
+        Returns (z: uint8 tensor of the members back to back, out_begin: int64 tensor [n_ranges + 1]), both on the device."""
+        import torch
+        if data.dtype != torch.uint8 or range_begin.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or not data.is_cuda or not range_begin.is_cuda:
+            raise ValueError("bgzf_launch takes a uint8 device tensor and int64 device range offsets")
+        data, rb = data.contiguous(), range_begin.contiguous()
+        n_ranges = rb.numel() - 1
+        if n_ranges < 0:
+            raise ValueError("range_begin needs n_ranges + 1 entries")
+        host_rb = rb.cpu().to(torch.int64)
+        if n_ranges and (bool((host_rb[1:] < host_rb[:-1]).any()) or int(host_rb[0]) < 0 or int(host_rb[-1]) > data.numel()):
+            raise ValueError("ranges must ascend inside the data")
+        n_bytes = int(host_rb[-1] - host_rb[0]) if n_ranges else 0
+        from . import bgzf
+        cap = bgzf.bound(n_bytes, n_ranges)
+        dev = data.device
+        ws = torch.empty(int(self._lib.v2p_bgzf_workspace_bytes(n_bytes, n_ranges)) + 256, dtype=torch.uint8, device=dev)
+        ws_ptr = (ws.data_ptr() + 255) & ~255
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        ob = torch.zeros(n_ranges + 1, dtype=torch.int64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            self._check(self._lib.v2p_bgzf_launch(ctypes.c_void_p(st.cuda_stream), ctypes.c_void_p(data.data_ptr()),
+                                                  ctypes.c_void_p(rb.data_ptr()), n_ranges, ctypes.c_void_p(ws_ptr),
+                                                  ctypes.c_void_p(out.data_ptr()), cap, ctypes.c_void_p(ob.data_ptr())))
+            st.synchronize()
+        total = int(ob[-1])
+        if total > cap:
+            raise V2PError(N.V2P_ERR_INVALID_ARG, f"bgzf_launch: {total} bytes of members exceed the {cap}-byte output")
+        return out[:total], ob
+
     def upload_stream(self, stream) -> "ResidentStream":
         """v2p_stream_upload: a transcript stream (cohort.TxStream, txstream.HostTxStream: anything with a `.struct` laid out like
         v2p_txstream) made resident on this context's device -- the input of Batch.build_and_execute / build_from_stream."""
@@ -424,6 +457,27 @@ class Batch:
     def device_out(self) -> int:
         return int(self._lib.v2p_batch_device_out(self._h) or 0)
 
+    def bgzf(self) -> int:
+        """v2p_batch_bgzf: every haplotype of the executed arena as BGZF members (bgzf.py), compressed on the device; returns their
+        total bytes.  The members stay on the device until the next bgzf() or reset()."""
+        z = ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_batch_bgzf(self._h, ctypes.byref(z)))
+        return int(z.value)
+
+    def bgzf_range(self, h: int) -> Tuple[int, int]:
+        b, ln = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_batch_bgzf_hap_range(self._h, h, ctypes.byref(b), ctypes.byref(ln)))
+        return int(b.value), int(ln.value)
+
+    def bgzf_download(self, begin: int, length: int) -> bytes:
+        out = np.empty(length, dtype=np.uint8)
+        self.ctx._check(self._lib.v2p_batch_bgzf_download(self._h, begin, length, _p(out)))
+        return out.tobytes()
+
+    def bgzf_hap(self, h: int) -> bytes:
+        """haplotype h's BGZF members (no EOF block) after bgzf()"""
+        return self.bgzf_download(*self.bgzf_range(h))
+
     def scribble(self, byte: int = 0xEE):
         """v2p_batch_scribble: the whole arena overwritten (checkers call it before every re-execute they verify)."""
         self.ctx._check(self._lib.v2p_batch_scribble(self._h, byte))
@@ -508,12 +562,13 @@ class Pipeline:
         """v2p_pipeline_reserve: pin the slots' staging / result buffers now; how many threads copy a slice into its staging."""
         self.ctx._check(self._lib.v2p_pipeline_reserve(self._h, stream_bytes, out_bytes, copy_threads))
 
-    def submit_stream(self, stream, kernel: int = 0, digests: bool = False) -> int:
+    def submit_stream(self, stream, kernel: int = 0, digests: bool = False, bgzf: bool = False) -> int:
         """v2p_pipeline_submit_stream: a slice of the transcript stream (anything with a `.struct` laid out like v2p_txstream) -- checked and
         staged on this thread, uploaded, built + executed by the pipeline's runner, its arena copied back.  The slice may be freed on return.
-        Returns the ticket, or -1 when every slot is in use (V2P_BUSY: wait for a ticket, release it, submit again)."""
+        Returns the ticket, or -1 when every slot is in use (V2P_BUSY: wait for a ticket, release it, submit again).  bgzf: the arena is
+        compressed on the device and wait() returns the haplotypes' BGZF members (bgzf_info: where each starts)."""
         t = ctypes.c_uint32()
-        rc = self._lib.v2p_pipeline_submit_stream(self._h, ctypes.byref(stream.struct), kernel, 1 if digests else 0, ctypes.byref(t))
+        rc = self._lib.v2p_pipeline_submit_stream(self._h, ctypes.byref(stream.struct), kernel, (1 if digests else 0) | (2 if bgzf else 0), ctypes.byref(t))
         if rc == 1:                                          # V2P_BUSY: every slot is in use
             return -1
         self.ctx._check(rc)
@@ -528,6 +583,12 @@ class Pipeline:
         hob = np.ctypeslib.as_array(ctypes.cast(hb, ctypes.POINTER(ctypes.c_uint64)), shape=(nh + 1,)).copy()
         dig = np.ctypeslib.as_array(ctypes.cast(dg, ctypes.POINTER(ctypes.c_uint64)), shape=(nh,)).copy() if dg.value and nh else (np.zeros(0, np.uint64) if dg.value else None)
         return {"hap_out_begin": hob, "digests": dig, "stage_ms": float(times[0]), "runner_ms": float(times[1])}
+
+    def bgzf_info(self, ticket: int) -> np.ndarray:
+        """v2p_pipeline_bgzf_info of a bgzf slice that has been waited for: hap_z_begin [n_haps + 1] (copy)"""
+        zb, n = ctypes.c_void_p(), ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_pipeline_bgzf_info(self._h, ticket, ctypes.byref(zb), ctypes.byref(n)))
+        return np.ctypeslib.as_array(ctypes.cast(zb, ctypes.POINTER(ctypes.c_uint64)), shape=(int(n.value) + 1,)).copy()
 
     def wait(self, ticket: int) -> np.ndarray:
         """View of the slot's pinned result buffer (valid until release(ticket))."""

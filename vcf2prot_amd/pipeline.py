@@ -39,14 +39,25 @@ def read_fasta(text: str) -> Dict[str, str]:
     return records
 
 
+def _proband_bytes(b, k: int, bgzf: bool) -> bytes:
+    """haplotypes k and k + 1 of an executed batch: their text, or (bgzf, after Batch.bgzf()) their BGZF members and the EOF block"""
+    if not bgzf:
+        return b.download_hap(k).tobytes() + b.download_hap(k + 1).tobytes()
+    from .bgzf import EOF_BLOCK
+    return b.bgzf_hap(k) + b.bgzf_hap(k + 1) + EOF_BLOCK
+
+
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
-                 device_build: bool = True, slice_bytes: int = 256 << 20) -> Dict[str, bytes]:
+                 device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
     every slice goes through the stream-fed pipeline as soon as it is complete (v2p_pipeline_submit_stream: step 5, the image, step 6 and
     the record text on the device, the text back in pinned host memory) while steps 4a / 4b of the next probands run here;
-    False: the host builder (v2p_batch_add_transcript), one image -- same bytes."""
+    False: the host builder (v2p_batch_add_transcript), one image -- same bytes.
+    bgzf: {proband: text of <proband>.fasta.gz} instead -- BGZF compressed on the device (bgzf.py): haplotype 1's members, haplotype 2's
+    members, then the EOF block."""
+    from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
     idx = VcfIndex(vcf)
     lists = decode_bitmasks(ctx, idx)
@@ -86,10 +97,10 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         t, s0, s1, stream = job
         try:
             text = pipe.wait(t)
-            hob = pipe.result_info(t)["hap_out_begin"]
+            hob = pipe.bgzf_info(t) if bgzf else pipe.result_info(t)["hap_out_begin"]
             for s in range(s0, s1):
                 k = 2 * (s - s0)
-                out[sample_names[s]] = text[int(hob[k]):int(hob[k + 2])].tobytes()
+                out[sample_names[s]] = text[int(hob[k]):int(hob[k + 2])].tobytes() + (EOF_BLOCK if bgzf else b"")
             pipe.release(t)
         except N.V2PError as e:
             if e.code != -9:
@@ -101,9 +112,11 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
                 build_on_device_auto(fb, stream)
                 fb.execute()
                 fb.sync()
+                if bgzf:
+                    fb.bgzf()
                 for s in range(s0, s1):
                     k = 2 * (s - s0)
-                    out[sample_names[s]] = fb.download_hap(k).tobytes() + fb.download_hap(k + 1).tobytes()
+                    out[sample_names[s]] = _proband_bytes(fb, k, bgzf)
             finally:
                 fb.close()
         stream.close()
@@ -115,7 +128,7 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         if len(inflight) == slots:
             collect(inflight.pop(0))
         stream = sink.finish()
-        inflight.append((pipe.submit_stream(stream, 0, False), s0_box[0], s1, stream))
+        inflight.append((pipe.submit_stream(stream, 0, False, bgzf), s0_box[0], s1, stream))
         s0_box[0] = s1
         sink = TxStreamBuilder(fasta=True)
 
@@ -167,8 +180,10 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
             b.finalize()
             b.execute()
             b.sync()
+            if bgzf:
+                b.bgzf()
             for s, name in enumerate(sample_names):
-                out[name] = b.download_hap(2 * s).tobytes() + b.download_hap(2 * s + 1).tobytes()
+                out[name] = _proband_bytes(b, 2 * s, bgzf)
         return out
     finally:
         if pipe is not None:
