@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X SIR executor (vcf2prot step 6) -- driver contract in the task brief.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--samples S] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--samples S] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path -- v2p_batch_execute through the C ABI: the stitch kernel's phases (K0 fill + K1 in-chunk
 scan + K2 gather / scatter) over this rank's whole shard, inputs resident in HBM.  The workload at every N is the north star's
@@ -11,23 +11,26 @@ result bytes (shard.shard_by_bytes), one rank per GPU, no data-path collective. 
 product builds: ON the device, from the per-transcript Task vectors of step 4b, by the one call that also executes it the first time
 (v2p_stream_upload + v2p_batch_build_and_execute, rows images).
 
-The N = 1 line also carries
+A plain run does what the headline figure needs and nothing else: it makes the cohort's stream resident, builds the image by the one
+call, executes it once untimed (its re-execution form), settles the clocks, runs the W warm-up and the K timed steps, writes
+--dump-outputs and prints the line.  --full also checks every haplotype's digest against the oracle before timing (--verify) and the
+arena after it, and measures the rest; its N = 1 line also carries
   one_shot        Task vectors -> result bytes ONCE, as the reference does it: ONE C-ABI call (v2p_batch_build_and_execute) on the resident stream
   host_packed     the same cohort's host-packed image executed alternately with the device-built one
   c2_cohort       BASELINE.json configs[1] ("C2": 1 000 samples x 20 k transcripts, one missense each) the same way
   cpu_baseline    the oracle's reference-faithful flavour on this box's host cores (bounded sample)
   incl_transfers  PCIe-inclusive rate through v2p_pipeline_* (not `value`)
-and roofline.traffic measured in the run itself: last of all, two child runs of this file under `rocprofv3 --pmc FETCH_SIZE` / `--pmc
+and roofline (box_fill_GBps; traffic measured in the run itself: last of all, two child runs of this file under `rocprofv3 --pmc FETCH_SIZE` / `--pmc
 WRITE_SIZE` (separate passes, --kernel-trace only beside them) execute the same image between two marker launches; any failure there
-leaves the figure replayed from profiles/traffic_latest.json, labelled so (--no-live-traffic: skip).
+leaves the figure replayed from profiles/traffic_latest.json, labelled so; --no-live-traffic: skip).
 
 --gpus N > 1 launches itself: the parent spawns `python -m torch.distributed.run` with N ranks (one per GPU, RCCL) before it touches
 any GPU, and exits with the children's code; under an external launcher (RANK/WORLD_SIZE set) it just runs as a rank.
   --scaling strong one cohort of `--samples` samples cut by result bytes (default)
   --scaling weak   every rank executes its own `--samples`-sample shard of a samples*N cohort
 Haplotypes are independent: the path's only exchange is ONE all-gather of {haplotypes, result bytes} per image (the sizes do not
-change between steps); it is timed by itself (`allgather_us`).  Every rank verifies its own shard against the oracle; rank 0 prints
-ONE JSON line.
+change between steps); it is timed by itself (`allgather_us`).  With --full (or --verify) every rank verifies its own shard against
+the oracle; rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -52,6 +55,9 @@ DEFAULT_SAMPLES = {"weak": {"C2": 1000, "C3": 2000, "C4": 313, "C5": 10000},
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: every haplotype against the oracle "
+                    "(--verify all), the one-shot timings, the host-packed A/B, the transfers-inclusive legs, C2 / C4 / C5 whole, the CPU baseline, the roofline "
+                    "(box fill, live traffic); the --no-* options below drop single legs of it.  A plain run sets up, warms up, times the steps, dumps and prints")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C3", choices=["C2", "C3", "C4", "C5"], help="default: C3, the north star's cohort")
@@ -68,7 +74,8 @@ def parse_args():
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)      # (the child of live_traffic(): the image, a few executes between two digest launches, nothing else)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the transfers-inclusive leg (v2p_pipeline_*)")
-    ap.add_argument("--verify", default="all", choices=["all", "sample", "none"], help="haplotypes whose digest is compared with the oracle before timing")
+    ap.add_argument("--verify", default=None, choices=["all", "sample", "none"], help="haplotypes whose digest is compared with the oracle before timing "
+                    "(default: all with --full, none without)")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--temporal", action="store_true", help="plain result stores instead of non-temporal")
     ap.add_argument("--host-image", action="store_true", help="time the host-packed image instead of the device-built one")
@@ -84,6 +91,8 @@ def parse_args():
         ap.error("--dump-outputs needs the GPU path: a dry run computes nothing")
     if a.no_verify or a.dry_run:
         a.verify = "none"
+    elif a.verify is None:
+        a.verify = "all" if a.full else "none"
     return a
 
 
@@ -425,11 +434,14 @@ def box_fill_GBps(n_bytes=8 << 30, reps=4):
 
 
 def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verify, temporal=False, host_packed=True, time_host_image=False, label="", barrier=lambda: None,
-               settle_ms=0.0, dump_dir=""):
+               settle_ms=0.0, dump_dir="", full=True):
     """One GPU (this rank's), haplotypes [h0, h1) of the cohort.  The transcript stream is made RESIDENT (v2p_stream_upload), then the
     product's one call -- v2p_batch_build_and_execute: image built on the device, executed -- gives the one-shot numbers and the batch
     every step re-executes; every haplotype's digest is checked against the oracle before anything is timed; optionally the
-    host-packed image of the same haplotypes is executed alternately.  Returns the numbers as a dict."""
+    host-packed image of the same haplotypes is executed alternately.  Returns the numbers as a dict.
+    full=False (a plain bench.py run): the one call builds the batch once and one untimed execute puts its image in the form every later
+    execute runs (what the host-packed A/B executes did before the timed steps of a --full run); no one-shot timings, no image statistics,
+    no parity checks unless `verify` asks for the oracle's, no host-packed image unless it is the one timed."""
     import numpy as np
     import torch
     from vcf2prot_amd.cohort import Cohort
@@ -443,8 +455,7 @@ def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verif
     A = int(np.ctypeslib.as_array(stream.struct.length, shape=(max(stream.n_tasks, 1),))[:stream.n_tasks].sum(dtype=np.int64)) if stream.n_tasks else 0
     NT = stream.n_tasks
     stream_bytes = stream.nbytes
-    sizes = cohort.result_sizes(h0, h1, n_threads=n_threads)
-    out_bytes = int(sizes.sum())
+    out_bytes = int(cohort.result_sizes(h0, h1, n_threads=n_threads).sum()) if full else None
     res = {"workload": f"{workload}: {cohort_samples} samples, haplotypes [{h0}, {h1}) x {cohort.n_transcripts} transcripts" + (f" ({label})" if label else ""),
            "haplotypes": n_haps, "aa": A, "tasks": NT, "result_bytes": out_bytes, "stream_bytes": stream_bytes, "stream_generation_s": t_stream}
     ctx = Context(torch.cuda.current_device(), temporal_stores=temporal)
@@ -455,66 +466,74 @@ def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verif
         rs = ctx.upload_stream(stream)                          # tables checked on the host, arrays to HBM once: the timed regions below start with it resident
         t_upload = time.perf_counter() - t0
         stream.close()
-        assert rs.counts()["out_bytes"] == out_bytes
+        if full:
+            assert rs.counts()["out_bytes"] == out_bytes
+        else:
+            out_bytes = res["result_bytes"] = rs.counts()["out_bytes"]
         # ---- one shot: Task vectors -> result bytes ONCE, in one C-ABI call (v2p_batch_build_and_execute).  Three times: on a batch that
         # owns nothing yet (its arena, descriptor array and scratch are allocated inside the call), on the same batch reset (everything
         # recycled) behind the upload's idle time -- what a host that has just uploaded a cohort sees --, and reset again right behind four
         # executes (the GPU's clocks up: cohorts back to back).  profiles/r05_first_execute.txt: the difference is the shader clock's ramp.
+        # A plain run (not full) keeps the first call alone: it makes the batch the steps re-execute.
         ts = torch.cuda.Stream()
         ctx.set_stream(ts.cuda_stream)
         b = ctx.batch()
-        one = {}
         b.build_and_execute(rs, 0, 0); b.sync()
-        i0 = b.oneshot_info()
-        one["total_ms_first_call_allocating"] = i0["total_ms"]; one["call_wall_ms_first_call_allocating"] = i0["call_wall_ms"]
-        b.reset()
-        time.sleep(0.5)
-        b.build_and_execute(rs, 0, 0); b.sync()
-        i1 = b.oneshot_info()
-        # (clocks up: at least four executes and at least ~40 ms of them -- four executes of an eighth of the cohort are 4 ms, which leaves the
-        # shader clock where the idle host left it: profiles/r05_first_execute.txt)
-        n_busy = max(4, min(400, int(40.0 / max(i1["total_ms"] - i1["build_ms"] - i1["tables_ms"], 0.05))))
-        for _ in range(n_busy):
-            b.execute()
-        b.sync()
-        b.reset()
-        b.build_and_execute(rs, 0, 0); b.sync()
-        i2 = b.oneshot_info()
-        ctx.set_stream(0)
-        one.update({"total_ms": i1["total_ms"], "tables_ms": i1["tables_ms"], "build_kernels_ms": i1["build_ms"], "first_execute_ms": i1["total_ms"] - i1["build_ms"] - i1["tables_ms"],
-                    "call_wall_ms": i1["call_wall_ms"], "aa_per_s": A / (i1["total_ms"] * 1e-3) if A else 0.0,
-                    "total_ms_gpu_busy_before": i2["total_ms"], "build_kernels_ms_gpu_busy_before": i2["build_ms"],
-                    "aa_per_s_gpu_busy_before": A / (i2["total_ms"] * 1e-3) if A else 0.0,
-                    "kernel_choice": i1["kernel"], "n_slices": i1["n_slices"], "stream_upload_s_incl_host_checks": t_upload,
-                    "what": "ONE call, v2p_batch_build_and_execute, on the resident per-transcript Task vectors (un-rebased SoA, transcript offsets, alt bytes): "
-                            "res_counter per tile / haplotype are tables of the resident stream (made at its upload); one-pass parse; a rich wave image (C3, C4) stays padded -- no compaction pass -- and "
-                            "the read-ahead of every phase stages its descriptors in launch order for the stitch kernel (a thin or dense image: compaction beside the row cutter); row cutter, "
-                            "XCD order, then every phase of the stitch kernel; the timed steps behind it re-execute the same batch (made dense at its first re-execute); total_ms = HIP events "
-                            "from before the first build kernel to behind the last stitch kernel, buffers recycled, 0.5 s of host sleep in front (clocks down); "
-                            "*_gpu_busy_before: the same call right behind >= 4 executes and >= 40 ms of them (clocks up)"})
-        tiles = b.image_form().get("tiles", False)
-        if tiles:
-            # a TILE image (deep Task vectors, round 6): 8-byte pieces in the tiles' slots; a tile's record is its count (4 B) and its res_counter (8 B)
-            cn = b.counts()
-            n_desc_img, n_chunks_img, image_bytes = cn["n_desc"], cn["n_chunks"], 8 * cn["n_desc"] + 12 * cn["n_chunks"]
-            hbm_min, n_fused, n_imm = out_bytes + image_bytes + int(proteome.size), None, None
+        if full:
+            one = {}
+            i0 = b.oneshot_info()
+            one["total_ms_first_call_allocating"] = i0["total_ms"]; one["call_wall_ms_first_call_allocating"] = i0["call_wall_ms"]
+            b.reset()
+            time.sleep(0.5)
+            b.build_and_execute(rs, 0, 0); b.sync()
+            i1 = b.oneshot_info()
+            # (clocks up: at least four executes and at least ~40 ms of them -- four executes of an eighth of the cohort are 4 ms, which leaves the
+            # shader clock where the idle host left it: profiles/r05_first_execute.txt)
+            n_busy = max(4, min(400, int(40.0 / max(i1["total_ms"] - i1["build_ms"] - i1["tables_ms"], 0.05))))
+            for _ in range(n_busy):
+                b.execute()
+            b.sync()
+            b.reset()
+            b.build_and_execute(rs, 0, 0); b.sync()
+            i2 = b.oneshot_info()
+            ctx.set_stream(0)
+            one.update({"total_ms": i1["total_ms"], "tables_ms": i1["tables_ms"], "build_kernels_ms": i1["build_ms"], "first_execute_ms": i1["total_ms"] - i1["build_ms"] - i1["tables_ms"],
+                        "call_wall_ms": i1["call_wall_ms"], "aa_per_s": A / (i1["total_ms"] * 1e-3) if A else 0.0,
+                        "total_ms_gpu_busy_before": i2["total_ms"], "build_kernels_ms_gpu_busy_before": i2["build_ms"],
+                        "aa_per_s_gpu_busy_before": A / (i2["total_ms"] * 1e-3) if A else 0.0,
+                        "kernel_choice": i1["kernel"], "n_slices": i1["n_slices"], "stream_upload_s_incl_host_checks": t_upload,
+                        "what": "ONE call, v2p_batch_build_and_execute, on the resident per-transcript Task vectors (un-rebased SoA, transcript offsets, alt bytes): "
+                                "res_counter per tile / haplotype are tables of the resident stream (made at its upload); one-pass parse; a rich wave image (C3, C4) stays padded -- no compaction pass -- and "
+                                "the read-ahead of every phase stages its descriptors in launch order for the stitch kernel (a thin or dense image: compaction beside the row cutter); row cutter, "
+                                "XCD order, then every phase of the stitch kernel; the timed steps behind it re-execute the same batch (made dense at its first re-execute); total_ms = HIP events "
+                                "from before the first build kernel to behind the last stitch kernel, buffers recycled, 0.5 s of host sleep in front (clocks down); "
+                                "*_gpu_busy_before: the same call right behind >= 4 executes and >= 40 ms of them (clocks up)"})
+            tiles = b.image_form().get("tiles", False)
+            if tiles:
+                # a TILE image (deep Task vectors, round 6): 8-byte pieces in the tiles' slots; a tile's record is its count (4 B) and its res_counter (8 B)
+                cn = b.counts()
+                n_desc_img, n_chunks_img, image_bytes = cn["n_desc"], cn["n_chunks"], 8 * cn["n_desc"] + 12 * cn["n_chunks"]
+                hbm_min, n_fused, n_imm = out_bytes + image_bytes + int(proteome.size), None, None
+            else:
+                desc, chunks, hb = b.download_image()
+                hbm_min, n_fused, n_imm = image_stats(desc, chunks, proteome.size, out_bytes)
+                n_desc_img, n_chunks_img, image_bytes = int(desc.size), int(chunks.shape[0]), 8 * int(desc.size) + 16 * int(chunks.shape[0])
+                del desc, chunks
+            # bytes one shot must move: the stream read once, the image written and read once, the result written once
+            one_bytes = stream_bytes + 2 * image_bytes + out_bytes + int(proteome.size)
+            one["hbm_bytes_min"] = one_bytes
+            one["frac_physical"] = one_bytes / (one["total_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            one["frac_physical_gpu_busy_before"] = one_bytes / (one["total_ms_gpu_busy_before"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            res.update({"descriptors": n_desc_img, "chunks": n_chunks_img, "fused_substitution_descriptors": n_fused, "immediate_descriptors": n_imm,
+                        "kernel": "stitchw_kernel (rows image)" if i1["kernel"] == 6 else ("stitch_tiles_kernel (a tile image: <= 16-byte pieces straight from the parse, one workgroup per tile of transcripts; first execute and every later one)" if tiles else
+                                                                                             "stitch_pieces_kernel (a dense rows image, re-written as <= 16-byte pieces at its first re-execute; its first execute: stitch_dense_kernel)"),
+                        "hbm_bytes_min_per_launch": hbm_min, "algorithmic_bytes_per_launch": 2 * A + 16 * NT, "one_shot": one})
         else:
-            desc, chunks, hb = b.download_image()
-            hbm_min, n_fused, n_imm = image_stats(desc, chunks, proteome.size, out_bytes)
-            n_desc_img, n_chunks_img, image_bytes = int(desc.size), int(chunks.shape[0]), 8 * int(desc.size) + 16 * int(chunks.shape[0])
-            del desc, chunks
-        # bytes one shot must move: the stream read once, the image written and read once, the result written once
-        one_bytes = stream_bytes + 2 * image_bytes + out_bytes + int(proteome.size)
-        one["hbm_bytes_min"] = one_bytes
-        one["frac_physical"] = one_bytes / (one["total_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-        one["frac_physical_gpu_busy_before"] = one_bytes / (one["total_ms_gpu_busy_before"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-        res.update({"descriptors": n_desc_img, "chunks": n_chunks_img, "fused_substitution_descriptors": n_fused, "immediate_descriptors": n_imm,
-                    "kernel": "stitchw_kernel (rows image)" if i1["kernel"] == 6 else ("stitch_tiles_kernel (a tile image: <= 16-byte pieces straight from the parse, one workgroup per tile of transcripts; first execute and every later one)" if tiles else
-                                                                                         "stitch_pieces_kernel (a dense rows image, re-written as <= 16-byte pieces at its first re-execute; its first execute: stitch_dense_kernel)"),
-                    "hbm_bytes_min_per_launch": hbm_min, "algorithmic_bytes_per_launch": 2 * A + 16 * NT, "one_shot": one})
+            b.execute(); b.sync()                               # (the image's re-execution form, made at its first re-execute, before the clock settle)
+            ctx.set_stream(0)
         t = Timed(ctx, b)
         # ---- parity before timing: per-haplotype digests vs the oracle ----
-        dig = b.digests()
+        dig = b.digests() if full or verify != "none" else None
         verified = None
         if verify != "none":
             every = verify == "all"
@@ -540,16 +559,17 @@ def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verif
             hbatch.finalize()
             hbatch.execute()
             hbatch.sync()
-            same = bool(np.array_equal(hbatch.digests(), dig))
-            th = Timed(ctx, hbatch)
-            ab_h, ab_d = [], []
-            for _ in range(3):
-                th.once(); t.once()
-            for _ in range(9):
-                ab_h.append(th.once()); ab_d.append(t.once())
-            res["host_packed"] = {"image_build_s": t_pack, "descriptors": int(img.desc.size), "chunks": int(img.chunks.shape[0]), "digests_equal_device_built_image": same,
-                                  "ab_execute_ms_host_packed": sorted(ab_h)[4], "ab_execute_ms_device_built": sorted(ab_d)[4],
-                                  "what": "the same haplotypes packed on the host (sir_pack.hpp, greedy chunks), executed alternately with the device-built image in this process"}
+            if host_packed:                                     # (the A/B; a plain run that times this image executes it once above)
+                same = bool(np.array_equal(hbatch.digests(), dig)) if dig is not None else None
+                th = Timed(ctx, hbatch)
+                ab_h, ab_d = [], []
+                for _ in range(3):
+                    th.once(); t.once()
+                for _ in range(9):
+                    ab_h.append(th.once()); ab_d.append(t.once())
+                res["host_packed"] = {"image_build_s": t_pack, "descriptors": int(img.desc.size), "chunks": int(img.chunks.shape[0]), "digests_equal_device_built_image": same,
+                                      "ab_execute_ms_host_packed": sorted(ab_h)[4], "ab_execute_ms_device_built": sorted(ab_d)[4],
+                                      "what": "the same haplotypes packed on the host (sir_pack.hpp, greedy chunks), executed alternately with the device-built image in this process"}
             del img
         # ---- timed region ----
         timed = Timed(ctx, hbatch) if time_host_image else t
@@ -557,7 +577,7 @@ def cohort_leg(workload, cohort_samples, h0, h1, steps, warmup, n_threads, verif
         res.update({"elapsed_s": elapsed, "kernel_ms": kern_ms, "image_timed": "host-packed" if time_host_image else "device-built", "clock_settle_ms": timed.settled_ms})
         # ---- parity AFTER timing: the timed steps re-execute the image in its re-execution form (a padded image made dense, its descriptors
         # staged; a dense image from its pieces) -- the arena they leave must be the one that was verified above (Timed.run scribbled it in between)
-        if not time_host_image:
+        if dig is not None and not time_host_image:
             after = b.digests()
             if not np.array_equal(after, dig):
                 raise RuntimeError(f"PARITY FAILURE: the arena after the timed steps differs from the verified one ({int((after != dig).sum())} haplotypes of {workload})")
@@ -707,7 +727,7 @@ def main():
             build.build_cohort()                               # host logic only: no hipcc, no HIP runtime
         else:
             build.build_all()
-        if args.verify != "none" or not args.no_cpu_baseline:
+        if args.verify != "none" or (args.full and not args.no_cpu_baseline):
             import sir_oracle
             sir_oracle.build_c_oracle()
     if dist_on:
@@ -725,8 +745,11 @@ def main():
     else:
         cohort_samples = samples
         cohort = Cohort.preset(args.workload, n_samples=cohort_samples)
-        sizes = cohort.result_sizes(0, cohort.n_haplotypes, n_threads=n_threads)
-        h0, h1 = shard_by_bytes(sizes.tolist(), world)[rank]              # equal result bytes per rank
+        if world == 1:
+            h0, h1 = 0, cohort.n_haplotypes
+        else:
+            sizes = cohort.result_sizes(0, cohort.n_haplotypes, n_threads=n_threads)
+            h0, h1 = shard_by_bytes(sizes.tolist(), world)[rank]          # equal result bytes per rank
     speedup_ref = None
     if world > 1 and args.scaling == "strong" and rank == 0 and args.speedup_ref and not args.dry_run:
         try:                                                   # the same cohort alone on this GPU, one image (the 1-GPU point of the curve)
@@ -749,9 +772,9 @@ def main():
         st.close()
     else:
         leg = cohort_leg(args.workload, cohort_samples, h0, h1, args.steps, args.warmup, n_threads, args.verify, temporal=args.temporal,
-                         host_packed=not args.no_host_packed and world == 1, time_host_image=args.host_image,
+                         host_packed=args.full and not args.no_host_packed and world == 1, time_host_image=args.host_image,
                          barrier=(dist.barrier if dist_on else (lambda: None)), settle_ms=args.clock_settle_ms,
-                         dump_dir=args.dump_outputs if rank == 0 else "")
+                         dump_dir=args.dump_outputs if rank == 0 else "", full=args.full)
     n_haps, out_bytes, A, NT = leg["haplotypes"], leg["result_bytes"], leg["aa"], leg["tasks"]
 
     # ---- the path's only exchange: {haplotypes, result bytes} of every rank, ONCE per image (sizes do not change between steps) ----
@@ -795,28 +818,44 @@ def main():
     if rank == 0:
         steps = len(kern_ms)
         avg_ms = sum(kern_ms) / len(kern_ms)
-        hbm_min = leg["hbm_bytes_min_per_launch"]
-        b_alg = leg["algorithmic_bytes_per_launch"]
-        achieved = hbm_min / (avg_ms * 1e-3) / 1e9 if not args.dry_run else 0.0
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath) and not args.dry_run:
-            try:
-                tj = json.load(open(tpath))
-                tj = tj.get(args.workload, tj)
-                if tj.get("workload") == args.workload and tj.get("haplotypes") == n_haps:
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_source = ("replayed, not measured in this run: " + str(tj.get("source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same command")) +
-                                      " (profiles/traffic_latest.json)")
-            except Exception:
-                traffic = None
         whole = world == 1 and args.scaling == "strong"
-        fill_gbps = None
-        if not args.dry_run:
-            try:
-                fill_gbps = box_fill_GBps()
-            except Exception:
-                fill_gbps = None
+        roofline = None
+        if "hbm_bytes_min_per_launch" in leg:                  # (--full, and the dry run's zeros: the roofline of the timed image)
+            hbm_min = leg["hbm_bytes_min_per_launch"]
+            b_alg = leg["algorithmic_bytes_per_launch"]
+            achieved = hbm_min / (avg_ms * 1e-3) / 1e9 if not args.dry_run else 0.0
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath) and not args.dry_run:
+                try:
+                    tj = json.load(open(tpath))
+                    tj = tj.get(args.workload, tj)
+                    if tj.get("workload") == args.workload and tj.get("haplotypes") == n_haps:
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_source = ("replayed, not measured in this run: " + str(tj.get("source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same command")) +
+                                          " (profiles/traffic_latest.json)")
+                except Exception:
+                    traffic = None
+            fill_gbps = None
+            if not args.dry_run:
+                try:
+                    fill_gbps = box_fill_GBps()
+                except Exception:
+                    fill_gbps = None
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "frac_definition": "physical",
+                        "traffic": traffic, "traffic_source": traffic_source,
+                        "bytes": "achieved = hbm_bytes_min / kernel time: result bytes written once + 8 B per descriptor + 16 B per chunk + alt bytes "
+                                 "outside descriptors + the proteome once (reference reads are served by L2 and not counted)",
+                        "hbm_bytes_min_per_launch": hbm_min,
+                        "algorithmic_bytes_per_launch": b_alg, "algorithmic_GBps": b_alg / (avg_ms * 1e-3) / 1e9,
+                        "frac_b_alg": b_alg / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "frac_b_alg_note": "SURVEY 8d's B_alg = 2A + 16N prices one HBM read per residue and 16 B per Task; the design serves reference reads from L2 and fuses "
+                                           "Task triples into 8-byte descriptors, so this ratio exceeds 1 without skipping work -- `frac` (physical bytes) is the roofline figure",
+                        "kernel": leg["kernel"] + ": a step = the image's phases, each read ahead into the memory-side cache (touch_image_kernel + stitch launches) -- kernel_ms is the whole step",
+                        "kernel_ms_avg": avg_ms, "kernel_ms_min": min(kern_ms),
+                        "box_fill_GBps": fill_gbps, "frac_of_box_fill": (achieved / fill_gbps) if fill_gbps else None,
+                        "box_fill_note": "this box's rate for a bare fill of 8 GiB (torch fill_), measured in this process: boxes of the pool differ by several per cent"}
         line = {
             "metric": "amino-acids written/sec", "value": A_all * steps / elapsed, "unit": "aa/s",
             "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / steps,
@@ -828,30 +867,19 @@ def main():
                                                           (f"the whole {samples}-sample cohort as ONE image, one v2p_batch_execute per step" if whole else
                                                            f"one {samples}-sample cohort over {world} GPU(s), equal result bytes per rank"))
                                    + f" ({int(A_all):.3e} aa) x {cohort.n_transcripts} transcripts, SIR Task vectors at the step-6 boundary",
-                       "haplotypes_rank0": n_haps, "tasks_rank0": NT, "aa_rank0": A, "chunks_rank0": leg["chunks"], "descriptors_rank0": leg["descriptors"],
+                       "haplotypes_rank0": n_haps, "tasks_rank0": NT, "aa_rank0": A, "chunks_rank0": leg.get("chunks"), "descriptors_rank0": leg.get("descriptors"),
                        "descriptor_bytes": 8, "image": leg.get("image_timed", "none") + " (v2p_batch_build_and_execute on the resident transcript stream)" if not args.host_image else "host-packed",
                        "fused_substitution_descriptors_rank0": leg.get("fused_substitution_descriptors"), "immediate_descriptors_rank0": leg.get("immediate_descriptors"),
                        "step": "v2p_batch_execute through the C ABI (ctypes), HIP events on the launch stream",
                        "parallelism": f"haplotype-sharded x{world}, no data-path collective; one all-gather of 16 B per rank per image (RCCL), outside the step loop" if world > 1 else "1 GPU"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "frac_definition": "physical",
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "bytes": "achieved = hbm_bytes_min / kernel time: result bytes written once + 8 B per descriptor + 16 B per chunk + alt bytes "
-                                  "outside descriptors + the proteome once (reference reads are served by L2 and not counted)",
-                         "hbm_bytes_min_per_launch": hbm_min,
-                         "algorithmic_bytes_per_launch": b_alg, "algorithmic_GBps": b_alg / (avg_ms * 1e-3) / 1e9,
-                         "frac_b_alg": b_alg / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "frac_b_alg_note": "SURVEY 8d's B_alg = 2A + 16N prices one HBM read per residue and 16 B per Task; the design serves reference reads from L2 and fuses "
-                                            "Task triples into 8-byte descriptors, so this ratio exceeds 1 without skipping work -- `frac` (physical bytes) is the roofline figure",
-                         "kernel": leg["kernel"] + ": a step = the image's phases, each read ahead into the memory-side cache (touch_image_kernel + stitch launches) -- kernel_ms is the whole step",
-                         "kernel_ms_avg": avg_ms, "kernel_ms_min": min(kern_ms),
-                         "box_fill_GBps": fill_gbps, "frac_of_box_fill": (achieved / fill_gbps) if fill_gbps else None,
-                         "box_fill_note": "this box's rate for a bare fill of 8 GiB (torch fill_), measured in this process: boxes of the pool differ by several per cent"},
+            "roofline": roofline,
             "comparable_to_previous_rounds": "since round 4 the N = 1 line is C3 whole (the north star's cohort), strong scaling, the size all-gather outside the step loop; "
                                              "rounds 1-3 reported C2 / weak.  Round 5: same metric and config as round 4; one_shot is now ONE C-ABI call on a resident stream",
             "kernel_only_aa_per_s_rank0": A / (avg_ms * 1e-3),
             "verified": leg["verified"], "stream_generation_s": leg.get("stream_generation_s"),
         }
+        if roofline is None:
+            del line["roofline"]
         for k in ("one_shot", "host_packed", "digests_equal_after_timed_steps", "image_form_timed", "dump_outputs"):
             if k in leg:
                 line[k] = leg[k]
@@ -868,7 +896,7 @@ def main():
                 line["speedup_method"] = "host wall-clock per step of the execute loop (barrier + synchronize on both sides), 1 GPU whole cohort / max over ranks"
         if args.dry_run:
             line["data"] = "synthetic (dry run: no kernel was launched, value is meaningless)"
-        if world == 1 and not args.dry_run:
+        if world == 1 and not args.dry_run and args.full:
             if not args.no_pcie:
                 # (right behind the headline leg, before the other cohorts come and go: 0.71 s here, 0.74-0.78 behind them)
                 ref_dig = leg.get("_oracle_checked_digests")

@@ -84,6 +84,17 @@ def test_zero_steps_and_a_dry_dump_are_refused():
         assert p.returncode == 2 and why in p.stderr, (extra, p.stderr)
 
 
+def test_the_oracle_check_is_part_of_a_full_run(monkeypatch):
+    """A plain run compares nothing with the oracle unless --verify asks for it; --full checks every haplotype by default."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for argv, full, verify in (([], False, "none"), (["--full"], True, "all"), (["--verify", "sample"], False, "sample"),
+                               (["--full", "--verify", "sample"], True, "sample"), (["--full", "--no-verify"], True, "none"), (["--full", "--dry-run"], True, "none")):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        a = bench.parse_args()
+        assert (a.full, a.verify) == (full, verify), argv
+
+
 class _FakeBatch:
     """The part of engine.Batch that bench.dump_outputs reads, over an arena whose byte at address a is a * 7 % 251."""
 

@@ -25,8 +25,8 @@ def run_bench(*extra):
 
 
 def test_two_ranks_strong_scaling_on_the_gpu(built, gpu_ctx):
-    one = run_bench("--gpus", "1", "--samples", "150", "--verify", "all")
-    two = run_bench("--gpus", "2", "--samples", "150", "--verify", "all")
+    one = run_bench("--gpus", "1", "--samples", "150", "--full")
+    two = run_bench("--gpus", "2", "--samples", "150", "--full")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["scaling"] == "strong" and two["config"]["workload"].startswith("C3")
     # N = 1: roofline.traffic is measured in the run itself (two child runs under rocprofv3 --pmc) -- at least the result bytes, no more than twice the minimum
     # (a box on which the profiler cannot collect counters leaves the replayed / null figure and says why: that is not this suite's failure)
@@ -100,3 +100,19 @@ def test_dumped_outputs_are_the_oracle_bytes_whatever_the_step_count(built, gpu_
             assert (hi << 32) | lo == coracle.digest_u8(want), h
         pos += w
     assert pos == a["sample_residues"].size
+
+
+def test_a_plain_run_times_what_a_full_run_times(built, gpu_ctx, tmp_path):
+    """Without --full the run only sets up, warms up, times and dumps: no oracle, no one-shot timings, no roofline -- and the timed steps
+    leave the same arena as those of a --full run, whose every haplotype the oracle checked."""
+    import numpy as np
+    plain = run_bench("--gpus", "1", "--samples", "150", "--dump-outputs", str(tmp_path / "plain"))
+    full = run_bench("--gpus", "1", "--samples", "150", "--full", "--no-live-traffic", "--dump-outputs", str(tmp_path / "full"))
+    assert plain["steps"] == full["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["verified"] is None and not {"one_shot", "roofline", "digests_equal_after_timed_steps"} & set(plain)
+    assert full["verified"]["every_haplotype"] is True and full["digests_equal_after_timed_steps"] is True and "one_shot" in full and "roofline" in full
+    assert plain["config"]["aa_rank0"] == full["config"]["aa_rank0"] and plain["config"]["haplotypes_rank0"] == full["config"]["haplotypes_rank0"] == 300
+    assert sorted(plain["dump_outputs"]["files"]) == sorted(full["dump_outputs"]["files"])
+    for name in plain["dump_outputs"]["files"]:
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
