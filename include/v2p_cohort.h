@@ -164,6 +164,26 @@ int  v2p_bgzf_compress_host(const uint8_t* in, const uint64_t* range_begin, uint
 /* worst-case output of n_bytes cut into n_ranges ranges (every member at most its input + 31 bytes) */
 uint64_t v2p_bgzf_bound(uint64_t n_bytes, uint64_t n_ranges);
 
+/* BGZF input.  V2P_ERR_GZIP (-28, include/v2p_frontend.h): a member that is not BGZF or does not inflate. */
+#ifndef V2P_ERR_GZIP
+#define V2P_ERR_GZIP            (-28)
+#endif
+/* The members of a BGZF file gz[0, n), walked by BSIZE of the BC extra subfield: each must start 1f 8b 08 with FLG.FEXTRA (no
+ * reserved FLG bits), hold a BC subfield (other subfields may come before it), fit the file and have ISIZE <= 65 536.  The EOF block
+ * is an empty member like any other.  member_begin / out_begin [capacity + 1]: member k is gz[member_begin[k], member_begin[k + 1])
+ * and inflates to [out_begin[k], out_begin[k + 1]) of the text; both null: only *n_members is computed.  On V2P_ERR_GZIP *n_members is
+ * the failing member's index k and, if k < capacity, member_begin[k] = its byte offset and out_begin[k + 1] = its reason (the
+ * status codes of v2p_bgzf_inflate_host).  V2P_ERR_INVALID_ARG when there are more than capacity members. */
+int  v2p_bgzf_members(const uint8_t* gz, uint64_t n, uint64_t* member_begin, uint64_t* out_begin, uint64_t capacity, uint64_t* n_members);
+/* Host emulation of v2p_bgzf_inflate_launch (include/vcf2prot_hip.h): the same decoder (vcf2prot_amd/csrc/inflate_format.hpp), the
+ * same bytes and statuses.  Member m of gz[member_begin[m], member_begin[m + 1]) inflates into out[out_begin[m], out_begin[m + 1]),
+ * written only if it is good.  status [n_members + 1]: status[m] = 0 or the member's reason -- 1 bad header, 2 bad block type,
+ * 3 stored length, 4 invalid or over-subscribed code lengths, 5 invalid code, 6 distance before the start of the member, 7 output
+ * longer than ISIZE, 8 input exhausted, 9 CRC mismatch, 10 ISIZE mismatch, 11 bytes after the trailer, 12 bad range;
+ * status[n_members] = the smallest failing member, ~0u if none.  Returns V2P_OK or V2P_ERR_GZIP. */
+int  v2p_bgzf_inflate_host(const uint8_t* gz, const uint64_t* member_begin, const uint64_t* out_begin, uint64_t n_members, uint8_t* out,
+                           uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ struct v2p_ctx;                                   /* include/vcf2prot_hip.h */
 #define V2P_ERR_CAPACITY        (-25)   /* raw launcher only: ids / multi-word capacity too small (needed size reported) */
 #define V2P_ERR_VCF_FORMAT      (-26)   /* readers.rs:113-150      no "#CHROM" line, fewer than 10 columns, no records */
 #define V2P_ERR_DUPLICATE_POS   (-27)   /* vcf_ds.rs:411           two different mutations on one reference position  */
+#ifndef V2P_ERR_GZIP
+#define V2P_ERR_GZIP            (-28)   /* a BGZF member that does not inflate (v2p_decode_inflate, include/v2p_cohort.h)  */
+#endif
 
 /* ---------------------------------------------------------------------------------------------------------
  * (1) record index (host)
@@ -90,6 +93,23 @@ int  v2p_decode_device(const v2p_decode* d, const uint64_t** d_hap_begin, const 
 /* kernel time of the last run in milliseconds (HIP events around the four kernels), for benches */
 int  v2p_decode_timing(const v2p_decode* d, float* ms_parse, float* ms_count, float* ms_scan, float* ms_emit);
 void v2p_decode_destroy(v2p_decode* d);
+
+/* BGZF input (a .vcf.gz as bgzip writes it), inflated on the device.  gz[0, n_gz): the compressed file, host memory; member_begin /
+ * out_begin [n_members + 1]: the member walk of v2p_bgzf_members (include/v2p_cohort.h).  Uploads the members, inflates every one into
+ * the padded device text of a new v2p_decode (16 readable bytes on each side, as v2p_decode_launch requires) and copies the text,
+ * out_begin[n_members] - out_begin[0] bytes, into text_out (host).  On a corrupt member returns V2P_ERR_GZIP with
+ * v2p_last_error_index(ctx) = the smallest failing member and v2p_last_error(ctx) = "corrupt BGZF member <m> at byte <offset>:
+ * <reason>"; nothing is written to text_out.  The v2p_decode holds no lists until v2p_decode_run_inflated; destroy it either way. */
+int  v2p_decode_inflate(struct v2p_ctx* ctx, const uint8_t* gz, uint64_t n_gz, const uint64_t* member_begin, const uint64_t* out_begin,
+                        uint64_t n_members, uint8_t* text_out, v2p_decode** out);
+/* v2p_decode_run on the text v2p_decode_inflate left on the device (no upload); row ranges are offsets in that text.  Afterwards
+ * v2p_decode_counts / _download / _device / _timing work as after v2p_decode_run.  On failure d keeps its text. */
+int  v2p_decode_run_inflated(struct v2p_ctx* ctx, v2p_decode* d,
+                             const uint64_t* row_begin, const uint64_t* row_end, uint64_t n_records, uint64_t n_samples,
+                             const uint32_t* csq_begin, const uint8_t* csq_supported);
+/* milliseconds of v2p_decode_inflate (HIP events): the upload of the members, the inflate kernel, the copy of the text to the host;
+ * zeros for a v2p_decode_run decode */
+int  v2p_decode_inflate_timing(const v2p_decode* d, float* ms_h2d, float* ms_inflate, float* ms_d2h);
 
 /* Raw launcher on device buffers the caller owns (benches, profilers).  All pointers are device pointers.
  *   d_text            the file text; 16 readable bytes before d_text and after d_text + n_text

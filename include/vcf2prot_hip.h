@@ -485,6 +485,14 @@ int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_
 uint64_t v2p_bgzf_workspace_bytes(uint64_t n_bytes, uint64_t n_ranges);
 int v2p_bgzf_launch(void* hip_stream, const uint8_t* d_in, const uint64_t* d_range_begin, uint64_t n_ranges, uint8_t* d_workspace,
                     uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_begin);
+/* BGZF input: gzip members inflated on the device (vcf2prot_amd/csrc/bgzf_inflate.hip), one wave64 workgroup per member, on caller-owned
+ * device memory, enqueued on hip_stream with no host wait.  Member m is d_in[d_member_begin[m], d_member_begin[m + 1]) and inflates to
+ * d_out[d_out_begin[m], d_out_begin[m + 1]) (at most 65 536 bytes: v2p_bgzf_members of include/v2p_cohort.h gives both arrays).  Every
+ * member is verified against its trailer (CRC32, ISIZE) and written only if good; a corrupt member reads and writes nothing outside
+ * its two ranges.  d_status [n_members + 1] u32: [m] = 0 or the member's reason (the codes of v2p_bgzf_inflate_host, whose bytes and
+ * statuses these equal), [n_members] = the smallest failing member, ~0u if none. */
+int v2p_bgzf_inflate_launch(void* hip_stream, const uint8_t* d_in, const uint64_t* d_member_begin, const uint64_t* d_out_begin,
+                            uint64_t n_members, uint8_t* d_out, uint32_t* d_status);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

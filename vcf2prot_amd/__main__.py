@@ -2,7 +2,10 @@
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
-CPU code and is refused."""
+CPU code and is refused.
+
+-f takes the VCF as text or compressed: a .vcf.gz as bgzip or `bcftools -O z` writes it (BGZF) is inflated on the GPU, member by member;
+any other gzip is inflated on the host first."""
 import argparse
 import os
 import subprocess
@@ -11,7 +14,7 @@ import sys
 
 def main() -> int:
     ap = argparse.ArgumentParser(prog="python -m vcf2prot_amd")
-    ap.add_argument("-f", "--vcf_file", required=True)
+    ap.add_argument("-f", "--vcf_file", required=True, help="the VCF: text, BGZF (.vcf.gz, inflated on the GPU) or other gzip")
     ap.add_argument("-r", "--fasta_ref", required=True)
     ap.add_argument("-o", "--output_path", required=True)
     ap.add_argument("-g", "--engine", default="gpu")

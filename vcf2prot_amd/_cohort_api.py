@@ -84,4 +84,6 @@ COHORT_API = {
     "v2p_cohort_pack_grid": (c_int, [c_void_p, c_uint64, c_uint64, c_uint32, c_int, POINTER(PackedImage)]),
     "v2p_bgzf_compress_host": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     "v2p_bgzf_bound": (c_uint64, [c_uint64, c_uint64]),
+    "v2p_bgzf_members": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, POINTER(c_uint64)]),
+    "v2p_bgzf_inflate_host": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
 }

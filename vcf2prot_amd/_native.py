@@ -106,6 +106,7 @@ HIP_API = {
     "v2p_batch_bgzf_download": (c_int, [c_void_p, c_uint64, c_uint64, c_void_p]),
     "v2p_bgzf_workspace_bytes": (c_uint64, [c_uint64, c_uint64]),
     "v2p_bgzf_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p]),
+    "v2p_bgzf_inflate_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
 }
 
 _hip = None

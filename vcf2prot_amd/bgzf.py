@@ -3,6 +3,8 @@ helpers that read what either side wrote.
 
     compress_host(data, range_begin) -> (z, out_begin)   v2p_bgzf_compress_host (include/v2p_cohort.h)
     members(z)                                         [(offset, size)] of every member, walked by BSIZE
+    walk(z)                                            v2p_bgzf_members: (member_begin, out_begin) for the inflater
+    inflate_host(z, member_begin, out_begin)           v2p_bgzf_inflate_host: (text, status) -- the emulation of the GPU inflater
     gzi(z)                                             bgzip's .gzi index of a BGZF file
     EOF_BLOCK                                          the 28-byte empty member that ends a BGZF file
 
@@ -80,3 +82,67 @@ def gzi(z) -> bytes:
             pairs.append((o, u))
         u += struct.unpack_from("<I", z, o + s - 4)[0]
     return struct.pack("<Q", len(pairs)) + b"".join(struct.pack("<QQ", c, d) for c, d in pairs)
+
+
+# member status codes of the inflater (include/v2p_cohort.h, vcf2prot_amd/csrc/inflate_format.hpp)
+REASONS = {0: "ok", 1: "bad gzip header", 2: "bad block type", 3: "stored block length does not match its complement",
+           4: "invalid or over-subscribed code lengths", 5: "invalid literal/length or distance code",
+           6: "distance before the start of the member", 7: "output longer than ISIZE", 8: "input exhausted", 9: "CRC mismatch",
+           10: "ISIZE mismatch", 11: "bytes after the member's trailer", 12: "bad member or output range",
+           13: "not a BGZF member (gzip header with a BC extra subfield)", 14: "ISIZE larger than 65536"}
+
+
+def is_bgzf(data) -> bool:
+    """1f 8b 08 with FLG.FEXTRA and a BC subfield in the first member's extra field."""
+    h = bytes(data[:65536 + 12])
+    if len(h) < 18 or h[:3] != b"\x1f\x8b\x08" or not h[3] & 4:
+        return False
+    xlen, x = struct.unpack_from("<H", h, 10)[0], 0
+    while x + 4 <= xlen and 12 + x + 4 <= len(h):
+        slen = struct.unpack_from("<H", h, 12 + x + 2)[0]
+        if h[12 + x:12 + x + 2] == b"BC" and slen == 2:
+            return True
+        x += 4 + slen
+    return False
+
+
+class GzipError(ValueError):
+    """a BGZF member that the walk or the inflater refuses: .member (index), .offset (byte), .reason (status code)"""
+
+    def __init__(self, member: int, offset: int, reason: int):
+        super().__init__(f"corrupt BGZF member {member} at byte {offset}: {REASONS.get(reason, reason)}")
+        self.member, self.offset, self.reason = member, offset, reason
+
+
+def walk(z):
+    """v2p_bgzf_members: (member_begin, out_begin), uint64 arrays [n_members + 1] -- member k is z[member_begin[k]:member_begin[k + 1]]
+    and inflates to text[out_begin[k]:out_begin[k + 1]].  Raises GzipError on bytes that are not BGZF."""
+    import ctypes
+    from ._native import V2PError, cohort_lib
+    buf = np.frombuffer(bytes(z), dtype=np.uint8)
+    lib = cohort_lib()
+    n = ctypes.c_uint64()
+    rc = lib.v2p_bgzf_members(buf.ctypes.data if buf.size else None, buf.size, None, None, 0, ctypes.byref(n))
+    cap = int(n.value) + 1
+    mb, ob = np.zeros(cap + 1, np.uint64), np.zeros(cap + 1, np.uint64)
+    rc2 = lib.v2p_bgzf_members(buf.ctypes.data if buf.size else None, buf.size, mb.ctypes.data, ob.ctypes.data, cap, ctypes.byref(n))
+    k = int(n.value)
+    if rc != 0 or rc2 != 0:
+        if rc2 == -28:
+            raise GzipError(k, int(mb[k]), int(ob[k + 1]))
+        raise V2PError(rc2 or rc, "v2p_bgzf_members")
+    return mb[:k + 1].copy(), ob[:k + 1].copy()
+
+
+def inflate_host(z, member_begin, out_begin):
+    """v2p_bgzf_inflate_host: (text: bytes, status: uint32 array [n_members + 1]) -- the host emulation of the GPU inflater; a bad member's
+    output bytes stay zero, status[m] is its reason and status[n_members] the smallest bad member (0xffffffff if none)."""
+    from ._native import cohort_lib
+    buf = np.frombuffer(bytes(z), dtype=np.uint8)
+    mb, ob = np.ascontiguousarray(member_begin, np.uint64), np.ascontiguousarray(out_begin, np.uint64)
+    n = mb.size - 1
+    out = np.zeros(max(int(ob[-1]) if n >= 0 and ob.size else 0, 1), np.uint8)
+    status = np.zeros(n + 1, np.uint32)
+    cohort_lib().v2p_bgzf_inflate_host(buf.ctypes.data if buf.size else None, mb.ctypes.data, ob.ctypes.data, n, out.ctypes.data,
+                                       status.ctypes.data)
+    return out[:int(ob[-1]) if ob.size else 0].tobytes(), status

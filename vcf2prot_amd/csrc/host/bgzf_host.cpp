@@ -6,6 +6,7 @@
 
 #include "../../../include/v2p_cohort.h"
 #include "../bgzf_format.hpp"
+#include "../inflate_format.hpp"
 
 namespace {
 
@@ -66,9 +67,64 @@ uint32_t encode_block(const uint8_t* in, uint32_t n, const uint32_t* crc_table, 
     return total;
 }
 
+// the inflater's wave on the host: one lane (inflate_format.hpp)
+struct HostWave {
+    uint32_t lane() const { return 0; }
+    uint32_t size() const { return 1; }
+    void sync() const {}
+    uint64_t ballot(bool p) const { return p ? 1u : 0u; }
+    uint32_t popc(uint64_t m) const { return uint32_t(__builtin_popcountll(m)); }
+    uint32_t rank(uint64_t) const { return 0; }
+    uint32_t xor_all(uint32_t v) const { return v; }
+};
+
 }  // namespace
 
 extern "C" {
+
+int v2p_bgzf_members(const uint8_t* gz, uint64_t n, uint64_t* member_begin, uint64_t* out_begin, uint64_t capacity, uint64_t* n_members)
+{
+    if (!n_members || (n && !gz) || (!member_begin != !out_begin)) return V2P_ERR_INVALID_ARG;
+    const bool fill = member_begin != nullptr;
+    uint64_t o = 0, k = 0, u = 0;
+    if (fill) { member_begin[0] = 0; out_begin[0] = 0; }
+    while (o < n) {
+        uint32_t size = 0, isize = 0;
+        const uint32_t r = infl::walk_member(gz, n, o, &size, &isize);
+        if (r != infl::OK) {
+            *n_members = k;
+            if (fill && k + 1 <= capacity) { member_begin[k] = o; out_begin[k + 1] = r; }
+            return V2P_ERR_GZIP;
+        }
+        if (fill && k + 1 > capacity) { *n_members = k; return V2P_ERR_INVALID_ARG; }
+        o += size; u += isize; ++k;
+        if (fill) { member_begin[k] = o; out_begin[k] = u; }
+    }
+    *n_members = k;
+    return V2P_OK;
+}
+
+int v2p_bgzf_inflate_host(const uint8_t* gz, const uint64_t* member_begin, const uint64_t* out_begin, uint64_t n_members, uint8_t* out,
+                          uint32_t* status)
+{
+    if (!status || (n_members && (!gz || !member_begin || !out_begin || !out))) return V2P_ERR_INVALID_ARG;
+    std::vector<infl::Scratch> sv(1);
+    infl::Scratch& s = sv[0];
+    HostWave w;
+    infl::fill_crc_table(w, s.crc);
+    uint32_t first = ~0u;
+    for (uint64_t m = 0; m < n_members; ++m) {
+        const uint64_t ob = out_begin[m], oe = out_begin[m + 1];
+        uint32_t n_done = 0, r;
+        if (oe < ob || oe - ob > infl::WINDOW) r = infl::BAD_RANGE;
+        else r = infl::inflate_member(w, s, gz, member_begin[m], member_begin[m + 1], uint32_t(oe - ob), &n_done);
+        if (r == infl::OK) memcpy(out + ob, s.window, oe - ob);
+        status[m] = r;
+        if (r != infl::OK && first == ~0u) first = uint32_t(m < 0xffffffffu ? m : 0xfffffffeu);
+    }
+    status[n_members] = first;
+    return first == ~0u ? V2P_OK : V2P_ERR_GZIP;
+}
 
 uint64_t v2p_bgzf_bound(uint64_t n_bytes, uint64_t n_ranges) { return bgzf::bound(n_bytes, n_ranges); }
 

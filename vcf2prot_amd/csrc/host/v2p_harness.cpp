@@ -7,6 +7,7 @@
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
 //   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
 //                                            steps 4-5 produce slices of probands that stream through v2p_pipeline_submit_stream while the next are made
 //   v2p_harness sharded <preset> <samples> --devices N [--oversubscribe] [--threads T] [--streamed [--slice-mb M]]
 //                                            the cohort over N devices in THIS process (ppgg::execute_sharded): N contexts, N worker
@@ -35,6 +36,7 @@
 
 #include "../../../include/v2p_cohort.h"
 #include "../../../include/v2p_step4a.h"
+#include "../inflate_format.hpp"
 #include "ppgg_gpu.hpp"
 
 using namespace ppgg;
@@ -278,6 +280,52 @@ static std::string bgzf_gzi(const std::vector<std::pair<const uint8_t*, uint64_t
 
 static const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
+// BGZF input: 1f 8b 08 with FLG.FEXTRA, and a BC subfield in the first member's extra field
+static bool is_bgzf(const std::string& f)
+{
+    const uint8_t* h = reinterpret_cast<const uint8_t*>(f.data());
+    if (f.size() < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4u)) return false;
+    const uint64_t xlen = h[10] | uint64_t(h[11]) << 8;
+    for (uint64_t x = 0; x + 4 <= xlen && 12 + x + 4 <= f.size();) {
+        const uint64_t slen = h[12 + x + 2] | uint64_t(h[12 + x + 3]) << 8;
+        if (h[12 + x] == 'B' && h[12 + x + 1] == 'C' && slen == 2) return true;
+        x += 4 + slen;
+    }
+    return false;
+}
+
+// any other gzip (one member or several, as gzip writes them): zlib on the host
+static bool gunzip(const std::string& gz, std::string& out, std::string& err)
+{
+    z_stream z{};
+    if (inflateInit2(&z, 16 + MAX_WBITS) != Z_OK) { err = "inflateInit2 failed"; return false; }
+    out.resize(gz.size() * 4 + (1u << 20));
+    uint64_t in_at = 0, out_at = 0;
+    int rc = Z_OK;
+    for (;;) {
+        if (out_at == out.size()) out.resize(out.size() * 2);
+        const uint64_t in_n = std::min<uint64_t>(gz.size() - in_at, 1u << 30), out_n = std::min<uint64_t>(out.size() - out_at, 1u << 30);
+        z.next_in = reinterpret_cast<Bytef*>(const_cast<char*>(gz.data()) + in_at); z.avail_in = uInt(in_n);
+        z.next_out = reinterpret_cast<Bytef*>(&out[0] + out_at); z.avail_out = uInt(out_n);
+        rc = inflate(&z, Z_NO_FLUSH);
+        in_at += in_n - z.avail_in; out_at += out_n - z.avail_out;
+        if (rc == Z_STREAM_END) {
+            if (in_at == gz.size()) break;
+            inflateReset(&z);                                        // the next member
+            continue;
+        }
+        if (rc == Z_BUF_ERROR && z.avail_out == 0) continue;
+        if (rc != Z_OK) {
+            err = std::string(z.msg ? z.msg : rc == Z_BUF_ERROR ? "unexpected end of file" : "inflate failed") + " at byte " + std::to_string(in_at);
+            inflateEnd(&z);
+            return false;
+        }
+    }
+    inflateEnd(&z);
+    out.resize(out_at);
+    return true;
+}
+
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
                     bool bgzf)
 {
@@ -286,22 +334,61 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     const auto t_start = clk::now();
     auto t0 = clk::now();
     double t_read, t_index, t_decode, t_group, t_build, t_exec, t_write;
-    const std::string vcf = slurp(vcf_path);
+    std::string vcf = slurp(vcf_path);
     const auto ref = read_fasta(slurp(fasta_path));
-    const uint8_t* text = reinterpret_cast<const uint8_t*>(vcf.data());
     t_read = since(t0); t0 = clk::now();
+    // the input: BGZF (a .vcf.gz from bgzip or `bcftools -O z`) inflated on the GPU into the decode's device text, any other gzip
+    // inflated here (it cannot be split), anything else the text itself
+    std::unique_ptr<GpuContext> ctx_box;
+    v2p_decode* dec = nullptr;                                      // BGZF: holds the inflated text on the device
+    const char* input_format = "text";
+    float ims[3] = {0, 0, 0};
+    if (is_bgzf(vcf)) {
+        input_format = "bgzf";
+        uint64_t n_members = 0;
+        const uint8_t* gz = reinterpret_cast<const uint8_t*>(vcf.data());
+        if (v2p_bgzf_members(gz, vcf.size(), nullptr, nullptr, 0, &n_members) != V2P_OK) {
+            std::vector<uint64_t> mb(n_members + 2), ob(n_members + 2);
+            uint64_t at = 0;
+            v2p_bgzf_members(gz, vcf.size(), mb.data(), ob.data(), n_members + 1, &at);
+            std::fprintf(stderr, "corrupt BGZF member %llu at byte %llu: %s\n", (unsigned long long)at, (unsigned long long)mb[at],
+                         infl::reason_text(uint32_t(ob[at + 1])));
+            return 101;
+        }
+        std::vector<uint64_t> mb(n_members + 1), ob(n_members + 1);
+        if (v2p_bgzf_members(gz, vcf.size(), mb.data(), ob.data(), n_members, &n_members) != V2P_OK) { std::fprintf(stderr, "BGZF member walk failed\n"); return 101; }
+        ctx_box.reset(new GpuContext());
+        std::string inflated(ob[n_members], '\0');
+        if (v2p_decode_inflate(ctx_box->raw(), gz, vcf.size(), mb.data(), ob.data(), n_members, reinterpret_cast<uint8_t*>(&inflated[0]), &dec) != V2P_OK) {
+            std::fprintf(stderr, "%s\n", v2p_last_error(ctx_box->raw()));
+            return 101;
+        }
+        v2p_decode_inflate_timing(dec, &ims[0], &ims[1], &ims[2]);
+        vcf.swap(inflated);
+    } else if (vcf.size() >= 2 && uint8_t(vcf[0]) == 0x1f && uint8_t(vcf[1]) == 0x8b) {
+        input_format = "gzip";
+        std::string inflated, err;
+        if (!gunzip(vcf, inflated, err)) { std::fprintf(stderr, "corrupt gzip input: %s\n", err.c_str()); return 101; }
+        vcf.swap(inflated);
+    }
+    const double t_inflate = since(t0); t0 = clk::now();
+    const uint8_t* text = reinterpret_cast<const uint8_t*>(vcf.data());
     v2p_vcf_index* idx = nullptr;
     if (v2p_vcf_index_build(text, vcf.size(), &idx) != 0) {
         std::fprintf(stderr, "reading the file failed: %s\n", v2p_vcf_index_error(idx));
+        if (dec) v2p_decode_destroy(dec);
         return 101;
     }
     const uint64_t S = v2p_vcf_index_n_samples(idx), R = v2p_vcf_index_n_records(idx);
     t_index = since(t0); t0 = clk::now();
-    GpuContext ctx;
-    v2p_decode* dec = nullptr;
-    if (v2p_decode_run(ctx.raw(), text, vcf.size(), v2p_vcf_index_row_begin(idx), v2p_vcf_index_row_end(idx), R, S,
-                       v2p_vcf_index_csq_begin(idx), v2p_vcf_index_csq_supported(idx), &dec) != V2P_OK) {
+    if (!ctx_box) ctx_box.reset(new GpuContext());
+    GpuContext& ctx = *ctx_box;
+    if (dec ? v2p_decode_run_inflated(ctx.raw(), dec, v2p_vcf_index_row_begin(idx), v2p_vcf_index_row_end(idx), R, S,
+                                      v2p_vcf_index_csq_begin(idx), v2p_vcf_index_csq_supported(idx)) != V2P_OK
+            : v2p_decode_run(ctx.raw(), text, vcf.size(), v2p_vcf_index_row_begin(idx), v2p_vcf_index_row_end(idx), R, S,
+                             v2p_vcf_index_csq_begin(idx), v2p_vcf_index_csq_supported(idx), &dec) != V2P_OK) {
         std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw()));
+        if (dec) v2p_decode_destroy(dec);
         return 101;
     }
     std::vector<uint64_t> hap_begin(2 * S + 1);
@@ -587,11 +674,12 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
                 (unsigned long long)written, outdir);
     std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
-                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f}, "
-                "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}}\n",
+                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f}, "
+                "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}, \"input_format\": \"%s\", "
+                "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}}\n",
                 (unsigned long long)R, (unsigned long long)S, (unsigned long long)written, (unsigned long long)n_slices, (unsigned long long)n_fallback,
                 t_read, t_index, t_decode, t_group, t_build, t_exec, t_write,
-                since(t_start), kms[0], kms[1], kms[2], kms[3]);
+                since(t_start), t_inflate, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
     v2p_batch_destroy(b);
     v2p_groups_destroy(g);
     v2p_vcf_index_destroy(idx);

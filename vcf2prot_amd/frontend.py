@@ -4,6 +4,12 @@
     lists  = decode_bitmasks(ctx, idx)               # VCFRecords::get_csq_per_patient on the GPU (vcf_ds.rs:192-329)
     groups = group_per_transcript(idx, lists)        # vcf_tools.rs:82-96 + vcf_ds.rs:387-420, host
 
+A .vcf.gz as bgzip writes it (BGZF) is inflated on the GPU first, and its text stays there for the decode:
+
+    text, resident = inflate_bgzf(ctx, gz_bytes)     # v2p_decode_inflate: the text on the device and here
+    idx    = VcfIndex(text)
+    lists  = decode_bitmasks(ctx, idx, resident)     # v2p_decode_run_inflated: no second upload
+
 The decode has no CPU path: without the HIP library / a GPU it raises.
 """
 from __future__ import annotations
@@ -17,8 +23,10 @@ from . import _native as N
 
 V2P_ERR_MASK_NEGATIVE, V2P_ERR_MASK_PARSE, V2P_ERR_MASK_INDEX, V2P_ERR_COLUMNS = -20, -21, -22, -23
 V2P_ERR_FIELD_TOO_LONG, V2P_ERR_CAPACITY, V2P_ERR_VCF_FORMAT, V2P_ERR_DUPLICATE_POS = -24, -25, -26, -27
+V2P_ERR_GZIP = -28
 N.ERR_NAMES.update({-20: "V2P_ERR_MASK_NEGATIVE", -21: "V2P_ERR_MASK_PARSE", -22: "V2P_ERR_MASK_INDEX", -23: "V2P_ERR_COLUMNS",
-                    -24: "V2P_ERR_FIELD_TOO_LONG", -25: "V2P_ERR_CAPACITY", -26: "V2P_ERR_VCF_FORMAT", -27: "V2P_ERR_DUPLICATE_POS"})
+                    -24: "V2P_ERR_FIELD_TOO_LONG", -25: "V2P_ERR_CAPACITY", -26: "V2P_ERR_VCF_FORMAT", -27: "V2P_ERR_DUPLICATE_POS",
+                    -28: "V2P_ERR_GZIP"})
 
 
 class v2p_mutation(ctypes.Structure):
@@ -37,6 +45,9 @@ DECODE_API = {
     "v2p_decode_workspace_bytes": (c_uint64, [c_uint64, c_uint64, c_uint64]),
     "v2p_decode_launch": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, ctypes.c_uint]),
+    "v2p_decode_inflate": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
+    "v2p_decode_run_inflated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "v2p_decode_inflate_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -154,12 +165,65 @@ class HaplotypeLists:
         return self.ids[int(self.hap_begin[h]):int(self.hap_begin[h + 1])]
 
 
-def decode_bitmasks(ctx, idx: VcfIndex) -> HaplotypeLists:
-    """VCFRecords::get_csq_per_patient (vcf_ds.rs:192-211) for every proband, on the GPU of `ctx` (engine.Context)."""
+def input_format(data) -> str:
+    """"bgzf" (1f 8b 08 with FLG.FEXTRA and a BC subfield in the first member), "gzip" (any other gzip) or "text"."""
+    from .bgzf import is_bgzf
+    b = bytes(data[:2])
+    return "bgzf" if is_bgzf(data) else "gzip" if b == b"\x1f\x8b" else "text"
+
+
+class InflatedText:
+    """The text of a BGZF file inflated on the GPU (v2p_decode_inflate), resident for decode_bitmasks."""
+
+    def __init__(self, ctx, h, n_text: int):
+        self.ctx, self._h, self.n_text = ctx, h, n_text
+
+    def timing_ms(self) -> dict:
+        t = [c_float() for _ in range(3)]
+        _hip().v2p_decode_inflate_timing(self._h, *[ctypes.byref(x) for x in t])
+        return dict(zip(("h2d", "inflate", "d2h"), (x.value for x in t)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _hip().v2p_decode_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def inflate_bgzf(ctx, gz):
+    """BGZF bytes -> (text: bytes, InflatedText): every member inflated on the GPU of `ctx` into the decode's device text, the text copied
+    back once for the host index.  A corrupt member raises V2PError(V2P_ERR_GZIP) with the member's index."""
+    from .bgzf import walk
+    gz = bytes(gz)
+    mb, ob = walk(gz)
     lib = _hip()
+    buf = np.frombuffer(gz, dtype=np.uint8)
+    text = np.empty(max(int(ob[-1] - ob[0]), 1), dtype=np.uint8)
     h = c_void_p()
-    rc = lib.v2p_decode_run(ctx._h, idx.text.ctypes.data, idx.text.size, idx.row_begin.ctypes.data, idx.row_end.ctypes.data,
-                            idx.n_records, idx.n_samples, idx.csq_begin.ctypes.data, idx.csq_supported.ctypes.data, ctypes.byref(h))
+    rc = lib.v2p_decode_inflate(ctx._h, buf.ctypes.data if buf.size else None, buf.size, mb.ctypes.data, ob.ctypes.data, mb.size - 1,
+                                text.ctypes.data, ctypes.byref(h))
+    if rc != 0:
+        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    return text[:int(ob[-1] - ob[0])].tobytes(), InflatedText(ctx, h, int(ob[-1] - ob[0]))
+
+
+def decode_bitmasks(ctx, idx: VcfIndex, inflated: "InflatedText" = None) -> HaplotypeLists:
+    """VCFRecords::get_csq_per_patient (vcf_ds.rs:192-211) for every proband, on the GPU of `ctx` (engine.Context).  inflated: the text
+    of idx is already on the device (inflate_bgzf); the decode runs on it and `inflated` is used up."""
+    lib = _hip()
+    if inflated is not None:
+        h = inflated._h
+        inflated._h = None
+        rc = lib.v2p_decode_run_inflated(ctx._h, h, idx.row_begin.ctypes.data, idx.row_end.ctypes.data, idx.n_records, idx.n_samples,
+                                         idx.csq_begin.ctypes.data, idx.csq_supported.ctypes.data)
+        if rc != 0:
+            lib.v2p_decode_destroy(h)
+    else:
+        h = c_void_p()
+        rc = lib.v2p_decode_run(ctx._h, idx.text.ctypes.data, idx.text.size, idx.row_begin.ctypes.data, idx.row_end.ctypes.data,
+                                idx.n_records, idx.n_samples, idx.csq_begin.ctypes.data, idx.csq_supported.ctypes.data, ctypes.byref(h))
     if rc != 0:
         raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
     try:

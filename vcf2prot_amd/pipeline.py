@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _native as N
 from . import step4a
-from .frontend import VcfIndex, decode_bitmasks, group_per_transcript
+from .frontend import VcfIndex, decode_bitmasks, group_per_transcript, inflate_bgzf, input_format
 from .step4b import inspect_transcript_tasks, transcript_g_rep
 
 
@@ -56,11 +56,24 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     the record text on the device, the text back in pinned host memory) while steps 4a / 4b of the next probands run here;
     False: the host builder (v2p_batch_add_transcript), one image -- same bytes.
     bgzf: {proband: text of <proband>.fasta.gz} instead -- BGZF compressed on the device (bgzf.py): haplotype 1's members, haplotype 2's
-    members, then the EOF block."""
+    members, then the EOF block.
+    vcf may be the bytes of a .vcf.gz: BGZF is inflated on the device and its text stays there for the decode (frontend.inflate_bgzf);
+    any other gzip is inflated here."""
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
-    idx = VcfIndex(vcf)
-    lists = decode_bitmasks(ctx, idx)
+    fmt, inflated = input_format(vcf), None
+    if fmt == "bgzf":
+        vcf, inflated = inflate_bgzf(ctx, vcf)
+    elif fmt == "gzip":
+        import gzip
+        vcf = gzip.decompress(bytes(vcf))
+    try:
+        idx = VcfIndex(vcf)
+    except N.V2PError:
+        if inflated is not None:
+            inflated.close()
+        raise
+    lists = decode_bitmasks(ctx, idx, inflated)
     groups = group_per_transcript(idx, lists)
     names = [groups.transcript_name(r) for r in range(groups.n_transcripts)]
     if write_all:
