@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from whole_util import oracle_digests
+
 pytestmark = pytest.mark.gpu
 
 
@@ -40,7 +42,6 @@ def test_c3_whole_cohort_on_one_gpu_every_haplotype_by_digest(built, gpu_ctx, co
     the digest of EVERY haplotype equals the digest of the oracle's result -- for the image the PRODUCT builds (on the device, from
     the per-transcript Task vectors: v2p_batch_build_on_device, kernel 6 -- haplotype_instruction.rs:94-133 as kernels) and for the
     host-packed image of the same haplotypes."""
-    from concurrent.futures import ThreadPoolExecutor
     from vcf2prot_amd.cohort import Cohort
     from vcf2prot_amd.txstream import build_on_device_auto
     c = Cohort.preset("C3")
@@ -66,6 +67,7 @@ def test_c3_whole_cohort_on_one_gpu_every_haplotype_by_digest(built, gpu_ctx, co
     db.execute()                                             # executed again: descriptors staged by the read-ahead, 44 MB phases (round 5)
     db.sync()
     assert np.array_equal(db.digests(), dig_dev) and db.image_form()["staging_buffers"]
+    db.scribble()                                            # the one call's first execute below must not find this answer in recycled pages
     db.close()
     # ... and the ONE call of round 5 (v2p_stream_upload + v2p_batch_build_and_execute): the image stays PADDED, its first execute reads
     # staged descriptors; the first re-execute makes it dense -- every form must leave the arena the two-call builder's image leaves
@@ -84,6 +86,7 @@ def test_c3_whole_cohort_on_one_gpu_every_haplotype_by_digest(built, gpu_ctx, co
     assert not ob.image_form()["padded"] and np.array_equal(ob.digests(), dig_dev), "the one call's image, made dense and executed again"
     _, _, hb1 = ob.download_image()
     assert np.array_equal(hb1, hb) and ob.counts() == cn
+    ob.scribble()
     ob.close()
     rs.close()
     # the host packer's image
@@ -96,22 +99,9 @@ def test_c3_whole_cohort_on_one_gpu_every_haplotype_by_digest(built, gpu_ctx, co
     b.execute()
     b.sync()
     dig = b.digests()
+    b.scribble()
     b.close()
-    workers = min(64, os.cpu_count() or 1)
-
-    def oracle_digests(w):
-        cc = Cohort.preset("C3")
-        out = {}
-        for h in range(w, n, workers):
-            hap = cc.haplotype(h)
-            t = coracle.pack_tasks(hap.code, hap.start_pos, hap.length, hap.start_pos_res)
-            want = coracle.gir_execute_u8(t, cc.ref_tape_u32(h).astype(np.uint8), hap.alt, np.full(hap.n_res, ord("."), dtype=np.uint8))
-            out[h] = coracle.digest_u8(want)
-        return out
-    want = {}
-    with ThreadPoolExecutor(workers) as pool:
-        for part in pool.map(oracle_digests, range(workers)):
-            want.update(part)
+    want = oracle_digests("C3")
     bad = [h for h in range(n) if int(dig_dev[h]) != want[h]]
     assert not bad, ("device-built image", bad[:10])
     bad = [h for h in range(n) if int(dig[h]) != want[h]]
@@ -123,7 +113,6 @@ def test_c2_whole_cohort_through_the_one_call_and_the_stream_pipeline(built, gpu
     product's one call (v2p_stream_upload + v2p_batch_build_and_execute) and, slice by slice with the results returning to the host,
     through the stream-fed pipeline (v2p_pipeline_submit_stream): the digest of EVERY haplotype is the oracle's, and what comes back over
     the link digests the same on the host."""
-    from concurrent.futures import ThreadPoolExecutor
     from vcf2prot_amd.cohort import Cohort
     from vcf2prot_amd.driver import run_streamed
     c = Cohort.preset("C2")
@@ -143,22 +132,8 @@ def test_c2_whole_cohort_through_the_one_call_and_the_stream_pipeline(built, gpu
     dig = b.digests()
     b.scribble(); b.execute(); b.sync()
     assert np.array_equal(b.digests(), dig), "the re-executed image left another arena"
-    b.close(); rs.close()
-    workers = threads
-
-    def oracle_digests(w):
-        cc = Cohort.preset("C2")
-        out = {}
-        for h in range(w, n, workers):
-            hap = cc.haplotype(h)
-            t = coracle.pack_tasks(hap.code, hap.start_pos, hap.length, hap.start_pos_res)
-            want = coracle.gir_execute_u8(t, cc.ref_tape_u32(h).astype(np.uint8), hap.alt, np.full(hap.n_res, ord("."), dtype=np.uint8))
-            out[h] = coracle.digest_u8(want)
-        return out
-    want = {}
-    with ThreadPoolExecutor(workers) as pool:
-        for part in pool.map(oracle_digests, range(workers)):
-            want.update(part)
+    b.scribble(); b.close(); rs.close()
+    want = oracle_digests("C2")
     bad = [h for h in range(n) if int(dig[h]) != want[h]]
     assert not bad, ("the one call", bad[:10])
     seen = 0

@@ -5,31 +5,13 @@ every haplotype against the oracle; then the same cohort the way eight ranks wou
 after the other -- must reproduce the single launch: per-haplotype digests, and the byte offsets the size all-gather derives
 (shard.layout_from_sizes) must be the single arena's own haplotype offsets."""
 import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+from whole_util import oracle_digests
+
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_digests(preset, coracle, n, workers):
-    from vcf2prot_amd.cohort import Cohort
-
-    def work(w):
-        cc = Cohort.preset(preset)                     # own generator state per thread
-        out = {}
-        for h in range(w, n, workers):
-            hap = cc.haplotype(h)
-            t = coracle.pack_tasks(hap.code, hap.start_pos, hap.length, hap.start_pos_res)
-            want = coracle.gir_execute_u8(t, cc.ref_tape_u32(h).astype(np.uint8), hap.alt, np.full(hap.n_res, ord("."), dtype=np.uint8))
-            out[h] = coracle.digest_u8(want)
-        return out
-    res = {}
-    with ThreadPoolExecutor(workers) as pool:
-        for part in pool.map(work, range(workers)):
-            res.update(part)
-    return np.array([res[h] for h in range(n)], dtype=np.uint64)
 
 
 def _run_device_built(gpu_ctx, c, n, threads, kernel):
@@ -51,6 +33,7 @@ def _run_device_built(gpu_ctx, c, n, threads, kernel):
     b.sync()
     assert np.array_equal(np.array(b.digests(), dtype=np.uint64), dig), "the re-executed image left another arena"
     assert b.image_form()["pieces"] == (kernel == 7)
+    b.scribble()                                   # no later first execute may find this answer in recycled pages
     b.close()
     return dig, hb.astype(np.int64), cn
 
@@ -62,6 +45,7 @@ def _run(gpu_ctx, img):
     b.execute()
     b.sync()
     dig = np.array(b.digests(), dtype=np.uint64)
+    b.scribble()                                   # no later first execute may find this answer in recycled pages
     b.close()
     return dig
 
@@ -80,7 +64,7 @@ def test_whole_cohort_one_launch_and_as_eight_shards(built, gpu_ctx, coracle, pr
     whole_begin = img.hap_out_begin.astype(np.int64)
     whole = _run(gpu_ctx, img)
     del img
-    want = _oracle_digests(preset, coracle, n, min(32, os.cpu_count() or 1))
+    want = oracle_digests(preset)
     bad = np.nonzero(whole != want)[0]
     assert bad.size == 0, (preset, bad[:10])
     # ... and the device-built image of the whole cohort (C4: kernel 6, wave rows image over the 56 MB proteome, 30 GB of arena; C5:
