@@ -476,6 +476,14 @@ int v2p_routing_rules(uint64_t n_desc, uint64_t n_chunks, uint64_t result_bytes,
  * order first if it is not.  v2p_batch_finalize() does this itself (v2p_batch_build_on_device the same on the device); callers of v2p_stitch_launch_opts() may want it too.  Speed only: chunks are independent. */
 int v2p_order_chunks_for_xcds(v2p_chunk* chunks, uint64_t n_chunks, const uint64_t* desc, uint64_t n_desc,
                               uint64_t proteome_len);
+/* The digest kernel of v2p_batch_digests (the definition is given there) on caller-owned device memory, enqueued on hip_stream with no
+ * host wait: haplotype h is d_out[d_hap_begin[h], d_hap_begin[h + 1]), d_hap_begin [n_haps + 1] ascending (equal neighbours: an empty
+ * haplotype, digest 0).  d_digests [n_haps] is ADDED TO (mod 2^64, device atomics), never stored: zero it on the stream first, or
+ * accumulate on purpose; d_out and d_hap_begin are only read, and no byte outside d_out[0, out_bytes) is.  d_out may have any alignment
+ * (a 16-byte aligned one takes the fast path).  n_haps == 0 or out_bytes == 0: V2P_OK, nothing launched or written; otherwise a NULL
+ * d_out, d_hap_begin or d_digests is V2P_ERR_INVALID_ARG.  The launcher cannot look into device memory without a wait, so two things are
+ * the CALLER'S obligation and undefined if broken: d_hap_begin[0] == 0 (bytes in front of the first haplotype are not skipped) and
+ * out_bytes == d_hap_begin[n_haps] (the grid is sized by the one, the walk by the other).  Pinned by tests/test_gpu_digest.py. */
 int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_hap_begin, uint64_t n_haps,
                       uint64_t out_bytes, uint64_t* d_digests);
 /* BGZF members of the ranges [d_range_begin[r], d_range_begin[r + 1]) of d_in (ascending; n_bytes = their span) on caller-owned device

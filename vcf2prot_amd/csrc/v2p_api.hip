@@ -3704,8 +3704,10 @@ int v2p_stitch_launch(void* hip_stream,
 int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_hap_begin, uint64_t n_haps,
                       uint64_t out_bytes, uint64_t* d_digests)
 {
+    if (n_haps == 0 || out_bytes == 0) return V2P_OK;             // nothing to digest: nothing is launched, nothing written
+    if (!d_out || !d_hap_begin || !d_digests) return V2P_ERR_INVALID_ARG;
     DigestArgs a{d_out, d_hap_begin, n_haps, d_digests};
-    return launch_digest(a, out_bytes, reinterpret_cast<hipStream_t>(hip_stream)) == hipSuccess ? V2P_OK : V2P_ERR_HIP;
+    return launch_digest(a, out_bytes,reinterpret_cast<hipStream_t>(hip_stream)) == hipSuccess ? V2P_OK : V2P_ERR_HIP;
 }
 
 int v2p_stitch_launch_bits(const v2p_chunk* chunks, uint64_t n_chunks)
