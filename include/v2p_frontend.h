@@ -12,9 +12,12 @@
  *                         SUP_TYPE filter of decode_back (vcf_ds.rs:213-329).
  *   (3) v2p_groups_*      host, O(n log n) per haplotype: group_muts_per_transcript (vcf_tools.rs:82-96, quadratic
  *                         in the reference) + AltTranscript::drop_replicate (vcf_ds.rs:387-420), in id space.
+ *   (4) -s / --stats      the three tables of summary.rs:10-32 (exec.rs:45-64): v2p_csq_tables_* (host) are the file-wide
+ *                         per-consequence tables the grouping rule needs, v2p_decode_stats (device) counts the tables on the
+ *                         id lists the decode left on the GPU, v2p_groups_stats (host) reads them off the grouped CSR.
  *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
- * libvcf2prot_hip.so exports (2); libv2p_cohort.so (plain C++) exports (1) and (3).
+ * libvcf2prot_hip.so exports (2) and the v2p_decode_stats* calls of (4); libv2p_cohort.so (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -165,6 +168,66 @@ const uint64_t* v2p_groups_hap_group_begin(const v2p_groups* g);
 const uint32_t* v2p_groups_group_transcript(const v2p_groups* g);
 const uint64_t* v2p_groups_group_member_begin(const v2p_groups* g);
 const uint32_t* v2p_groups_member_ids(const v2p_groups* g);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (4) cohort statistics (-s / --stats).  For haplotype list L: present(L) = the distinct rank[id] != ~0u; the members of group r
+ * are the ids of L with mut_ok and (rank[id] == r or r among extra[id]), in list order, stably sorted by mut_pos, after
+ * drop_replicate.  per_proband[s] = |present(2s)| + |present(2s+1)|; per_type[22*s + t] = surviving members of type t over all
+ * groups of both lists; per_transcript[r] = the number of lists of the file with r in present.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct v2p_csq_tables v2p_csq_tables;
+
+/* The file-wide phase of v2p_groups_build on its own: every supported consequence parsed once.  n_threads = 0 -> hardware threads. */
+int  v2p_csq_tables_build(const v2p_vcf_index* x, const uint8_t* text, uint32_t n_threads, v2p_csq_tables** out);
+void v2p_csq_tables_destroy(v2p_csq_tables* t);
+uint64_t v2p_csq_tables_n_consequences(const v2p_csq_tables* t);
+uint64_t v2p_csq_tables_n_transcripts(const v2p_csq_tables* t);                 /* unique transcript ids of the file, sorted */
+int  v2p_csq_tables_transcript(const v2p_csq_tables* t, uint64_t rank, uint64_t* begin, uint64_t* len);     /* id text */
+const uint64_t* v2p_csq_tables_transcript_begin(const v2p_csq_tables* t);       /* [n_transcripts] the same ranges as arrays */
+const uint32_t* v2p_csq_tables_transcript_len(const v2p_csq_tables* t);
+const uint32_t* v2p_csq_tables_rank(const v2p_csq_tables* t);                   /* [n_consequences] own transcript rank, ~0u = the string does not split */
+const uint32_t* v2p_csq_tables_flags(const v2p_csq_tables* t);                  /* [n_consequences] bit 0 mut_ok (Mutation::new is Ok), bit 1 poison
+                                                                                   (text_parser.rs:52 would abort), bits 8-15 index into SUP_TYPE */
+const uint16_t* v2p_csq_tables_mut_pos(const v2p_csq_tables* t);                /* [n_consequences] 0-based, of a mut_ok consequence */
+const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t);
+const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t);                  /* [n_consequences] identity class of drop_replicate's dedup_by, ~0u if not mut_ok */
+const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t);            /* [n_consequences + 1] CSR of ... */
+const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t);                  /* ... the OTHER transcript ranks whose id occurs in the text, ascending */
+
+/* The three tables read off the grouped CSR of a successful v2p_groups_build over 2 * n_samples lists.  per_proband[n_samples],
+ * per_type[22 * n_samples], per_transcript[v2p_groups_n_transcripts]. */
+int  v2p_groups_stats(const v2p_groups* g, uint64_t n_samples, uint64_t* per_proband, uint64_t* per_type, uint64_t* per_transcript);
+
+/* Fixed sizes of the statistics kernel, per haplotype list (one workgroup, everything in LDS); 0 = chosen from the file.  A list over
+ * a limit is REFUSED: nothing is counted for it and it is reported, never truncated. */
+typedef struct v2p_stats_caps {
+    uint32_t bitmap_words;      /* present-set bitmap: a list with a transcript rank >= 32 * bitmap_words is refused */
+    uint32_t filter_words;      /* collision pre-filter, a power of two; its size changes how many groups take the sorted path, not results */
+    uint32_t sort_capacity;     /* members of groups that may hold a repeated ref_pos, per list, a power of two; more -> refused */
+} v2p_stats_caps;
+typedef struct v2p_stats_info {
+    uint64_t n_refused;         /* lists the kernel refused (indices: v2p_decode_stats_refused) */
+    uint64_t n_sorted_members;  /* members that went through the sorted drop_replicate path, file-wide */
+    uint32_t bitmap_words, filter_words, sort_capacity, lds_bytes;      /* what was launched */
+} v2p_stats_info;
+
+/* The three tables counted on the device from the lists v2p_decode_run / v2p_decode_run_inflated left there; the ids never cross the
+ * link.  The table arrays are host pointers (the v2p_csq_tables_* accessors), uploaded once per call; tx_text / tx_begin / tx_len name
+ * the transcripts in error messages (may be null).  The outputs are host arrays, 8 * (23 * n_samples + n_transcripts) bytes in all.
+ * An abort of the reference (drop_replicate's panic, a poison id) returns V2P_ERR_DUPLICATE_POS with v2p_last_error_index(ctx) = the
+ * smallest aborting list among those the kernel did not refuse and v2p_last_error(ctx) naming the transcript; info is filled in
+ * either way, and a caller with refused lists completes them on the host (v2p_groups_build + v2p_groups_stats) and takes the smaller
+ * index.  caps may be null. */
+int  v2p_decode_stats(struct v2p_ctx* ctx, v2p_decode* d,
+                      const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos, const uint32_t* ident,
+                      const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_consequences, uint64_t n_transcripts,
+                      const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len,
+                      uint64_t* per_proband, uint64_t* per_type, uint64_t* per_transcript,
+                      const v2p_stats_caps* caps, v2p_stats_info* info);
+/* lists[info.n_refused] of the last v2p_decode_stats on d, ascending */
+int  v2p_decode_stats_refused(const v2p_decode* d, uint64_t* lists);
+/* milliseconds of the last v2p_decode_stats on d (HIP events): the upload of the tables, the kernel */
+int  v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_kernel);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -103,6 +103,9 @@ Parsed parse_csq(std::string_view s)
 
 struct Table {
     std::vector<Parsed> parsed;
+    std::vector<uint32_t> flags;                 // v2p_csq_tables_flags: bit 0 mut_ok, bit 1 poison, bits 8-15 type
+    std::vector<uint16_t> mut_pos, ref_pos;
+    std::vector<uint64_t> tx_begin; std::vector<uint32_t> tx_len;      // unique transcript ids (text ranges), sorted
     std::vector<uint32_t> rank;                  // own transcript rank, ~0u if split failed
     std::vector<uint32_t> ident;                 // identity class of drop_replicate's dedup_by (vcf_ds.rs:399-406)
     std::vector<uint32_t> extra_begin, extra;    // other transcript ranks whose id occurs in the consequence text
@@ -113,17 +116,13 @@ constexpr uint64_t HB = 0x100000001B3ull;
 
 }  // namespace
 
-extern "C" {
+struct v2p_csq_tables { Table T; };
 
-int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint64_t* hap_begin, const uint32_t* ids,
-                     uint64_t n_haps, uint32_t n_threads, v2p_groups** out)
+namespace {
+
+// the file-wide phase: every consequence parsed once, the transcript ranks, the identity classes, the substring matches
+void build_tables(Table& T, const v2p_vcf_index* x, const uint8_t* text_u8, uint32_t n_threads)
 {
-    if (!out) return -1;
-    *out = nullptr;
-    if (!x || !text_u8 || !hap_begin || (!ids && hap_begin[n_haps])) return -1;
-    v2p_groups* g = new (std::nothrow) v2p_groups();
-    if (!g) return -1;
-    *out = g;
     const char* text = reinterpret_cast<const char*>(text_u8);
     const uint64_t n_csq = v2p_vcf_index_n_consequences(x);
     const uint64_t* tb = v2p_vcf_index_csq_text_begin(x);
@@ -141,7 +140,6 @@ int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint6
         return nt;
     };
 
-    Table T;
     T.parsed.resize(n_csq);
     parallel_csq([&](uint64_t b, uint64_t e, uint32_t) {
         for (uint64_t i = b; i < e; ++i)
@@ -160,31 +158,29 @@ int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint6
     rank_of.reserve(T.names.size() * 2);
     for (uint32_t r = 0; r < T.names.size(); ++r) {
         rank_of.emplace(T.names[r], r);
-        g->tx_begin.push_back(uint64_t(T.names[r].data() - text));
-        g->tx_len.push_back(uint32_t(T.names[r].size()));
+        T.tx_begin.push_back(uint64_t(T.names[r].data() - text));
+        T.tx_len.push_back(uint32_t(T.names[r].size()));
     }
     T.rank.assign(n_csq, ~0u);
     T.ident.assign(n_csq, ~0u);
-    g->muts.resize(n_csq);
-    g->aa.resize(n_csq);
+    T.flags.assign(n_csq, 0u);
+    T.mut_pos.assign(n_csq, 0);
+    T.ref_pos.assign(n_csq, 0);
     {
         std::unordered_map<std::string, uint32_t> classes;
         std::string key;
         for (uint64_t i = 0; i < n_csq; ++i) {
             const Parsed& p = T.parsed[i];
-            v2p_mutation m{};
-            m.transcript = ~0u;
-            if (p.split_ok) { T.rank[i] = rank_of[p.tx]; m.transcript = T.rank[i]; }
+            if (p.split_ok) T.rank[i] = rank_of[p.tx];
+            if (p.poison) T.flags[i] |= 2u;
             if (p.mut_ok) {
-                m.valid = 1; m.type = uint8_t(p.type); m.ref_aa_position = p.ref_pos; m.mut_aa_position = p.mut_pos;
+                T.flags[i] |= 1u | uint32_t(p.type) << 8; T.ref_pos[i] = p.ref_pos; T.mut_pos[i] = p.mut_pos;
                 key.assign(1, char(p.type));
                 key.append(reinterpret_cast<const char*>(&p.ref_pos), 2).append(reinterpret_cast<const char*>(&p.mut_pos), 2);
                 key.append(p.ref_aa).push_back('>');
                 key.append(p.mut_aa);
                 T.ident[i] = classes.emplace(key, uint32_t(classes.size())).first->second;
             }
-            g->muts[i] = m;
-            if (p.mut_ok) { g->aa[i].ref_aa = p.ref_aa; g->aa[i].mut_aa = p.mut_aa; }
         }
     }
     // str::contains of vcf_tools.rs:91: which OTHER transcript ids occur somewhere in a consequence's text
@@ -235,6 +231,70 @@ int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint6
             }
         }
         T.extra_begin[n_csq] = uint32_t(T.extra.size());
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2p_csq_tables_build(const v2p_vcf_index* x, const uint8_t* text, uint32_t n_threads, v2p_csq_tables** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!x || !text) return -1;
+    v2p_csq_tables* t = new (std::nothrow) v2p_csq_tables();
+    if (!t) return -1;
+    build_tables(t->T, x, text, n_threads);
+    *out = t;
+    return 0;
+}
+
+void v2p_csq_tables_destroy(v2p_csq_tables* t) { delete t; }
+uint64_t v2p_csq_tables_n_consequences(const v2p_csq_tables* t) { return t ? t->T.rank.size() : 0; }
+uint64_t v2p_csq_tables_n_transcripts(const v2p_csq_tables* t) { return t ? t->T.tx_begin.size() : 0; }
+int v2p_csq_tables_transcript(const v2p_csq_tables* t, uint64_t rank, uint64_t* begin, uint64_t* len)
+{
+    if (!t || rank >= t->T.tx_begin.size() || !begin || !len) return -1;
+    *begin = t->T.tx_begin[rank];
+    *len = t->T.tx_len[rank];
+    return 0;
+}
+const uint64_t* v2p_csq_tables_transcript_begin(const v2p_csq_tables* t) { return t ? t->T.tx_begin.data() : nullptr; }
+const uint32_t* v2p_csq_tables_transcript_len(const v2p_csq_tables* t) { return t ? t->T.tx_len.data() : nullptr; }
+const uint32_t* v2p_csq_tables_rank(const v2p_csq_tables* t) { return t ? t->T.rank.data() : nullptr; }
+const uint32_t* v2p_csq_tables_flags(const v2p_csq_tables* t) { return t ? t->T.flags.data() : nullptr; }
+const uint16_t* v2p_csq_tables_mut_pos(const v2p_csq_tables* t) { return t ? t->T.mut_pos.data() : nullptr; }
+const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t) { return t ? t->T.ref_pos.data() : nullptr; }
+const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t) { return t ? t->T.ident.data() : nullptr; }
+const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t) { return t ? t->T.extra_begin.data() : nullptr; }
+const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t) { return t ? t->T.extra.data() : nullptr; }
+
+int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint64_t* hap_begin, const uint32_t* ids,
+                     uint64_t n_haps, uint32_t n_threads, v2p_groups** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!x || !text_u8 || !hap_begin || (!ids && hap_begin[n_haps])) return -1;
+    v2p_groups* g = new (std::nothrow) v2p_groups();
+    if (!g) return -1;
+    *out = g;
+    const uint64_t n_csq = v2p_vcf_index_n_consequences(x);
+    Table T;
+    build_tables(T, x, text_u8, n_threads);
+    g->tx_begin = T.tx_begin;
+    g->tx_len = T.tx_len;
+    g->muts.resize(n_csq);
+    g->aa.resize(n_csq);
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        Parsed& p = T.parsed[i];
+        v2p_mutation m{};
+        m.transcript = T.rank[i];
+        if (p.mut_ok) {
+            m.valid = 1; m.type = uint8_t(p.type); m.ref_aa_position = p.ref_pos; m.mut_aa_position = p.mut_pos;
+            g->aa[i].ref_aa = std::move(p.ref_aa); g->aa[i].mut_aa = std::move(p.mut_aa);
+        }
+        g->muts[i] = m;
     }
 
     // ---- per haplotype ----
@@ -365,5 +425,24 @@ const uint64_t* v2p_groups_hap_group_begin(const v2p_groups* g) { return g ? g->
 const uint32_t* v2p_groups_group_transcript(const v2p_groups* g) { return g ? g->group_transcript.data() : nullptr; }
 const uint64_t* v2p_groups_group_member_begin(const v2p_groups* g) { return g ? g->group_member_begin.data() : nullptr; }
 const uint32_t* v2p_groups_member_ids(const v2p_groups* g) { return g ? g->member_ids.data() : nullptr; }
+
+// summary.rs:10-32 read off the CSR: groups per proband, members of each type per proband, haplotypes per transcript
+int v2p_groups_stats(const v2p_groups* g, uint64_t n_samples, uint64_t* per_proband, uint64_t* per_type, uint64_t* per_transcript)
+{
+    if (!g || !per_proband || !per_type || (!per_transcript && !g->tx_begin.empty()) || g->error_hap >= 0 ||
+        g->hap_group_begin.size() != 2 * n_samples + 1) return -1;
+    std::fill(per_proband, per_proband + n_samples, 0);
+    std::fill(per_type, per_type + 22 * n_samples, 0);
+    std::fill(per_transcript, per_transcript + g->tx_begin.size(), 0);
+    for (uint64_t h = 0; h < 2 * n_samples; ++h) {
+        per_proband[h / 2] += g->hap_group_begin[h + 1] - g->hap_group_begin[h];
+        for (uint64_t k = g->hap_group_begin[h]; k < g->hap_group_begin[h + 1]; ++k) {
+            ++per_transcript[g->group_transcript[k]];
+            for (uint64_t m = g->group_member_begin[k]; m < g->group_member_begin[k + 1]; ++m)
+                ++per_type[22 * (h / 2) + g->muts[g->member_ids[m]].type];
+        }
+    }
+    return 0;
+}
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
 //                                            steps 4-5 produce slices of probands that stream through v2p_pipeline_submit_stream while the next are made
 //   v2p_harness sharded <preset> <samples> --devices N [--oversubscribe] [--threads T] [--streamed [--slice-mb M]]
@@ -326,8 +326,41 @@ static bool gunzip(const std::string& gz, std::string& out, std::string& err)
     return true;
 }
 
+// writers.rs:70-150: the three files of -s / --stats, each row as the reference formats it; rows in VCF sample order and in sorted
+// transcript order (the reference iterates a HashMap).  The second file has no line feeds: header and rows are tab-terminated tokens.
+static bool write_stats_files(const std::string& outdir, const std::vector<std::string>& samples, const std::vector<std::string>& transcripts,
+                              const std::vector<uint64_t>& per_proband, const std::vector<uint64_t>& per_type, const std::vector<uint64_t>& per_transcript)
+{
+    static const char* const SUP_TYPE[22] = {
+        "missense", "*missense", "frameshift", "*frameshift", "inframe_insertion", "*inframe_insertion", "inframe_deletion",
+        "*inframe_deletion", "stop_gained", "stop_lost", "*missense&inframe_altering", "*frameshift&stop_retained",
+        "*stop_gained&inframe_altering", "frameshift&stop_retained", "inframe_deletion&stop_retained",
+        "inframe_insertion&stop_retained", "stop_gained&inframe_altering", "start_lost", "*stop_gained", "stop_lost&frameshift",
+        "missense&inframe_altering", "start_lost&splice_region"};
+    std::string a = "Proband Name \t Number of mutations\n", b = "Proband Name\t", c = "Transcript Name \t Number of mutations\n";
+    for (const char* t : SUP_TYPE) { b += t; b += '\t'; }
+    for (size_t s = 0; s < samples.size(); ++s) {
+        a += samples[s] + ",\t" + std::to_string(per_proband[s]) + "\n";
+        b += samples[s] + "\t";
+        for (int t = 0; t < 22; ++t) b += std::to_string(per_type[22 * s + t]) + "\t";
+    }
+    for (size_t r = 0; r < transcripts.size(); ++r)
+        if (per_transcript[r]) c += transcripts[r] + ",\t" + std::to_string(per_transcript[r]) + "\n";
+    const std::pair<const char*, const std::string*> files[3] = {{"number_of_mutations_per_proband.tsv", &a}, {"type_of_mutations_per_patient.tsv", &b},
+                                                                 {"number_of_mutations_per_transcript.tsv", &c}};
+    for (const auto& f : files) {
+        const std::string path = outdir + "/" + f.first;
+        FILE* fp = std::fopen(path.c_str(), "wb");
+        if (!fp || std::fwrite(f.second->data(), 1, f.second->size(), fp) != f.second->size() || std::fclose(fp) != 0) {
+            std::fprintf(stderr, "Creating the file: %s failed\n", path.c_str());
+            return false;
+        }
+    }
+    return true;
+}
+
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf)
+                    bool bgzf, bool stats)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -393,6 +426,38 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     }
     std::vector<uint64_t> hap_begin(2 * S + 1);
     if (v2p_decode_counts(dec, hap_begin.data()) != V2P_OK) { std::fprintf(stderr, "panicked: decode counts unavailable\n"); return 101; }
+    // -s / --stats (main.rs:39-45): the three tables counted on the device from the lists the decode left there
+    double t_stats = 0;
+    float sms[2] = {0, 0};
+    v2p_stats_info sinfo{};
+    std::vector<uint64_t> st_proband, st_type, st_tx;
+    std::vector<std::string> st_names;
+    if (stats) {
+        const auto ts = clk::now();
+        v2p_csq_tables* tb = nullptr;
+        if (v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
+        const uint64_t T = v2p_csq_tables_n_transcripts(tb);
+        st_proband.assign(S, 0); st_type.assign(22 * S, 0); st_tx.assign(T + 1, 0);
+        const int rc = v2p_decode_stats(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
+                                        v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
+                                        text, v2p_csq_tables_transcript_begin(tb), v2p_csq_tables_transcript_len(tb),
+                                        st_proband.data(), st_type.data(), st_tx.data(), nullptr, &sinfo);
+        // (a refused list is completed from the grouping below, which reports its abort if it has one)
+        if (rc != V2P_OK && !(rc == V2P_ERR_DUPLICATE_POS && sinfo.n_refused)) {
+            std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw()));
+            v2p_csq_tables_destroy(tb);
+            v2p_decode_destroy(dec);
+            return 101;
+        }
+        v2p_decode_stats_timing(dec, &sms[0], &sms[1]);
+        for (uint64_t r = 0; r < T; ++r) {
+            uint64_t b = 0, n = 0;
+            v2p_csq_tables_transcript(tb, r, &b, &n);
+            st_names.push_back(vcf.substr(b, n));
+        }
+        v2p_csq_tables_destroy(tb);
+        t_stats = since(ts);
+    }
     std::vector<uint32_t> ids(hap_begin.back() + 1);
     if (v2p_decode_download(dec, ids.data()) != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
     float kms[4] = {0, 0, 0, 0};
@@ -405,6 +470,20 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         return 101;
     }
     t_group = since(t0); t0 = clk::now();
+    if (stats) {
+        const auto ts = clk::now();
+        // lists the kernel refused: the grouping above holds every list, so the tables are read off it
+        if (sinfo.n_refused && v2p_groups_stats(g, S, st_proband.data(), st_type.data(), st_tx.data()) != 0) { std::fprintf(stderr, "panicked: statistics of the grouping failed\n"); return 101; }
+        std::vector<std::string> samples(S);
+        for (uint64_t s = 0; s < S; ++s) {
+            uint64_t b = 0, n = 0;
+            v2p_vcf_index_sample(idx, s, &b, &n);
+            samples[s] = vcf.substr(b, n);
+        }
+        if (!write_stats_files(outdir, samples, st_names, st_proband, st_type, st_tx)) return 101;
+        t_stats += since(ts);
+        t0 = clk::now();
+    }
     // resident reference: the transcripts the file touches + their two record headers
     const uint64_t n_tx = v2p_groups_n_transcripts(g);
     std::vector<std::string> names(n_tx);
@@ -671,15 +750,21 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         t_exec = since(t0) - (t_write_acc - w0); t0 = clk::now();
     }
     t_write = host_build ? since(t0) : t_write_acc;
+    char stats_seconds[48] = "";
+    if (stats) std::snprintf(stats_seconds, sizeof(stats_seconds), ", \"stats\": %.4f", t_stats);
     std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
                 (unsigned long long)written, outdir);
     std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
-                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f}, "
+                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f%s}, "
                 "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}, \"input_format\": \"%s\", "
-                "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}}\n",
+                "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}",
                 (unsigned long long)R, (unsigned long long)S, (unsigned long long)written, (unsigned long long)n_slices, (unsigned long long)n_fallback,
                 t_read, t_index, t_decode, t_group, t_build, t_exec, t_write,
-                since(t_start), t_inflate, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
+                since(t_start), t_inflate, stats_seconds, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
+    if (stats)
+        std::printf(", \"stats_ms\": {\"upload\": %.3f, \"kernel\": %.3f, \"refused_lists\": %llu, \"sorted_members\": %llu, \"lds_bytes\": %u}",
+                    sms[0], sms[1], (unsigned long long)sinfo.n_refused, (unsigned long long)sinfo.n_sorted_members, sinfo.lds_bytes);
+    std::printf("}\n");
     v2p_batch_destroy(b);
     v2p_groups_destroy(g);
     v2p_vcf_index_destroy(idx);
@@ -782,7 +867,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -791,9 +876,10 @@ int main(int argc, char** argv)
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
+            stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

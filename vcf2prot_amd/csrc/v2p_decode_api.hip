@@ -1,6 +1,7 @@
 // v2p_decode_api.hip -- C ABI of the BCSQ bitmask decode (include/v2p_frontend.h, part 2) on the gfx950 kernels of
 // decode_kernels.hip.  Replaces the Engine::GPU arm of VCFRecords::get_csq_per_patient (vcf_ds.rs:192-211).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "../../include/v2p_frontend.h"
 #include "decode_kernels.h"
+#include "group_stats.h"
 #include "inflate_format.hpp"
 #include "v2p_ctx_internal.h"
 
@@ -30,6 +32,8 @@ struct v2p_decode {
     std::vector<uint64_t> hap_begin;
     float ms[4] = {0, 0, 0, 0};
     float ms_inflate[3] = {0, 0, 0};  // upload of the members, inflate kernel, text to the host
+    float ms_stats[2] = {0, 0};       // v2p_decode_stats: upload of the tables, kernel
+    std::vector<uint64_t> refused;    // lists the last v2p_decode_stats refused
     void release_lists() {
         for (void* p : {(void*)d_rows, (void*)d_csq, (void*)d_work, (void*)d_hap_begin, (void*)d_ids, (void*)d_status})
             if (p) (void)hipFree(p);
@@ -394,6 +398,140 @@ int v2p_decode_inflate_timing(const v2p_decode* d, float* ms_h2d, float* ms_infl
     if (ms_h2d) *ms_h2d = d->ms_inflate[0];
     if (ms_inflate) *ms_inflate = d->ms_inflate[1];
     if (ms_d2h) *ms_d2h = d->ms_inflate[2];
+    return V2P_OK;
+}
+
+int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos,
+                     const uint32_t* ident, const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_csq, uint64_t n_tx,
+                     const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len,
+                     uint64_t* per_proband, uint64_t* per_type, uint64_t* per_transcript, const v2p_stats_caps* caps, v2p_stats_info* info)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    if (!d || d->ctx != ctx || !d->d_hap_begin || d->hap_begin.empty())
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: needs a decode that holds lists (v2p_decode_run / v2p_decode_run_inflated)", -1);
+    if (!per_proband || !per_type || (n_tx && !per_transcript) || !info ||
+        (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !extra_begin)) || (n_csq && extra_begin[n_csq] && !extra))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: null argument", -1);
+    if (n_csq >= 0xffffffffull || n_tx > STATS_MAX_RANKS)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: more than 2^24 transcripts or 2^32 consequences", -1);
+    const uint64_t S = d->n_samples, n_haps = 2 * S;
+    // one 16-byte row per consequence id
+    std::vector<StatsRec> rec(n_csq + 1);
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        if (extra_begin[i + 1] < extra_begin[i] || extra_begin[i + 1] - extra_begin[i] > 0xffffu)
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: extra_begin must ascend by at most 65535 per consequence", int64_t(i));
+        if ((flags[i] & 1u) && ((flags[i] >> 8 & 0xffu) >= STATS_TYPES || rank[i] == ~0u))
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: a mut_ok consequence needs a type below 22 and a transcript", int64_t(i));
+        if (rank[i] != ~0u && rank[i] >= n_tx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: rank outside the transcripts", int64_t(i));
+        rec[i] = StatsRec{rank[i], (flags[i] & 0xffffu) | (extra_begin[i + 1] - extra_begin[i]) << 16, uint32_t(mut_pos[i]) | uint32_t(ref_pos[i]) << 16, ident[i]};
+    }
+    const uint64_t n_extra = n_csq ? extra_begin[n_csq] : 0;
+    uint64_t max_len = 0;
+    for (uint64_t h = 0; h < n_haps; ++h) max_len = std::max(max_len, d->hap_begin[h + 1] - d->hap_begin[h]);
+    // sizes: the bitmap covers every transcript; the filter gets about 32 bits per id of the longest list inside 64 KiB of LDS, and
+    // more LDS (fewer workgroups per CU) only when that leaves fewer than 8 bits per id
+    auto pow2_floor = [](uint64_t v) { uint64_t p = 1; while (p * 2 <= v) p *= 2; return p; };
+    auto pow2_ceil = [](uint64_t v) { uint64_t p = 1; while (p < v) p *= 2; return p; };
+    uint32_t W = caps && caps->bitmap_words ? caps->bitmap_words : uint32_t(std::max<uint64_t>(1, (n_tx + 31) / 32));
+    uint32_t C = caps && caps->sort_capacity ? caps->sort_capacity : 2048u;
+    uint32_t F = caps ? caps->filter_words : 0u;
+    const uint64_t lds_max = 160u * 1024u;
+    if (!(caps && caps->bitmap_words) && stats_lds_bytes(W, 32, C) > lds_max) W = uint32_t((lds_max - 8ull * C - 4ull * (32 + STATS_MISC_WORDS)) / 8);
+    if (!F) {
+        const uint64_t want = pow2_ceil(std::max<uint64_t>(32, max_len));                        // words: 32 bits per id
+        const uint64_t fixed = stats_lds_bytes(W, 0, C);
+        auto fit = [&](uint64_t budget) { return fixed + 4 * 32 <= budget ? pow2_floor((budget - fixed) / 4) : 0; };
+        uint64_t f = std::min(want, fit(64u * 1024u));
+        if (f * 4 < max_len) f = std::min(want, fit(lds_max));
+        F = uint32_t(std::max<uint64_t>(f, 32));
+    }
+    if ((F & (F - 1)) || (C & (C - 1)) || uint64_t(W) * 32 > STATS_MAX_RANKS || stats_lds_bytes(W, F, C) > lds_max)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: filter_words and sort_capacity must be powers of two and all of it fit 160 KiB of LDS", -1);
+    info->n_refused = 0; info->n_sorted_members = 0;
+    info->bitmap_words = W; info->filter_words = F; info->sort_capacity = C; info->lds_bytes = uint32_t(stats_lds_bytes(W, F, C));
+    d->refused.clear();
+    d->ms_stats[0] = d->ms_stats[1] = 0;
+
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    struct Temp {                                       // freed on every exit path
+        void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
+    } tmp;
+    const uint64_t n_out = 23 * S + n_tx + 3;           // per_proband | per_type | per_transcript | status
+    RTRY(dmalloc(&tmp.p[0], rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
+    RTRY(dmalloc(&tmp.p[1], (n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
+    RTRY(dmalloc(&tmp.p[2], (n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
+    RTRY(dmalloc(&tmp.p[3], n_out * sizeof(uint64_t)), "hipMalloc(stats tables)");
+    RTRY(dmalloc(&tmp.p[4], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
+    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
+    const uint32_t zero = 0;
+    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
+    RTRY(hipMemcpyAsync(tmp.p[0], rec.data(), rec.size() * sizeof(StatsRec), hipMemcpyHostToDevice, st), "H2D(stats rows)");
+    RTRY(hipMemcpyAsync(tmp.p[1], n_csq ? extra_begin : &zero, (n_csq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra_begin)");
+    if (n_extra) RTRY(hipMemcpyAsync(tmp.p[2], extra, n_extra * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra)");
+    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
+    uint64_t* d_out = static_cast<uint64_t*>(tmp.p[3]);
+    RTRY(hipMemsetAsync(d_out, 0, n_out * sizeof(uint64_t), st), "hipMemset(stats tables)");
+    RTRY(hipMemsetAsync(d_out + 23 * S + n_tx, 0xFF, sizeof(uint64_t), st), "hipMemset(stats status)");
+    RTRY(hipMemsetAsync(tmp.p[4], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
+    StatsArgs a{};
+    a.hap_begin = d->d_hap_begin; a.ids = d->d_ids; a.n_haps = uint32_t(n_haps);
+    a.rec = static_cast<const StatsRec*>(tmp.p[0]); a.extra_begin = static_cast<const uint32_t*>(tmp.p[1]);
+    a.extra = static_cast<const uint32_t*>(tmp.p[2]); a.n_csq = uint32_t(n_csq);
+    a.per_proband = reinterpret_cast<unsigned long long*>(d_out);
+    a.per_type = reinterpret_cast<unsigned long long*>(d_out + S);
+    a.per_transcript = reinterpret_cast<unsigned long long*>(d_out + 23 * S);
+    a.status = reinterpret_cast<unsigned long long*>(d_out + 23 * S + n_tx);
+    a.refused = static_cast<uint32_t*>(tmp.p[4]);
+    a.bitmap_words = W; a.filter_words = F; a.sort_capacity = C;
+    RTRY(launch_group_stats(a, st), "group_stats_kernel");
+    RTRY(hipEventRecord(tmp.e[2], st), "hipEventRecord");
+    std::vector<uint64_t> out(n_out);
+    RTRY(hipMemcpyAsync(out.data(), d_out, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(stats tables)");
+    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&d->ms_stats[0], tmp.e[0], tmp.e[1]);
+    (void)hipEventElapsedTime(&d->ms_stats[1], tmp.e[1], tmp.e[2]);
+    const uint64_t* status = out.data() + 23 * S + n_tx;
+    info->n_refused = status[1]; info->n_sorted_members = status[2];
+    if (status[1]) {
+        std::vector<uint32_t> fl(n_haps);
+        RTRY(hipMemcpy(fl.data(), tmp.p[4], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
+        for (uint64_t h = 0; h < n_haps; ++h) if (fl[h]) d->refused.push_back(h);
+    }
+    if (status[0] != ~0ull) {
+        const uint64_t hap = status[0] >> 32;
+        const uint32_t why = uint32_t(status[0]);
+        std::string msg;
+        if (why == STATS_ERR_POISON) msg = "start_lost consequence with fewer than three fields (text_parser.rs:52 would abort)";
+        else if (why == STATS_ERR_RANGE) msg = "consequence id out of range";
+        else {
+            const uint32_t r = why - 1;
+            msg = "Encountered a logical error with analyzing mutations in transcript: " +
+                  (tx_text && tx_begin && tx_len && r < n_tx ? std::string(reinterpret_cast<const char*>(tx_text) + tx_begin[r], tx_len[r]) : "rank " + std::to_string(r));
+        }
+        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, msg, int64_t(hap));
+    }
+    memcpy(per_proband, out.data(), S * sizeof(uint64_t));
+    memcpy(per_type, out.data() + S, 22 * S * sizeof(uint64_t));
+    if (n_tx) memcpy(per_transcript, out.data() + 23 * S, n_tx * sizeof(uint64_t));
+    return V2P_OK;
+}
+
+int v2p_decode_stats_refused(const v2p_decode* d, uint64_t* lists)
+{
+    if (!d || (!lists && !d->refused.empty())) return V2P_ERR_INVALID_ARG;
+    if (!d->refused.empty()) memcpy(lists, d->refused.data(), d->refused.size() * sizeof(uint64_t));
+    return V2P_OK;
+}
+
+int v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_kernel)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    if (ms_upload) *ms_upload = d->ms_stats[0];
+    if (ms_kernel) *ms_kernel = d->ms_stats[1];
     return V2P_OK;
 }
 

@@ -48,6 +48,10 @@ DECODE_API = {
     "v2p_decode_inflate": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
     "v2p_decode_run_inflated": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
     "v2p_decode_inflate_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "v2p_decode_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_decode_stats_refused": (c_int, [c_void_p, c_void_p]),
+    "v2p_decode_stats_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float)]),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -75,7 +79,31 @@ HOST_API = {
     "v2p_groups_group_transcript": (POINTER(c_uint32), [c_void_p]),
     "v2p_groups_group_member_begin": (POINTER(c_uint64), [c_void_p]),
     "v2p_groups_member_ids": (POINTER(c_uint32), [c_void_p]),
+    "v2p_groups_stats": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "v2p_csq_tables_build": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "v2p_csq_tables_destroy": (None, [c_void_p]),
+    "v2p_csq_tables_n_consequences": (c_uint64, [c_void_p]),
+    "v2p_csq_tables_n_transcripts": (c_uint64, [c_void_p]),
+    "v2p_csq_tables_transcript": (c_int, [c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_csq_tables_transcript_begin": (POINTER(c_uint64), [c_void_p]),
+    "v2p_csq_tables_transcript_len": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_rank": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_flags": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_mut_pos": (POINTER(c_uint16), [c_void_p]),
+    "v2p_csq_tables_ref_pos": (POINTER(c_uint16), [c_void_p]),
+    "v2p_csq_tables_ident": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_extra_begin": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_extra": (POINTER(c_uint32), [c_void_p]),
 }
+
+
+class v2p_stats_caps(ctypes.Structure):
+    _fields_ = [("bitmap_words", c_uint32), ("filter_words", c_uint32), ("sort_capacity", c_uint32)]
+
+
+class v2p_stats_info(ctypes.Structure):
+    _fields_ = [("n_refused", c_uint64), ("n_sorted_members", c_uint64), ("bitmap_words", c_uint32), ("filter_words", c_uint32),
+                ("sort_capacity", c_uint32), ("lds_bytes", c_uint32)]
 
 _bound = {}
 
@@ -209,9 +237,57 @@ def inflate_bgzf(ctx, gz):
     return text[:int(ob[-1] - ob[0])].tobytes(), InflatedText(ctx, h, int(ob[-1] - ob[0]))
 
 
+class ResidentLists:
+    """The decode's lists left on the device (decode_resident): what cohort_stats counts without the ids crossing the link.  download()
+    gives the HaplotypeLists; close() frees the device memory."""
+
+    def __init__(self, ctx, h, n_samples: int):
+        self.ctx, self._h, self.n_samples = ctx, h, n_samples
+        self.hap_begin = np.zeros(2 * n_samples + 1, dtype=np.uint64)
+        _hip().v2p_decode_counts(h, self.hap_begin.ctypes.data)
+
+    @property
+    def n_haplotypes(self):
+        return self.hap_begin.size - 1
+
+    def timing_ms(self) -> dict:
+        t = [c_float() for _ in range(4)]
+        _hip().v2p_decode_timing(self._h, *[ctypes.byref(x) for x in t])
+        return dict(zip(("parse", "count", "scan", "emit"), (x.value for x in t)))
+
+    def download(self) -> HaplotypeLists:
+        lib = _hip()
+        ids = np.zeros(int(self.hap_begin[-1]), dtype=np.uint32)
+        rc = lib.v2p_decode_download(self._h, ids.ctypes.data if ids.size else None)
+        if rc != 0:
+            raise N.V2PError(rc, lib.v2p_last_error(self.ctx._h).decode())
+        return HaplotypeLists(self.hap_begin.copy(), ids, self.timing_ms())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _hip().v2p_decode_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def decode_resident(ctx, idx: VcfIndex, inflated: "InflatedText" = None) -> ResidentLists:
+    """decode_bitmasks that leaves the lists on the device and downloads only their lengths."""
+    return ResidentLists(ctx, _decode_run(ctx, idx, inflated), idx.n_samples)
+
+
 def decode_bitmasks(ctx, idx: VcfIndex, inflated: "InflatedText" = None) -> HaplotypeLists:
     """VCFRecords::get_csq_per_patient (vcf_ds.rs:192-211) for every proband, on the GPU of `ctx` (engine.Context).  inflated: the text
     of idx is already on the device (inflate_bgzf); the decode runs on it and `inflated` is used up."""
+    res = decode_resident(ctx, idx, inflated)
+    try:
+        return res.download()
+    finally:
+        res.close()
+
+
+def _decode_run(ctx, idx: VcfIndex, inflated: "InflatedText" = None):
     lib = _hip()
     if inflated is not None:
         h = inflated._h
@@ -226,18 +302,7 @@ def decode_bitmasks(ctx, idx: VcfIndex, inflated: "InflatedText" = None) -> Hapl
                                 idx.n_records, idx.n_samples, idx.csq_begin.ctypes.data, idx.csq_supported.ctypes.data, ctypes.byref(h))
     if rc != 0:
         raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
-    try:
-        hap_begin = np.zeros(2 * idx.n_samples + 1, dtype=np.uint64)
-        lib.v2p_decode_counts(h, hap_begin.ctypes.data)
-        ids = np.zeros(int(hap_begin[-1]), dtype=np.uint32)
-        rc = lib.v2p_decode_download(h, ids.ctypes.data if ids.size else None)
-        if rc != 0:
-            raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode())
-        t = [c_float() for _ in range(4)]
-        lib.v2p_decode_timing(h, *[ctypes.byref(x) for x in t])
-        return HaplotypeLists(hap_begin, ids, dict(zip(("parse", "count", "scan", "emit"), (x.value for x in t))))
-    finally:
-        lib.v2p_decode_destroy(h)
+    return h
 
 
 class Groups:
@@ -263,6 +328,7 @@ class Groups:
         self.group_member_begin = _arr(L.v2p_groups_group_member_begin(h), n_groups + 1, np.uint64)
         self.member_ids = _arr(L.v2p_groups_member_ids(h), int(self.group_member_begin[-1]), np.uint32)
         m = L.v2p_groups_mutations(h)
+        self._n_samples = lists.n_haplotypes // 2
         self.mutations = np.ctypeslib.as_array(ctypes.cast(m, POINTER(c_uint8)), shape=(idx.n_consequences * ctypes.sizeof(v2p_mutation),)).view(
             np.dtype([("transcript", "<u4"), ("ref_aa_position", "<u2"), ("mut_aa_position", "<u2"), ("type", "u1"), ("valid", "u1"), ("pad", "u1", 2)])).copy() \
             if idx.n_consequences else None
@@ -271,6 +337,17 @@ class Groups:
         b, n = c_uint64(), c_uint64()
         self._lib.v2p_groups_transcript(self._h, rank, ctypes.byref(b), ctypes.byref(n))
         return self._idx._bytes[b.value:b.value + n.value].decode()
+
+    def stats(self):
+        """(per_proband[n_samples], per_type[n_samples, 22], per_transcript[n_transcripts]) of summary.rs:10-32, off the CSR
+        (v2p_groups_stats)."""
+        pp = np.zeros(self._n_samples, np.uint64)
+        pt = np.zeros((self._n_samples, 22), np.uint64)
+        px = np.zeros(max(self.n_transcripts, 1), np.uint64)
+        rc = self._lib.v2p_groups_stats(self._h, self._n_samples, pp.ctypes.data, pt.ctypes.data, px.ctypes.data)
+        if rc != 0:
+            raise N.V2PError(rc, "v2p_groups_stats failed")
+        return pp, pt, px[:self.n_transcripts]
 
     def of(self, hap: int):
         """[(transcript name, [consequence ids])] of one haplotype, in the reference's order."""
@@ -291,3 +368,127 @@ class Groups:
 
 def group_per_transcript(idx: VcfIndex, lists: HaplotypeLists, n_threads: int = 0) -> Groups:
     return Groups(idx, lists, n_threads)
+
+
+SUP_TYPE = ("missense", "*missense", "frameshift", "*frameshift", "inframe_insertion", "*inframe_insertion", "inframe_deletion",
+            "*inframe_deletion", "stop_gained", "stop_lost", "*missense&inframe_altering", "*frameshift&stop_retained",
+            "*stop_gained&inframe_altering", "frameshift&stop_retained", "inframe_deletion&stop_retained",
+            "inframe_insertion&stop_retained", "stop_gained&inframe_altering", "start_lost", "*stop_gained", "stop_lost&frameshift",
+            "missense&inframe_altering", "start_lost&splice_region")          # Constants.rs:3-8, the columns of per_type
+
+
+class CsqTables:
+    """The file-wide per-consequence tables of the grouping rule (v2p_csq_tables_build): rank, flags (bit 0 mut_ok, bit 1 poison,
+    bits 8-15 type), mut_pos, ref_pos, ident, the CSR extra_begin / extra, and the sorted transcript names."""
+
+    def __init__(self, idx: VcfIndex, n_threads: int = 0):
+        L = self._lib = _host()
+        self._idx = idx
+        h = c_void_p()
+        rc = L.v2p_csq_tables_build(idx._h, idx.text.ctypes.data, n_threads, ctypes.byref(h))
+        self._h = h
+        if rc != 0:
+            raise N.V2PError(rc, "v2p_csq_tables_build failed")
+        n = self.n_consequences = int(L.v2p_csq_tables_n_consequences(h))
+        t = self.n_transcripts = int(L.v2p_csq_tables_n_transcripts(h))
+        self.rank = _arr(L.v2p_csq_tables_rank(h), n, np.uint32)
+        self.flags = _arr(L.v2p_csq_tables_flags(h), n, np.uint32)
+        self.mut_pos = _arr(L.v2p_csq_tables_mut_pos(h), n, np.uint16)
+        self.ref_pos = _arr(L.v2p_csq_tables_ref_pos(h), n, np.uint16)
+        self.ident = _arr(L.v2p_csq_tables_ident(h), n, np.uint32)
+        self.extra_begin = _arr(L.v2p_csq_tables_extra_begin(h), n + 1, np.uint32)
+        self.extra = _arr(L.v2p_csq_tables_extra(h), int(self.extra_begin[-1]), np.uint32)
+        self.transcript_begin = _arr(L.v2p_csq_tables_transcript_begin(h), t, np.uint64)
+        self.transcript_len = _arr(L.v2p_csq_tables_transcript_len(h), t, np.uint32)
+
+    def transcript_names(self):
+        return [self._idx._bytes[int(b):int(b) + int(n)].decode() for b, n in zip(self.transcript_begin, self.transcript_len)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.v2p_csq_tables_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class CohortStats:
+    """The three tables of -s / --stats: per_proband[n_samples], per_type[n_samples, 22] (columns SUP_TYPE), per_transcript
+    [n_transcripts], with the sample names (VCF order) and the transcript names (sorted).  refused: the haplotype lists the kernel
+    refused and the host completed; timing_ms: upload of the tables and the kernel; info: the launched sizes."""
+
+    def __init__(self, per_proband, per_type, per_transcript, sample_names, transcript_names, refused=(), timing_ms=None, info=None):
+        self.per_proband, self.per_type, self.per_transcript = per_proband, per_type, per_transcript
+        self.sample_names, self.transcript_names = sample_names, transcript_names
+        self.refused, self.timing_ms, self.info = list(refused), timing_ms, info
+
+
+def device_stats(ctx, resident: ResidentLists, tables: CsqTables, caps=None):
+    """v2p_decode_stats alone: (per_proband, per_type, per_transcript, refused lists, info dict, error or None).  Nothing is completed on
+    the host; refused lists count nothing."""
+    lib = _hip()
+    S, T = resident.n_samples, tables.n_transcripts
+    pp, pt, px = np.zeros(S, np.uint64), np.zeros((S, 22), np.uint64), np.zeros(max(T, 1), np.uint64)
+    info = v2p_stats_info()
+    c = v2p_stats_caps(*caps) if caps is not None else None
+    idx = tables._idx
+    ptr = lambda a: a.ctypes.data if a.size else None
+    rc = lib.v2p_decode_stats(ctx._h, resident._h, ptr(tables.rank), ptr(tables.flags), ptr(tables.mut_pos), ptr(tables.ref_pos),
+                              ptr(tables.ident), tables.extra_begin.ctypes.data, ptr(tables.extra), tables.n_consequences, T,
+                              idx.text.ctypes.data, ptr(tables.transcript_begin), ptr(tables.transcript_len),
+                              pp.ctypes.data, pt.ctypes.data, px.ctypes.data, ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    err = None
+    if rc == V2P_ERR_DUPLICATE_POS:
+        err = N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    elif rc != 0:
+        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    refused = np.zeros(int(info.n_refused), np.uint64)
+    lib.v2p_decode_stats_refused(resident._h, ptr(refused))
+    t = [c_float(), c_float()]
+    lib.v2p_decode_stats_timing(resident._h, ctypes.byref(t[0]), ctypes.byref(t[1]))
+    inf = {k: int(getattr(info, k)) for k, _ in v2p_stats_info._fields_}
+    inf["timing_ms"] = {"upload": t[0].value, "kernel": t[1].value}
+    return pp, pt, px[:T], refused.astype(np.int64).tolist(), inf, err
+
+
+def cohort_stats(ctx, idx: VcfIndex, lists, tables: CsqTables = None, caps=None, n_threads: int = 0) -> CohortStats:
+    """compute_states (exec.rs:45-64).  lists = ResidentLists (decode_resident): counted on the GPU, the ids stay there; lists the kernel
+    refuses are downloaded and completed through Groups + v2p_groups_stats, those haplotypes only.  lists = HaplotypeLists: the host path
+    for all of them.  Raises V2PError(V2P_ERR_DUPLICATE_POS) with the smallest aborting haplotype list where the reference panics."""
+    if isinstance(lists, HaplotypeLists):
+        g = Groups(idx, lists, n_threads)
+        try:
+            pp, pt, px = g.stats()
+            return CohortStats(pp, pt, px, idx.sample_names(), [g.transcript_name(r) for r in range(g.n_transcripts)])
+        finally:
+            g.close()
+    own = tables is None
+    if own:
+        tables = CsqTables(idx, n_threads)
+    try:
+        pp, pt, px, refused, info, err = device_stats(ctx, lists, tables, caps)
+        if refused:
+            full = lists.download()
+            keep = np.zeros(full.n_haplotypes, bool)
+            keep[refused] = True
+            lens = np.where(keep, np.diff(full.hap_begin.astype(np.int64)), 0)
+            hb = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+            ids = np.concatenate([full.of(h) for h in refused]) if refused else np.zeros(0, np.uint32)
+            try:
+                g = Groups(idx, HaplotypeLists(hb, np.ascontiguousarray(ids, dtype=np.uint32)), n_threads)
+            except N.V2PError as e:
+                if err is None or e.index < err.index:
+                    err = e
+            else:
+                try:
+                    hp, ht, hx = g.stats()
+                    pp, pt, px = pp + hp, pt + ht, px + hx
+                finally:
+                    g.close()
+        if err is not None:
+            raise err
+        return CohortStats(pp, pt, px, idx.sample_names(), tables.transcript_names(), refused, info["timing_ms"], info)
+    finally:
+        if own:
+            tables.close()

@@ -39,6 +39,35 @@ def read_fasta(text: str) -> Dict[str, str]:
     return records
 
 
+STATS_FILES = ("number_of_mutations_per_proband.tsv", "type_of_mutations_per_patient.tsv", "number_of_mutations_per_transcript.tsv")
+
+
+def stats_file_texts(stats) -> Dict[str, str]:
+    """{file name: text} of the reference's three -s files (writers.rs:70-150), each row formatted as the reference formats it: `name,\\tcount\\n`
+    in the first and third file; in the second the header and every row are tab-terminated tokens and NO line feed separates rows.  The
+    reference iterates a HashMap, so its row order is arbitrary; here rows go in VCF sample order and in sorted transcript order.  Only
+    transcripts altered in at least one haplotype are rows of the third file (summary.rs:26-32)."""
+    from .frontend import SUP_TYPE
+    a = ["Proband Name \t Number of mutations\n"]
+    b = ["Proband Name\t"] + [t + "\t" for t in SUP_TYPE]
+    c = ["Transcript Name \t Number of mutations\n"]
+    for s, name in enumerate(stats.sample_names):
+        a.append(f"{name},\t{int(stats.per_proband[s])}\n")
+        b.append(name + "\t" + "".join(f"{int(v)}\t" for v in stats.per_type[s]))
+    for r, name in enumerate(stats.transcript_names):
+        if int(stats.per_transcript[r]):
+            c.append(f"{name},\t{int(stats.per_transcript[r])}\n")
+    return dict(zip(STATS_FILES, ("".join(a), "".join(b), "".join(c))))
+
+
+def write_stats(outdir, stats) -> None:
+    """Write the three files of stats_file_texts(stats) (frontend.CohortStats) into outdir."""
+    import os
+    for name, text in stats_file_texts(stats).items():
+        with open(os.path.join(outdir, name), "wb") as f:
+            f.write(text.encode())
+
+
 def _proband_bytes(b, k: int, bgzf: bool) -> bytes:
     """haplotypes k and k + 1 of an executed batch: their text, or (bgzf, after Batch.bgzf()) their BGZF members and the EOF block"""
     if not bgzf:
