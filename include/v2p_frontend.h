@@ -16,8 +16,12 @@
  *                         per-consequence tables the grouping rule needs, v2p_decode_stats (device) counts the tables on the
  *                         id lists the decode left on the GPU, v2p_groups_stats (host) reads them off the grouped CSR.
  *
+ *   (5) grouping on the device   v2p_decode_groups produces the grouped CSR of (3) on the GPU from the id lists the decode left
+ *                         there; v2p_groups_from_csr (host) wraps it, with the tables of (4), into the v2p_groups of (3).
+ *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
- * libvcf2prot_hip.so exports (2) and the v2p_decode_stats* calls of (4); libv2p_cohort.so (plain C++) exports the rest.
+ * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4) and the v2p_decode_groups* calls of (5); libv2p_cohort.so
+ * (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -228,6 +232,61 @@ int  v2p_decode_stats(struct v2p_ctx* ctx, v2p_decode* d,
 int  v2p_decode_stats_refused(const v2p_decode* d, uint64_t* lists);
 /* milliseconds of the last v2p_decode_stats on d (HIP events): the upload of the tables, the kernel */
 int  v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_kernel);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (5) grouping per transcript on the device.  The rule is that of (3) and (4), in id space: a group exists for every distinct
+ * rank[id] != ~0u of a list, even when none of its ids is mut_ok (such a group has no members); the members of group r are the mut_ok
+ * ids of the list with rank[id] == r or r among extra[id], stably sorted by mut_pos, after drop_replicate.
+ *
+ * Policy of the callers in this repository (v2p_harness vcf, pipeline.vcf_to_fasta): the tables are built once per file; the CSR comes
+ * from v2p_decode_groups and the ids stay on the device.  Only if a list was refused are the ids downloaded, and then the WHOLE file
+ * goes through v2p_groups_build_from_tables, the host path on the same tables.
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* (3)'s per-haplotype phase on tables that already exist: v2p_groups_build = v2p_csq_tables_build + this.  The tables are not
+ * consumed and may be destroyed afterwards.  Errors as v2p_groups_build. */
+int  v2p_groups_build_from_tables(const v2p_csq_tables* t, const uint64_t* hap_begin, const uint32_t* ids, uint64_t n_haps,
+                                  uint32_t n_threads, v2p_groups** out);
+/* A grouped CSR (the four arrays of (3), e.g. from v2p_decode_groups_download) and the tables it was made from, wrapped into a
+ * v2p_groups that every v2p_groups_* call takes.  The arrays are copied.  Returns -1 (and *out with v2p_groups_error set, to be
+ * destroyed) unless the offsets ascend from 0, every rank is below v2p_csq_tables_n_transcripts and ascends strictly inside a list,
+ * and every member id is below v2p_csq_tables_n_consequences and mut_ok. */
+int  v2p_groups_from_csr(const v2p_csq_tables* t, uint64_t n_haps, const uint64_t* hap_group_begin, const uint32_t* group_transcript,
+                         const uint64_t* group_member_begin, const uint32_t* member_ids, v2p_groups** out);
+
+/* Fixed sizes of the grouping kernel, per haplotype list (one workgroup, everything in LDS); 0 = chosen from the file.  A list over
+ * a limit is REFUSED: it gets no groups, nothing of it is written and it is reported, never truncated. */
+typedef struct v2p_groups_caps {
+    uint32_t bitmap_words;      /* present-set bitmap: a list with a transcript rank >= 32 * bitmap_words is refused */
+    uint32_t filter_words;      /* collision pre-filter, a power of two; its size changes which groups are walked for repeats, not results */
+    uint32_t key_capacity;      /* memberships of mut_ok ids per list (own group + every extra whose group is present), a power of two; more -> refused */
+} v2p_groups_caps;
+typedef struct v2p_groups_info {
+    uint64_t n_refused;         /* lists the kernel refused (indices: v2p_decode_groups_refused) */
+    uint64_t n_groups, n_members;                                       /* sizes of the CSR (0 on an abort) */
+    uint32_t bitmap_words, filter_words, key_capacity, lds_bytes;       /* what was launched */
+} v2p_groups_info;
+
+/* The grouped CSR of (3) made on the device from the lists v2p_decode_run / v2p_decode_run_inflated left there.  Table arguments and
+ * argument checks as v2p_decode_stats; when both run on one decode with the same tables these are uploaded once.  An abort of the
+ * reference returns V2P_ERR_DUPLICATE_POS with v2p_last_error_index(ctx) = the smallest aborting list among those not refused and
+ * v2p_last_error(ctx) naming the transcript.  A refused list has no groups in the CSR; a caller with refused lists groups on the host.
+ * The CSR stays on the decode until the next v2p_decode_groups, the next decode run on it, or v2p_decode_destroy.  caps may be null;
+ * info is filled in either way. */
+int  v2p_decode_groups(struct v2p_ctx* ctx, v2p_decode* d,
+                       const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos, const uint32_t* ident,
+                       const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_consequences, uint64_t n_transcripts,
+                       const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len,
+                       const v2p_groups_caps* caps, v2p_groups_info* info);
+/* hap_group_begin[2 * n_samples + 1], group_transcript[info.n_groups], group_member_begin[info.n_groups + 1], member_ids[info.n_members]
+ * of the last successful v2p_decode_groups on d, to host arrays */
+int  v2p_decode_groups_download(v2p_decode* d, uint64_t* hap_group_begin, uint32_t* group_transcript, uint64_t* group_member_begin,
+                                uint32_t* member_ids);
+/* lists[info.n_refused] of the last v2p_decode_groups on d, ascending */
+int  v2p_decode_groups_refused(const v2p_decode* d, uint64_t* lists);
+/* milliseconds of the last v2p_decode_groups / _download on d (HIP events): the upload of the tables (0 when the decode held them),
+ * the count launch, the scan, the emit launch, the download of the CSR */
+int  v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

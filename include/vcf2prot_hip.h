@@ -26,6 +26,8 @@
  * HIP stream.
  * Environment (debugging only, read once per process): V2P_DEBUG_POISON=1 fills every device buffer with 0xA5 whenever
  * a call sizes it -- reused allocations included -- so that no result can depend on what fresh or recycled device memory held;
+ * V2P_GROUPS_KEY_CAPACITY=<power of two> (read by v2p_harness vcf, not by the library) is the key_capacity it hands to v2p_decode_groups,
+ * so that a small file has lists the kernel refuses and the run takes the host grouping;
  * V2P_DECODE_CURSOR64 (v2p_frontend.h) forces the decode's 64-bit cursor kernels; the coalescing queue of v2p_execute_gir_shared
  * takes V2P_COALESCE_MB / _US / _BATCHES / _PROFILE (below).  Launch options are set through v2p_set_launch_opts, not the environment.
  */

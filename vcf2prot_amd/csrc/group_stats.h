@@ -43,6 +43,14 @@ inline uint64_t stats_lds_bytes(uint32_t bitmap_words, uint32_t filter_words, ui
     return 8ull * sort_capacity + 4ull * (2ull * bitmap_words + filter_words + STATS_MISC_WORDS);
 }
 
+// hash of one membership for the (rank, ref_pos) collision pre-filter of the statistics and the grouping kernels
+__device__ __forceinline__ uint32_t filter_hash(uint32_t rank, uint32_t ref_pos)
+{
+    uint32_t h = rank * 0x9E3779B1u ^ (ref_pos + 0x7F4A7C15u) * 0x85EBCA6Bu;
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
+    return h;
+}
+
 hipError_t launch_group_stats(const StatsArgs& a, hipStream_t st);
 
 }  // namespace v2p

@@ -22,13 +22,6 @@ namespace {
 
 enum : uint32_t { M_ERR = 22, M_ERR_CODE, M_REFUSE, M_NSORT, M_ABORT_RANK, M_NPRESENT };
 
-__device__ __forceinline__ uint32_t filter_hash(uint32_t rank, uint32_t ref_pos)
-{
-    uint32_t h = rank * 0x9E3779B1u ^ (ref_pos + 0x7F4A7C15u) * 0x85EBCA6Bu;
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
-    return h;
-}
-
 __global__ __launch_bounds__(STATS_THREADS) void group_stats_kernel(const StatsArgs a)
 {
     extern __shared__ unsigned long long lds_keys[];                   // [C], then the 32-bit arrays

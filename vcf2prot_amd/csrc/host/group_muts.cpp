@@ -234,70 +234,30 @@ void build_tables(Table& T, const v2p_vcf_index* x, const uint8_t* text_u8, uint
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int v2p_csq_tables_build(const v2p_vcf_index* x, const uint8_t* text, uint32_t n_threads, v2p_csq_tables** out)
+// the transcripts and the parsed consequences of the tables, as a v2p_groups carries them
+void fill_from_tables(v2p_groups* g, const Table& T)
 {
-    if (!out) return -1;
-    *out = nullptr;
-    if (!x || !text) return -1;
-    v2p_csq_tables* t = new (std::nothrow) v2p_csq_tables();
-    if (!t) return -1;
-    build_tables(t->T, x, text, n_threads);
-    *out = t;
-    return 0;
-}
-
-void v2p_csq_tables_destroy(v2p_csq_tables* t) { delete t; }
-uint64_t v2p_csq_tables_n_consequences(const v2p_csq_tables* t) { return t ? t->T.rank.size() : 0; }
-uint64_t v2p_csq_tables_n_transcripts(const v2p_csq_tables* t) { return t ? t->T.tx_begin.size() : 0; }
-int v2p_csq_tables_transcript(const v2p_csq_tables* t, uint64_t rank, uint64_t* begin, uint64_t* len)
-{
-    if (!t || rank >= t->T.tx_begin.size() || !begin || !len) return -1;
-    *begin = t->T.tx_begin[rank];
-    *len = t->T.tx_len[rank];
-    return 0;
-}
-const uint64_t* v2p_csq_tables_transcript_begin(const v2p_csq_tables* t) { return t ? t->T.tx_begin.data() : nullptr; }
-const uint32_t* v2p_csq_tables_transcript_len(const v2p_csq_tables* t) { return t ? t->T.tx_len.data() : nullptr; }
-const uint32_t* v2p_csq_tables_rank(const v2p_csq_tables* t) { return t ? t->T.rank.data() : nullptr; }
-const uint32_t* v2p_csq_tables_flags(const v2p_csq_tables* t) { return t ? t->T.flags.data() : nullptr; }
-const uint16_t* v2p_csq_tables_mut_pos(const v2p_csq_tables* t) { return t ? t->T.mut_pos.data() : nullptr; }
-const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t) { return t ? t->T.ref_pos.data() : nullptr; }
-const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t) { return t ? t->T.ident.data() : nullptr; }
-const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t) { return t ? t->T.extra_begin.data() : nullptr; }
-const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t) { return t ? t->T.extra.data() : nullptr; }
-
-int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint64_t* hap_begin, const uint32_t* ids,
-                     uint64_t n_haps, uint32_t n_threads, v2p_groups** out)
-{
-    if (!out) return -1;
-    *out = nullptr;
-    if (!x || !text_u8 || !hap_begin || (!ids && hap_begin[n_haps])) return -1;
-    v2p_groups* g = new (std::nothrow) v2p_groups();
-    if (!g) return -1;
-    *out = g;
-    const uint64_t n_csq = v2p_vcf_index_n_consequences(x);
-    Table T;
-    build_tables(T, x, text_u8, n_threads);
+    const uint64_t n_csq = T.rank.size();
     g->tx_begin = T.tx_begin;
     g->tx_len = T.tx_len;
     g->muts.resize(n_csq);
     g->aa.resize(n_csq);
     for (uint64_t i = 0; i < n_csq; ++i) {
-        Parsed& p = T.parsed[i];
+        const Parsed& p = T.parsed[i];
         v2p_mutation m{};
         m.transcript = T.rank[i];
         if (p.mut_ok) {
             m.valid = 1; m.type = uint8_t(p.type); m.ref_aa_position = p.ref_pos; m.mut_aa_position = p.mut_pos;
-            g->aa[i].ref_aa = std::move(p.ref_aa); g->aa[i].mut_aa = std::move(p.mut_aa);
+            g->aa[i].ref_aa = p.ref_aa; g->aa[i].mut_aa = p.mut_aa;
         }
         g->muts[i] = m;
     }
+}
 
-    // ---- per haplotype ----
+// the per-haplotype phase: every list grouped, sorted and drop_replicated on the worker threads, then stitched into the CSR of g
+int group_lists(v2p_groups* g, const Table& T, const uint64_t* hap_begin, const uint32_t* ids, uint64_t n_haps, uint32_t n_threads)
+{
+    const uint64_t n_csq = T.rank.size();
     struct HapOut { std::vector<uint32_t> group_tx; std::vector<uint32_t> group_size; std::vector<uint32_t> members; };
     std::vector<HapOut> outs(n_haps);
     std::atomic<uint64_t> next{0};
@@ -396,6 +356,104 @@ int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint6
         }
         g->hap_group_begin[h + 1] = g->group_transcript.size();
     }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2p_csq_tables_build(const v2p_vcf_index* x, const uint8_t* text, uint32_t n_threads, v2p_csq_tables** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!x || !text) return -1;
+    v2p_csq_tables* t = new (std::nothrow) v2p_csq_tables();
+    if (!t) return -1;
+    build_tables(t->T, x, text, n_threads);
+    *out = t;
+    return 0;
+}
+
+void v2p_csq_tables_destroy(v2p_csq_tables* t) { delete t; }
+uint64_t v2p_csq_tables_n_consequences(const v2p_csq_tables* t) { return t ? t->T.rank.size() : 0; }
+uint64_t v2p_csq_tables_n_transcripts(const v2p_csq_tables* t) { return t ? t->T.tx_begin.size() : 0; }
+int v2p_csq_tables_transcript(const v2p_csq_tables* t, uint64_t rank, uint64_t* begin, uint64_t* len)
+{
+    if (!t || rank >= t->T.tx_begin.size() || !begin || !len) return -1;
+    *begin = t->T.tx_begin[rank];
+    *len = t->T.tx_len[rank];
+    return 0;
+}
+const uint64_t* v2p_csq_tables_transcript_begin(const v2p_csq_tables* t) { return t ? t->T.tx_begin.data() : nullptr; }
+const uint32_t* v2p_csq_tables_transcript_len(const v2p_csq_tables* t) { return t ? t->T.tx_len.data() : nullptr; }
+const uint32_t* v2p_csq_tables_rank(const v2p_csq_tables* t) { return t ? t->T.rank.data() : nullptr; }
+const uint32_t* v2p_csq_tables_flags(const v2p_csq_tables* t) { return t ? t->T.flags.data() : nullptr; }
+const uint16_t* v2p_csq_tables_mut_pos(const v2p_csq_tables* t) { return t ? t->T.mut_pos.data() : nullptr; }
+const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t) { return t ? t->T.ref_pos.data() : nullptr; }
+const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t) { return t ? t->T.ident.data() : nullptr; }
+const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t) { return t ? t->T.extra_begin.data() : nullptr; }
+const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t) { return t ? t->T.extra.data() : nullptr; }
+
+int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint64_t* hap_begin, const uint32_t* ids,
+                     uint64_t n_haps, uint32_t n_threads, v2p_groups** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!x || !text_u8 || !hap_begin || (!ids && hap_begin[n_haps])) return -1;
+    v2p_groups* g = new (std::nothrow) v2p_groups();
+    if (!g) return -1;
+    *out = g;
+    Table T;
+    build_tables(T, x, text_u8, n_threads);
+    fill_from_tables(g, T);
+    return group_lists(g, T, hap_begin, ids, n_haps, n_threads);
+}
+
+int v2p_groups_build_from_tables(const v2p_csq_tables* t, const uint64_t* hap_begin, const uint32_t* ids, uint64_t n_haps,
+                                 uint32_t n_threads, v2p_groups** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!t || !hap_begin || (!ids && hap_begin[n_haps])) return -1;
+    v2p_groups* g = new (std::nothrow) v2p_groups();
+    if (!g) return -1;
+    *out = g;
+    fill_from_tables(g, t->T);
+    return group_lists(g, t->T, hap_begin, ids, n_haps, n_threads);
+}
+
+int v2p_groups_from_csr(const v2p_csq_tables* t, uint64_t n_haps, const uint64_t* hap_group_begin, const uint32_t* group_transcript,
+                        const uint64_t* group_member_begin, const uint32_t* member_ids, v2p_groups** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if (!t || !hap_group_begin || !group_member_begin) return -1;
+    v2p_groups* g = new (std::nothrow) v2p_groups();
+    if (!g) return -1;
+    *out = g;
+    const Table& T = t->T;
+    auto bad = [&](const std::string& what, int64_t hap) { g->error = "v2p_groups_from_csr: " + what; g->error_hap = hap; return -1; };
+    if (hap_group_begin[0] != 0 || group_member_begin[0] != 0) return bad("offsets must start at 0", -1);
+    for (uint64_t h = 0; h < n_haps; ++h)
+        if (hap_group_begin[h + 1] < hap_group_begin[h]) return bad("hap_group_begin descends", int64_t(h));
+    const uint64_t n_groups = hap_group_begin[n_haps];
+    if (n_groups && !group_transcript) return bad("null group_transcript", -1);
+    for (uint64_t h = 0; h < n_haps; ++h)
+        for (uint64_t k = hap_group_begin[h]; k < hap_group_begin[h + 1]; ++k) {
+            if (group_member_begin[k + 1] < group_member_begin[k]) return bad("group_member_begin descends", int64_t(h));
+            if (group_transcript[k] >= T.tx_begin.size()) return bad("transcript rank outside the tables", int64_t(h));
+            if (k > hap_group_begin[h] && group_transcript[k] <= group_transcript[k - 1]) return bad("transcript ranks must ascend inside a list", int64_t(h));
+        }
+    const uint64_t n_members = group_member_begin[n_groups];
+    if (n_members && !member_ids) return bad("null member_ids", -1);
+    for (uint64_t m = 0; m < n_members; ++m)
+        if (member_ids[m] >= T.rank.size() || !(T.flags[member_ids[m]] & 1u)) return bad("member id outside the tables or not a valid mutation", -1);
+    fill_from_tables(g, T);
+    g->hap_group_begin.assign(hap_group_begin, hap_group_begin + n_haps + 1);
+    g->group_transcript.assign(group_transcript, group_transcript + n_groups);
+    g->group_member_begin.assign(group_member_begin, group_member_begin + n_groups + 1);
+    g->member_ids.assign(member_ids, member_ids + n_members);
     return 0;
 }
 

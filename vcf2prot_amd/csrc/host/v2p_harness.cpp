@@ -6,7 +6,9 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//                                            the per-transcript grouping comes from the GPU (v2p_decode_groups); --host-groups, or a list the kernel
+//                                            refuses, sends the whole file through the host grouping on the same tables -- same bytes;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
 //                                            steps 4-5 produce slices of probands that stream through v2p_pipeline_submit_stream while the next are made
 //   v2p_harness sharded <preset> <samples> --devices N [--oversubscribe] [--threads T] [--streamed [--slice-mb M]]
@@ -360,7 +362,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats)
+                    bool bgzf, bool stats, bool host_groups)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -426,6 +428,12 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     }
     std::vector<uint64_t> hap_begin(2 * S + 1);
     if (v2p_decode_counts(dec, hap_begin.data()) != V2P_OK) { std::fprintf(stderr, "panicked: decode counts unavailable\n"); return 101; }
+    // the file-wide consequence tables, built once: the statistics and the grouping both read them
+    const auto tt = clk::now();
+    v2p_csq_tables* tb = nullptr;
+    if (v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
+    const uint64_t T = v2p_csq_tables_n_transcripts(tb);
+    const double t_tables = since(tt);
     // -s / --stats (main.rs:39-45): the three tables counted on the device from the lists the decode left there
     double t_stats = 0;
     float sms[2] = {0, 0};
@@ -434,9 +442,6 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     std::vector<std::string> st_names;
     if (stats) {
         const auto ts = clk::now();
-        v2p_csq_tables* tb = nullptr;
-        if (v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
-        const uint64_t T = v2p_csq_tables_n_transcripts(tb);
         st_proband.assign(S, 0); st_type.assign(22 * S, 0); st_tx.assign(T + 1, 0);
         const int rc = v2p_decode_stats(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
                                         v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
@@ -455,21 +460,52 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
             v2p_csq_tables_transcript(tb, r, &b, &n);
             st_names.push_back(vcf.substr(b, n));
         }
-        v2p_csq_tables_destroy(tb);
         t_stats = since(ts);
     }
-    std::vector<uint32_t> ids(hap_begin.back() + 1);
-    if (v2p_decode_download(dec, ids.data()) != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
     float kms[4] = {0, 0, 0, 0};
     v2p_decode_timing(dec, &kms[0], &kms[1], &kms[2], &kms[3]);
-    v2p_decode_destroy(dec);
-    t_decode = since(t0); t0 = clk::now();
+    t_decode = since(t0) - t_tables; t0 = clk::now();
+    // the grouping: the CSR made on the device from the resident lists (v2p_decode_groups), wrapped with the tables into a v2p_groups.
+    // Only if a list was refused -- or with --host-groups -- are the ids downloaded, and then the whole file is grouped on the host
+    // from the same tables (v2p_groups_build_from_tables).
     v2p_groups* g = nullptr;
-    if (v2p_groups_build(idx, text, hap_begin.data(), ids.data(), 2 * S, 0, &g) != 0) {
-        std::fprintf(stderr, "panicked: %s\n", v2p_groups_error(g));
-        return 101;
+    v2p_groups_info ginfo{};
+    v2p_groups_caps gcaps{0, 0, 0};
+    if (const char* e = std::getenv("V2P_GROUPS_KEY_CAPACITY")) gcaps.key_capacity = uint32_t(std::strtoul(e, nullptr, 10));
+    float gms[5] = {0, 0, 0, 0, 0};
+    bool device_groups = !host_groups;
+    if (device_groups) {
+        const int rc = v2p_decode_groups(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
+                                         v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
+                                         text, v2p_csq_tables_transcript_begin(tb), v2p_csq_tables_transcript_len(tb), &gcaps, &ginfo);
+        if (rc != V2P_OK && !(rc == V2P_ERR_DUPLICATE_POS && ginfo.n_refused)) {      // (with refused lists the host path reports the smallest aborting list)
+            std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw()));
+            v2p_csq_tables_destroy(tb);
+            v2p_decode_destroy(dec);
+            return 101;
+        }
+        if (rc != V2P_OK || ginfo.n_refused) device_groups = false;
     }
-    t_group = since(t0); t0 = clk::now();
+    if (device_groups) {
+        std::vector<uint64_t> c_hgb(2 * S + 1), c_gmb(ginfo.n_groups + 1);
+        std::vector<uint32_t> c_gtx(ginfo.n_groups + 1), c_mid(ginfo.n_members + 1);
+        if (v2p_decode_groups_download(dec, c_hgb.data(), c_gtx.data(), c_gmb.data(), c_mid.data()) != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
+        if (v2p_groups_from_csr(tb, 2 * S, c_hgb.data(), c_gtx.data(), c_gmb.data(), c_mid.data(), &g) != 0) {
+            std::fprintf(stderr, "panicked: %s\n", v2p_groups_error(g));
+            return 101;
+        }
+    } else {
+        std::vector<uint32_t> ids(hap_begin.back() + 1);
+        if (v2p_decode_download(dec, ids.data()) != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
+        if (v2p_groups_build_from_tables(tb, hap_begin.data(), ids.data(), 2 * S, 0, &g) != 0) {
+            std::fprintf(stderr, "panicked: %s\n", v2p_groups_error(g));
+            return 101;
+        }
+    }
+    v2p_decode_groups_timing(dec, &gms[0], &gms[1], &gms[2], &gms[3], &gms[4]);
+    v2p_decode_destroy(dec);
+    v2p_csq_tables_destroy(tb);
+    t_group = t_tables + since(t0); t0 = clk::now();     // the file-wide tables and the per-haplotype phase, as v2p_groups_build had them
     if (stats) {
         const auto ts = clk::now();
         // lists the kernel refused: the grouping above holds every list, so the tables are read off it
@@ -752,18 +788,23 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     t_write = host_build ? since(t0) : t_write_acc;
     char stats_seconds[48] = "";
     if (stats) std::snprintf(stats_seconds, sizeof(stats_seconds), ", \"stats\": %.4f", t_stats);
+    char tables_seconds[48];
+    std::snprintf(tables_seconds, sizeof(tables_seconds), ", \"tables\": %.4f", t_tables);
     std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
                 (unsigned long long)written, outdir);
     std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
-                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f%s}, "
+                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f%s%s}, "
                 "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}, \"input_format\": \"%s\", "
                 "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}",
                 (unsigned long long)R, (unsigned long long)S, (unsigned long long)written, (unsigned long long)n_slices, (unsigned long long)n_fallback,
                 t_read, t_index, t_decode, t_group, t_build, t_exec, t_write,
-                since(t_start), t_inflate, stats_seconds, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
+                since(t_start), t_inflate, stats_seconds, tables_seconds, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
     if (stats)
         std::printf(", \"stats_ms\": {\"upload\": %.3f, \"kernel\": %.3f, \"refused_lists\": %llu, \"sorted_members\": %llu, \"lds_bytes\": %u}",
                     sms[0], sms[1], (unsigned long long)sinfo.n_refused, (unsigned long long)sinfo.n_sorted_members, sinfo.lds_bytes);
+    std::printf(", \"groups\": {\"path\": \"%s\", \"n_refused\": %llu, \"key_capacity\": %u, \"lds_bytes\": %u, \"ms_upload\": %.3f, \"ms_count\": %.3f, "
+                "\"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f}", device_groups ? "device" : "host", (unsigned long long)ginfo.n_refused,
+                ginfo.key_capacity, ginfo.lds_bytes, gms[0], gms[1], gms[2], gms[3], gms[4]);
     std::printf("}\n");
     v2p_batch_destroy(b);
     v2p_groups_destroy(g);
@@ -867,19 +908,20 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
             no_test |= !std::strcmp(argv[i], "--no-test");
             host_build |= !std::strcmp(argv[i], "--host-build");
+            host_groups |= !std::strcmp(argv[i], "--host-groups");
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

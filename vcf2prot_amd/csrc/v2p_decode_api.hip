@@ -12,6 +12,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "../../include/v2p_frontend.h"
 #include "decode_kernels.h"
+#include "group_csr.h"
 #include "group_stats.h"
 #include "inflate_format.hpp"
 #include "v2p_ctx_internal.h"
@@ -34,14 +35,42 @@ struct v2p_decode {
     float ms_inflate[3] = {0, 0, 0};  // upload of the members, inflate kernel, text to the host
     float ms_stats[2] = {0, 0};       // v2p_decode_stats: upload of the tables, kernel
     std::vector<uint64_t> refused;    // lists the last v2p_decode_stats refused
+    // the file-wide tables of v2p_decode_stats / v2p_decode_groups on the device, kept while the next call brings the same ones
+    std::vector<StatsRec> tab_rec;
+    std::vector<uint32_t> tab_extra_begin, tab_extra;
+    StatsRec* d_tab_rec = nullptr;
+    uint32_t* d_tab_extra_begin = nullptr;
+    uint32_t* d_tab_extra = nullptr;
+    // v2p_decode_groups: the grouped CSR on the device until the next call
+    uint64_t* d_hap_group_begin = nullptr;    // [n_haps + 1], then the member bases [n_haps + 1]
+    uint32_t* d_group_transcript = nullptr;
+    uint64_t* d_group_member_begin = nullptr;
+    uint32_t* d_member_ids = nullptr;
+    uint64_t n_groups = 0, n_members = 0;
+    bool groups_ok = false;
+    float ms_groups[5] = {0, 0, 0, 0, 0};     // upload of the tables, count, scan, emit, download
+    std::vector<uint64_t> groups_refused;
+    void release_groups() {
+        for (void* p : {(void*)d_hap_group_begin, (void*)d_group_transcript, (void*)d_group_member_begin, (void*)d_member_ids})
+            if (p) (void)hipFree(p);
+        d_hap_group_begin = nullptr; d_group_transcript = nullptr; d_group_member_begin = nullptr; d_member_ids = nullptr;
+        n_groups = n_members = 0; groups_ok = false;
+    }
+    void release_tables() {
+        for (void* p : {(void*)d_tab_rec, (void*)d_tab_extra_begin, (void*)d_tab_extra}) if (p) (void)hipFree(p);
+        d_tab_rec = nullptr; d_tab_extra_begin = nullptr; d_tab_extra = nullptr;
+        tab_rec.clear(); tab_extra_begin.clear(); tab_extra.clear();
+    }
     void release_lists() {
         for (void* p : {(void*)d_rows, (void*)d_csq, (void*)d_work, (void*)d_hap_begin, (void*)d_ids, (void*)d_status})
             if (p) (void)hipFree(p);
         d_rows = nullptr; d_csq = nullptr; d_work = nullptr; d_hap_begin = nullptr; d_ids = nullptr; d_status = nullptr;
         n_ids = 0;
+        release_groups();
     }
     void release() {
         release_lists();
+        release_tables();
         if (d_text) (void)hipFree(d_text);
         d_text = nullptr;
     }
@@ -232,6 +261,59 @@ static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begi
     return rc;
 }
 
+// the reference's words for an aborting list (low word of the kernels' status[0]: group_stats.h)
+static std::string abort_message(uint32_t why, uint64_t n_tx, const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len)
+{
+    if (why == STATS_ERR_POISON) return "start_lost consequence with fewer than three fields (text_parser.rs:52 would abort)";
+    if (why == STATS_ERR_RANGE) return "consequence id out of range";
+    const uint32_t r = why - 1;
+    return "Encountered a logical error with analyzing mutations in transcript: " +
+           (tx_text && tx_begin && tx_len && r < n_tx ? std::string(reinterpret_cast<const char*>(tx_text) + tx_begin[r], tx_len[r]) : "rank " + std::to_string(r));
+}
+
+// the checks v2p_decode_stats and v2p_decode_groups share on the seven table arrays, one 16-byte row per consequence id, and the rows
+// and the extra CSR on the device: uploaded unless d already holds exactly these tables (*uploaded says which)
+static int prepare_tables(v2p_ctx* ctx, v2p_decode* d, const char* fn, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos,
+                          const uint16_t* ref_pos, const uint32_t* ident, const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_csq,
+                          uint64_t n_tx, hipStream_t st, bool* uploaded)
+{
+    const std::string f(fn);
+    *uploaded = false;
+    if (n_csq >= 0xffffffffull || n_tx > STATS_MAX_RANKS)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts or 2^32 consequences", -1);
+    std::vector<StatsRec> rec(n_csq + 1);
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        if (extra_begin[i + 1] < extra_begin[i] || extra_begin[i + 1] - extra_begin[i] > 0xffffu)
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": extra_begin must ascend by at most 65535 per consequence", int64_t(i));
+        if ((flags[i] & 1u) && ((flags[i] >> 8 & 0xffu) >= STATS_TYPES || rank[i] == ~0u))
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": a mut_ok consequence needs a type below 22 and a transcript", int64_t(i));
+        if (rank[i] != ~0u && rank[i] >= n_tx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": rank outside the transcripts", int64_t(i));
+        rec[i] = StatsRec{rank[i], (flags[i] & 0xffffu) | (extra_begin[i + 1] - extra_begin[i]) << 16, uint32_t(mut_pos[i]) | uint32_t(ref_pos[i]) << 16, ident[i]};
+    }
+    rec[n_csq] = StatsRec{~0u, 0u, 0u, ~0u};
+    const uint64_t n_extra = n_csq ? extra_begin[n_csq] : 0;
+    const uint32_t zero = 0;
+    const uint32_t* eb = n_csq ? extra_begin : &zero;
+    if (d->d_tab_rec && d->tab_rec.size() == rec.size() && d->tab_extra.size() == n_extra &&
+        !memcmp(d->tab_rec.data(), rec.data(), rec.size() * sizeof(StatsRec)) &&
+        !memcmp(d->tab_extra_begin.data(), eb, (n_csq + 1) * sizeof(uint32_t)) &&
+        (!n_extra || !memcmp(d->tab_extra.data(), extra, n_extra * sizeof(uint32_t))))
+        return V2P_OK;
+    d->release_tables();
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_rec), rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_extra_begin), (n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_extra), (n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
+    d->tab_rec.swap(rec);
+    d->tab_extra_begin.assign(eb, eb + n_csq + 1);
+    d->tab_extra.assign(extra, extra + n_extra);
+    // (the copies are made from the decode's own vectors: they outlive the stream's work)
+    RTRY(hipMemcpyAsync(d->d_tab_rec, d->tab_rec.data(), d->tab_rec.size() * sizeof(StatsRec), hipMemcpyHostToDevice, st), "H2D(stats rows)");
+    RTRY(hipMemcpyAsync(d->d_tab_extra_begin, d->tab_extra_begin.data(), (n_csq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra_begin)");
+    if (n_extra) RTRY(hipMemcpyAsync(d->d_tab_extra, d->tab_extra.data(), n_extra * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra)");
+    *uploaded = true;
+    return V2P_OK;
+}
+
 extern "C" {
 
 uint64_t v2p_decode_workspace_bytes(uint64_t n_records, uint64_t n_samples, uint64_t ovf_words)
@@ -413,20 +495,22 @@ int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const ui
     if (!per_proband || !per_type || (n_tx && !per_transcript) || !info ||
         (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !extra_begin)) || (n_csq && extra_begin[n_csq] && !extra))
         return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: null argument", -1);
-    if (n_csq >= 0xffffffffull || n_tx > STATS_MAX_RANKS)
-        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: more than 2^24 transcripts or 2^32 consequences", -1);
     const uint64_t S = d->n_samples, n_haps = 2 * S;
-    // one 16-byte row per consequence id
-    std::vector<StatsRec> rec(n_csq + 1);
-    for (uint64_t i = 0; i < n_csq; ++i) {
-        if (extra_begin[i + 1] < extra_begin[i] || extra_begin[i + 1] - extra_begin[i] > 0xffffu)
-            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: extra_begin must ascend by at most 65535 per consequence", int64_t(i));
-        if ((flags[i] & 1u) && ((flags[i] >> 8 & 0xffu) >= STATS_TYPES || rank[i] == ~0u))
-            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: a mut_ok consequence needs a type below 22 and a transcript", int64_t(i));
-        if (rank[i] != ~0u && rank[i] >= n_tx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: rank outside the transcripts", int64_t(i));
-        rec[i] = StatsRec{rank[i], (flags[i] & 0xffffu) | (extra_begin[i + 1] - extra_begin[i]) << 16, uint32_t(mut_pos[i]) | uint32_t(ref_pos[i]) << 16, ident[i]};
-    }
-    const uint64_t n_extra = n_csq ? extra_begin[n_csq] : 0;
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    struct Temp {                                       // freed on every exit path
+        void* p[2] = {nullptr, nullptr};
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
+    } tmp;
+    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
+    d->refused.clear();
+    d->ms_stats[0] = d->ms_stats[1] = 0;
+    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
+    bool uploaded = false;
+    const int trc = prepare_tables(ctx, d, "v2p_decode_stats", rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, st, &uploaded);
+    if (trc != V2P_OK) return trc;
+    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
     uint64_t max_len = 0;
     for (uint64_t h = 0; h < n_haps; ++h) max_len = std::max(max_len, d->hap_begin[h + 1] - d->hap_begin[h]);
     // sizes: the bitmap covers every transcript; the filter gets about 32 bits per id of the longest list inside 64 KiB of LDS, and
@@ -450,69 +534,41 @@ int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const ui
         return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: filter_words and sort_capacity must be powers of two and all of it fit 160 KiB of LDS", -1);
     info->n_refused = 0; info->n_sorted_members = 0;
     info->bitmap_words = W; info->filter_words = F; info->sort_capacity = C; info->lds_bytes = uint32_t(stats_lds_bytes(W, F, C));
-    d->refused.clear();
-    d->ms_stats[0] = d->ms_stats[1] = 0;
 
-    (void)hipSetDevice(ctx_device(ctx));
-    hipStream_t st = ctx_stream(ctx);
-    struct Temp {                                       // freed on every exit path
-        void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } tmp;
     const uint64_t n_out = 23 * S + n_tx + 3;           // per_proband | per_type | per_transcript | status
-    RTRY(dmalloc(&tmp.p[0], rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
-    RTRY(dmalloc(&tmp.p[1], (n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
-    RTRY(dmalloc(&tmp.p[2], (n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
-    RTRY(dmalloc(&tmp.p[3], n_out * sizeof(uint64_t)), "hipMalloc(stats tables)");
-    RTRY(dmalloc(&tmp.p[4], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
-    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
-    const uint32_t zero = 0;
-    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
-    RTRY(hipMemcpyAsync(tmp.p[0], rec.data(), rec.size() * sizeof(StatsRec), hipMemcpyHostToDevice, st), "H2D(stats rows)");
-    RTRY(hipMemcpyAsync(tmp.p[1], n_csq ? extra_begin : &zero, (n_csq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra_begin)");
-    if (n_extra) RTRY(hipMemcpyAsync(tmp.p[2], extra, n_extra * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra)");
-    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
-    uint64_t* d_out = static_cast<uint64_t*>(tmp.p[3]);
+    RTRY(dmalloc(&tmp.p[0], n_out * sizeof(uint64_t)), "hipMalloc(stats tables)");
+    RTRY(dmalloc(&tmp.p[1], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
+    uint64_t* d_out = static_cast<uint64_t*>(tmp.p[0]);
     RTRY(hipMemsetAsync(d_out, 0, n_out * sizeof(uint64_t), st), "hipMemset(stats tables)");
     RTRY(hipMemsetAsync(d_out + 23 * S + n_tx, 0xFF, sizeof(uint64_t), st), "hipMemset(stats status)");
-    RTRY(hipMemsetAsync(tmp.p[4], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
+    RTRY(hipMemsetAsync(tmp.p[1], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
     StatsArgs a{};
     a.hap_begin = d->d_hap_begin; a.ids = d->d_ids; a.n_haps = uint32_t(n_haps);
-    a.rec = static_cast<const StatsRec*>(tmp.p[0]); a.extra_begin = static_cast<const uint32_t*>(tmp.p[1]);
-    a.extra = static_cast<const uint32_t*>(tmp.p[2]); a.n_csq = uint32_t(n_csq);
+    a.rec = d->d_tab_rec; a.extra_begin = d->d_tab_extra_begin; a.extra = d->d_tab_extra; a.n_csq = uint32_t(n_csq);
     a.per_proband = reinterpret_cast<unsigned long long*>(d_out);
     a.per_type = reinterpret_cast<unsigned long long*>(d_out + S);
     a.per_transcript = reinterpret_cast<unsigned long long*>(d_out + 23 * S);
     a.status = reinterpret_cast<unsigned long long*>(d_out + 23 * S + n_tx);
-    a.refused = static_cast<uint32_t*>(tmp.p[4]);
+    a.refused = static_cast<uint32_t*>(tmp.p[1]);
     a.bitmap_words = W; a.filter_words = F; a.sort_capacity = C;
     RTRY(launch_group_stats(a, st), "group_stats_kernel");
     RTRY(hipEventRecord(tmp.e[2], st), "hipEventRecord");
     std::vector<uint64_t> out(n_out);
     RTRY(hipMemcpyAsync(out.data(), d_out, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(stats tables)");
     RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    (void)hipEventElapsedTime(&d->ms_stats[0], tmp.e[0], tmp.e[1]);
+    if (uploaded) (void)hipEventElapsedTime(&d->ms_stats[0], tmp.e[0], tmp.e[1]);
     (void)hipEventElapsedTime(&d->ms_stats[1], tmp.e[1], tmp.e[2]);
     const uint64_t* status = out.data() + 23 * S + n_tx;
     info->n_refused = status[1]; info->n_sorted_members = status[2];
     if (status[1]) {
         std::vector<uint32_t> fl(n_haps);
-        RTRY(hipMemcpy(fl.data(), tmp.p[4], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
+        RTRY(hipMemcpy(fl.data(), tmp.p[1], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
         for (uint64_t h = 0; h < n_haps; ++h) if (fl[h]) d->refused.push_back(h);
     }
     if (status[0] != ~0ull) {
         const uint64_t hap = status[0] >> 32;
         const uint32_t why = uint32_t(status[0]);
-        std::string msg;
-        if (why == STATS_ERR_POISON) msg = "start_lost consequence with fewer than three fields (text_parser.rs:52 would abort)";
-        else if (why == STATS_ERR_RANGE) msg = "consequence id out of range";
-        else {
-            const uint32_t r = why - 1;
-            msg = "Encountered a logical error with analyzing mutations in transcript: " +
-                  (tx_text && tx_begin && tx_len && r < n_tx ? std::string(reinterpret_cast<const char*>(tx_text) + tx_begin[r], tx_len[r]) : "rank " + std::to_string(r));
-        }
-        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, msg, int64_t(hap));
+        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, abort_message(why, n_tx, tx_text, tx_begin, tx_len), int64_t(hap));
     }
     memcpy(per_proband, out.data(), S * sizeof(uint64_t));
     memcpy(per_type, out.data() + S, 22 * S * sizeof(uint64_t));
@@ -532,6 +588,155 @@ int v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_ker
     if (!d) return V2P_ERR_INVALID_ARG;
     if (ms_upload) *ms_upload = d->ms_stats[0];
     if (ms_kernel) *ms_kernel = d->ms_stats[1];
+    return V2P_OK;
+}
+
+int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos,
+                      const uint32_t* ident, const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_csq, uint64_t n_tx,
+                      const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len, const v2p_groups_caps* caps, v2p_groups_info* info)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    if (!d || d->ctx != ctx || !d->d_hap_begin || d->hap_begin.empty())
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: needs a decode that holds lists (v2p_decode_run / v2p_decode_run_inflated)", -1);
+    if (!info || (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !extra_begin)) || (n_csq && extra_begin[n_csq] && !extra))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: null argument", -1);
+    const uint64_t n_haps = 2 * d->n_samples;
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    d->release_groups();
+    d->groups_refused.clear();
+    for (float& x : d->ms_groups) x = 0;
+    struct Temp {                                       // freed on every exit path
+        void* p[3] = {nullptr, nullptr, nullptr};
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
+    } tmp;
+    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
+    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
+    bool uploaded = false;
+    const int trc = prepare_tables(ctx, d, "v2p_decode_groups", rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, st, &uploaded);
+    if (trc != V2P_OK) return trc;
+    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
+    uint64_t max_len = 0;
+    for (uint64_t h = 0; h < n_haps; ++h) max_len = std::max(max_len, d->hap_begin[h + 1] - d->hap_begin[h]);
+    // sizes: the bitmap covers every transcript; keys for the longest list and an eighth more (extras are rare), at least 2 048, a power of two; the
+    // filter gets about 32 bits per id of the longest list.  Whatever does not fit 160 KiB of LDS shrinks, and lists over it are refused.
+    auto pow2_floor = [](uint64_t v) { uint64_t p = 1; while (p * 2 <= v) p *= 2; return p; };
+    auto pow2_ceil = [](uint64_t v) { uint64_t p = 1; while (p < v) p *= 2; return p; };
+    const uint64_t lds_max = 160u * 1024u;
+    uint64_t W = caps && caps->bitmap_words ? caps->bitmap_words : std::max<uint64_t>(1, (n_tx + 31) / 32);
+    uint64_t C = caps && caps->key_capacity ? caps->key_capacity : pow2_ceil(std::max<uint64_t>(2048, max_len + max_len / 8));
+    uint64_t F = caps ? caps->filter_words : 0u;
+    if (!(caps && caps->bitmap_words)) W = std::min<uint64_t>(W, (lds_max - groups_lds_bytes(0, 32, 64)) / 12);
+    if (!(caps && caps->key_capacity))
+        while (C > 64 && (C > (1u << 20) || groups_lds_bytes(uint32_t(W), 32, uint32_t(C)) > lds_max)) C /= 2;
+    if (W > STATS_MAX_RANKS / 32 || C > (1u << 20) || F > (1u << 20))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: filter_words and key_capacity must be powers of two and all of it fit 160 KiB of LDS", -1);
+    if (!F) {
+        const uint64_t fixed = groups_lds_bytes(uint32_t(W), 0, uint32_t(C));
+        const uint64_t room = fixed + 4 * 32 <= lds_max ? pow2_floor((lds_max - fixed) / 4) : 32;
+        F = std::max<uint64_t>(32, std::min(pow2_ceil(std::max<uint64_t>(32, max_len)), room));
+    }
+    if ((F & (F - 1)) || (C & (C - 1)) || groups_lds_bytes(uint32_t(W), uint32_t(F), uint32_t(C)) > lds_max)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: filter_words and key_capacity must be powers of two and all of it fit 160 KiB of LDS", -1);
+    info->n_refused = info->n_groups = info->n_members = 0;
+    info->bitmap_words = uint32_t(W); info->filter_words = uint32_t(F); info->key_capacity = uint32_t(C);
+    info->lds_bytes = uint32_t(groups_lds_bytes(uint32_t(W), uint32_t(F), uint32_t(C)));
+
+    RTRY(dmalloc(&tmp.p[0], 2 * n_haps * sizeof(uint32_t)), "hipMalloc(group counts)");
+    RTRY(dmalloc(&tmp.p[1], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
+    RTRY(dmalloc(&tmp.p[2], 2 * sizeof(uint64_t)), "hipMalloc(groups status)");
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_hap_group_begin), 2 * (n_haps + 1) * sizeof(uint64_t)), "hipMalloc(hap_group_begin)");
+    RTRY(hipMemsetAsync(tmp.p[1], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
+    RTRY(hipMemsetAsync(tmp.p[2], 0, 2 * sizeof(uint64_t), st), "hipMemset(groups status)");
+    RTRY(hipMemsetAsync(tmp.p[2], 0xFF, sizeof(uint64_t), st), "hipMemset(groups status)");
+    GroupsArgs a{};
+    a.hap_begin = d->d_hap_begin; a.ids = d->d_ids; a.n_haps = uint32_t(n_haps);
+    a.rec = d->d_tab_rec; a.extra_begin = d->d_tab_extra_begin; a.extra = d->d_tab_extra; a.n_csq = uint32_t(n_csq);
+    a.counts = static_cast<uint32_t*>(tmp.p[0]); a.refused = static_cast<uint32_t*>(tmp.p[1]);
+    a.status = static_cast<unsigned long long*>(tmp.p[2]);
+    a.hap_group_begin = reinterpret_cast<unsigned long long*>(d->d_hap_group_begin);
+    a.hap_member_begin = a.hap_group_begin + n_haps + 1;
+    a.bitmap_words = uint32_t(W); a.filter_words = uint32_t(F); a.key_capacity = uint32_t(C);
+    RTRY(launch_groups_count(a, st), "group_csr_kernel (count)");
+    RTRY(hipEventRecord(tmp.e[2], st), "hipEventRecord");
+    RTRY(launch_groups_scan(a, st), "group_csr_scan_kernel");
+    RTRY(hipEventRecord(tmp.e[3], st), "hipEventRecord");
+    uint64_t status[2] = {~0ull, 0}, totals[2] = {0, 0};
+    RTRY(hipMemcpyAsync(status, tmp.p[2], sizeof(status), hipMemcpyDeviceToHost, st), "D2H(groups status)");
+    RTRY(hipMemcpyAsync(&totals[0], d->d_hap_group_begin + n_haps, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group total)");
+    RTRY(hipMemcpyAsync(&totals[1], d->d_hap_group_begin + 2 * n_haps + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(member total)");
+    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (uploaded) (void)hipEventElapsedTime(&d->ms_groups[0], tmp.e[0], tmp.e[1]);
+    (void)hipEventElapsedTime(&d->ms_groups[1], tmp.e[1], tmp.e[2]);
+    (void)hipEventElapsedTime(&d->ms_groups[2], tmp.e[2], tmp.e[3]);
+    info->n_refused = status[1];
+    if (status[1]) {
+        std::vector<uint32_t> fl(n_haps);
+        RTRY(hipMemcpy(fl.data(), tmp.p[1], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
+        for (uint64_t h = 0; h < n_haps; ++h) if (fl[h]) d->groups_refused.push_back(h);
+    }
+    if (status[0] != ~0ull) {
+        d->release_groups();
+        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, abort_message(uint32_t(status[0]), n_tx, tx_text, tx_begin, tx_len), int64_t(status[0] >> 32));
+    }
+    d->n_groups = totals[0]; d->n_members = totals[1];
+    info->n_groups = totals[0]; info->n_members = totals[1];
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_group_transcript), (d->n_groups + 1) * sizeof(uint32_t)), "hipMalloc(group_transcript)");
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_group_member_begin), (d->n_groups + 1) * sizeof(uint64_t)), "hipMalloc(group_member_begin)");
+    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_member_ids), (d->n_members + 1) * sizeof(uint32_t)), "hipMalloc(member_ids)");
+    a.group_transcript = d->d_group_transcript;
+    a.group_member_begin = reinterpret_cast<unsigned long long*>(d->d_group_member_begin);
+    a.member_ids = d->d_member_ids;
+    a.n_groups = d->n_groups; a.n_members = d->n_members;
+    RTRY(hipEventRecord(tmp.e[3], st), "hipEventRecord");
+    RTRY(launch_groups_emit(a, st), "group_csr_kernel (emit)");
+    RTRY(hipEventRecord(tmp.e[4], st), "hipEventRecord");
+    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&d->ms_groups[3], tmp.e[3], tmp.e[4]);
+    d->groups_ok = true;
+    return V2P_OK;
+}
+
+int v2p_decode_groups_download(v2p_decode* d, uint64_t* hap_group_begin, uint32_t* group_transcript, uint64_t* group_member_begin, uint32_t* member_ids)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    Guard g(d->ctx);
+    v2p_ctx* ctx = d->ctx;
+    if (!d->groups_ok) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups_download: needs a successful v2p_decode_groups on this decode", -1);
+    if (!hap_group_begin || !group_member_begin || (d->n_groups && !group_transcript) || (d->n_members && !member_ids))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups_download: null argument", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    struct Events {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+    } evs;
+    for (auto& e : evs.e) RTRY(hipEventCreate(&e), "hipEventCreate");
+    RTRY(hipEventRecord(evs.e[0], st), "hipEventRecord");
+    RTRY(hipMemcpyAsync(hap_group_begin, d->d_hap_group_begin, (2 * d->n_samples + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_group_begin)");
+    RTRY(hipMemcpyAsync(group_member_begin, d->d_group_member_begin, (d->n_groups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group_member_begin)");
+    if (d->n_groups) RTRY(hipMemcpyAsync(group_transcript, d->d_group_transcript, d->n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(group_transcript)");
+    if (d->n_members) RTRY(hipMemcpyAsync(member_ids, d->d_member_ids, d->n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(member_ids)");
+    RTRY(hipEventRecord(evs.e[1], st), "hipEventRecord");
+    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&d->ms_groups[4], evs.e[0], evs.e[1]);
+    return V2P_OK;
+}
+
+int v2p_decode_groups_refused(const v2p_decode* d, uint64_t* lists)
+{
+    if (!d || (!lists && !d->groups_refused.empty())) return V2P_ERR_INVALID_ARG;
+    if (!d->groups_refused.empty()) memcpy(lists, d->groups_refused.data(), d->groups_refused.size() * sizeof(uint64_t));
+    return V2P_OK;
+}
+
+int v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    float* out[5] = {ms_upload, ms_count, ms_scan, ms_emit, ms_download};
+    for (int k = 0; k < 5; ++k) if (out[k]) *out[k] = d->ms_groups[k];
     return V2P_OK;
 }
 

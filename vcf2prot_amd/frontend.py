@@ -52,6 +52,11 @@ DECODE_API = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_decode_stats_refused": (c_int, [c_void_p, c_void_p]),
     "v2p_decode_stats_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float)]),
+    "v2p_decode_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_decode_groups_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_decode_groups_refused": (c_int, [c_void_p, c_void_p]),
+    "v2p_decode_groups_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -80,6 +85,8 @@ HOST_API = {
     "v2p_groups_group_member_begin": (POINTER(c_uint64), [c_void_p]),
     "v2p_groups_member_ids": (POINTER(c_uint32), [c_void_p]),
     "v2p_groups_stats": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "v2p_groups_build_from_tables": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, POINTER(c_void_p)]),
+    "v2p_groups_from_csr": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "v2p_csq_tables_build": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "v2p_csq_tables_destroy": (None, [c_void_p]),
     "v2p_csq_tables_n_consequences": (c_uint64, [c_void_p]),
@@ -104,6 +111,17 @@ class v2p_stats_caps(ctypes.Structure):
 class v2p_stats_info(ctypes.Structure):
     _fields_ = [("n_refused", c_uint64), ("n_sorted_members", c_uint64), ("bitmap_words", c_uint32), ("filter_words", c_uint32),
                 ("sort_capacity", c_uint32), ("lds_bytes", c_uint32)]
+
+
+
+class v2p_groups_caps(ctypes.Structure):
+    _fields_ = [("bitmap_words", c_uint32), ("filter_words", c_uint32), ("key_capacity", c_uint32)]
+
+
+class v2p_groups_info(ctypes.Structure):
+    _fields_ = [("n_refused", c_uint64), ("n_groups", c_uint64), ("n_members", c_uint64), ("bitmap_words", c_uint32), ("filter_words", c_uint32),
+                ("key_capacity", c_uint32), ("lds_bytes", c_uint32)]
+
 
 _bound = {}
 
@@ -308,13 +326,40 @@ def _decode_run(ctx, idx: VcfIndex, inflated: "InflatedText" = None):
 class Groups:
     """IntMap in id space (Map.rs:5-31): per haplotype the AltTranscripts, members as consequence ids."""
 
+    path, info = "host", None                                           # device_groups sets them: where the CSR was made, what was launched
+
     def __init__(self, idx: VcfIndex, lists: HaplotypeLists, n_threads: int = 0):
         self._lib = _host()
-        self._idx = idx
         h = c_void_p()
         rc = self._lib.v2p_groups_build(idx._h, idx.text.ctypes.data, lists.hap_begin.ctypes.data,
                                         lists.ids.ctypes.data if lists.ids.size else None, lists.n_haplotypes, n_threads, ctypes.byref(h))
-        self._h = h
+        self._take(idx, h, rc, lists.n_haplotypes)
+
+    @classmethod
+    def from_tables(cls, tables: "CsqTables", lists: HaplotypeLists, n_threads: int = 0) -> "Groups":
+        """v2p_groups_build_from_tables: the per-haplotype phase alone, on tables that exist (they are not consumed)."""
+        g = cls.__new__(cls)
+        g._lib = _host()
+        h = c_void_p()
+        rc = g._lib.v2p_groups_build_from_tables(tables._h, lists.hap_begin.ctypes.data, lists.ids.ctypes.data if lists.ids.size else None,
+                                                 lists.n_haplotypes, n_threads, ctypes.byref(h))
+        g._take(tables._idx, h, rc, lists.n_haplotypes)
+        return g
+
+    @classmethod
+    def from_csr(cls, tables: "CsqTables", hap_group_begin, group_transcript, group_member_begin, member_ids) -> "Groups":
+        """v2p_groups_from_csr: a grouped CSR (device_groups_csr) and the tables it was made from; a malformed CSR raises V2PError."""
+        g = cls.__new__(cls)
+        g._lib = _host()
+        a = [np.ascontiguousarray(hap_group_begin, np.uint64), np.ascontiguousarray(group_transcript, np.uint32),
+             np.ascontiguousarray(group_member_begin, np.uint64), np.ascontiguousarray(member_ids, np.uint32)]
+        h = c_void_p()
+        rc = g._lib.v2p_groups_from_csr(tables._h, a[0].size - 1, *[x.ctypes.data if x.size else None for x in a], ctypes.byref(h))
+        g._take(tables._idx, h, rc, a[0].size - 1)
+        return g
+
+    def _take(self, idx, h, rc, n_haps):
+        self._idx, self._h = idx, h
         if rc != 0:
             msg = self._lib.v2p_groups_error(h).decode() if h else "grouping failed"
             hap = int(self._lib.v2p_groups_error_haplotype(h)) if h else -1
@@ -322,16 +367,19 @@ class Groups:
             raise N.V2PError(rc, msg, hap)
         L = self._lib
         self.n_transcripts = int(L.v2p_groups_n_transcripts(h))
-        self.hap_group_begin = _arr(L.v2p_groups_hap_group_begin(h), lists.n_haplotypes + 1, np.uint64)
+        self.hap_group_begin = _arr(L.v2p_groups_hap_group_begin(h), n_haps + 1, np.uint64)
         n_groups = int(self.hap_group_begin[-1])
         self.group_transcript = _arr(L.v2p_groups_group_transcript(h), n_groups, np.uint32)
         self.group_member_begin = _arr(L.v2p_groups_group_member_begin(h), n_groups + 1, np.uint64)
         self.member_ids = _arr(L.v2p_groups_member_ids(h), int(self.group_member_begin[-1]), np.uint32)
         m = L.v2p_groups_mutations(h)
-        self._n_samples = lists.n_haplotypes // 2
+        self._n_samples = n_haps // 2
         self.mutations = np.ctypeslib.as_array(ctypes.cast(m, POINTER(c_uint8)), shape=(idx.n_consequences * ctypes.sizeof(v2p_mutation),)).view(
             np.dtype([("transcript", "<u4"), ("ref_aa_position", "<u2"), ("mut_aa_position", "<u2"), ("type", "u1"), ("valid", "u1"), ("pad", "u1", 2)])).copy() \
             if idx.n_consequences else None
+
+    def csr(self):
+        return self.hap_group_begin, self.group_transcript, self.group_member_begin, self.member_ids
 
     def transcript_name(self, rank: int) -> str:
         b, n = c_uint64(), c_uint64()
@@ -411,6 +459,57 @@ class CsqTables:
 
     def __del__(self):
         self.close()
+
+
+def device_groups_csr(ctx, resident: ResidentLists, tables, caps=None):
+    """v2p_decode_groups + v2p_decode_groups_download alone: ((hap_group_begin, group_transcript, group_member_begin, member_ids) or None,
+    refused lists, info dict, error or None).  `tables` is a CsqTables or anything with its arrays.  Refused lists have no groups in the
+    CSR; an abort (error, V2P_ERR_DUPLICATE_POS) leaves no CSR."""
+    lib = _hip()
+    T = tables.n_transcripts
+    info = v2p_groups_info()
+    c = v2p_groups_caps(*caps) if caps is not None else None
+    ptr = lambda a: a.ctypes.data if a.size else None
+    rc = lib.v2p_decode_groups(ctx._h, resident._h, ptr(tables.rank), ptr(tables.flags), ptr(tables.mut_pos), ptr(tables.ref_pos),
+                               ptr(tables.ident), tables.extra_begin.ctypes.data, ptr(tables.extra), tables.n_consequences, T,
+                               tables._idx.text.ctypes.data, ptr(tables.transcript_begin), ptr(tables.transcript_len),
+                               ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    err = None
+    if rc == V2P_ERR_DUPLICATE_POS:
+        err = N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    elif rc != 0:
+        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    refused = np.zeros(int(info.n_refused), np.uint64)
+    lib.v2p_decode_groups_refused(resident._h, ptr(refused))
+    csr = None
+    if err is None:
+        csr = (np.zeros(resident.n_haplotypes + 1, np.uint64), np.zeros(int(info.n_groups), np.uint32),
+               np.zeros(int(info.n_groups) + 1, np.uint64), np.zeros(int(info.n_members), np.uint32))
+        rc = lib.v2p_decode_groups_download(resident._h, csr[0].ctypes.data, ptr(csr[1]), csr[2].ctypes.data, ptr(csr[3]))
+        if rc != 0:
+            raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    t = [c_float() for _ in range(5)]
+    lib.v2p_decode_groups_timing(resident._h, *[ctypes.byref(x) for x in t])
+    inf = {k: int(getattr(info, k)) for k, _ in v2p_groups_info._fields_}
+    inf["timing_ms"] = dict(zip(("upload", "count", "scan", "emit", "download"), (x.value for x in t)))
+    return csr, refused.astype(np.int64).tolist(), inf, err
+
+
+def device_groups(ctx, idx: VcfIndex, resident: ResidentLists, tables: "CsqTables", caps=None, n_threads: int = 0) -> Groups:
+    """group_per_transcript with the CSR made on the GPU from the resident lists (v2p_decode_groups): the ids stay on the device.  If the
+    kernel refuses a list the ids are downloaded and the WHOLE file is grouped on the host from the same tables (Groups.from_tables).
+    The result's .path says "device" or "host", .info what was launched.  Raises V2PError(V2P_ERR_DUPLICATE_POS) with the smallest
+    aborting haplotype list where the reference panics."""
+    assert tables._idx is idx
+    csr, refused, info, err = device_groups_csr(ctx, resident, tables, caps)
+    if refused:
+        g = Groups.from_tables(tables, resident.download(), n_threads)
+    elif err is not None:
+        raise err
+    else:
+        g = Groups.from_csr(tables, *csr)
+    g.path, g.info = ("host" if refused else "device"), info
+    return g
 
 
 class CohortStats:

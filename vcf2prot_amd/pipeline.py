@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _native as N
 from . import step4a
-from .frontend import VcfIndex, decode_bitmasks, group_per_transcript, inflate_bgzf, input_format
+from .frontend import CsqTables, Groups, VcfIndex, decode_resident, device_groups, inflate_bgzf, input_format
 from .step4b import inspect_transcript_tasks, transcript_g_rep
 
 
@@ -77,7 +77,8 @@ def _proband_bytes(b, k: int, bgzf: bool) -> bytes:
 
 
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
-                 device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False) -> Dict[str, bytes]:
+                 device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False, host_groups: bool = False,
+                 groups_caps=None, report: dict = None) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
@@ -87,7 +88,10 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     bgzf: {proband: text of <proband>.fasta.gz} instead -- BGZF compressed on the device (bgzf.py): haplotype 1's members, haplotype 2's
     members, then the EOF block.
     vcf may be the bytes of a .vcf.gz: BGZF is inflated on the device and its text stays there for the decode (frontend.inflate_bgzf);
-    any other gzip is inflated here."""
+    any other gzip is inflated here.
+    The consequences are grouped per transcript on the GPU from the lists the decode left there (frontend.device_groups); if the kernel
+    refuses a list, or with host_groups, the ids are downloaded and the whole file is grouped on the host from the same tables -- same
+    bytes.  groups_caps: the kernel's sizes (tests); report: a dict that receives {"groups": {"path": "device" | "host", ...}}."""
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
     fmt, inflated = input_format(vcf), None
@@ -102,8 +106,21 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         if inflated is not None:
             inflated.close()
         raise
-    lists = decode_bitmasks(ctx, idx, inflated)
-    groups = group_per_transcript(idx, lists)
+    resident = decode_resident(ctx, idx, inflated)
+    try:
+        n_haplotypes = resident.n_haplotypes
+        tables = CsqTables(idx)
+        try:
+            if host_groups:
+                groups = Groups.from_tables(tables, resident.download())
+            else:
+                groups = device_groups(ctx, idx, resident, tables, groups_caps)
+        finally:
+            tables.close()
+    finally:
+        resident.close()
+    if report is not None:
+        report["groups"] = dict(groups.info or {}, path=groups.path)
     names = [groups.transcript_name(r) for r in range(groups.n_transcripts)]
     if write_all:
         names = sorted(set(names) | set(ref), key=lambda x: x.encode())
@@ -175,7 +192,7 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         sink = TxStreamBuilder(fasta=True)
 
     try:
-        for hap in range(lists.n_haplotypes):
+        for hap in range(n_haplotypes):
             if not device_build:
                 b.begin_haplotype()
             altered = dict(groups.of(hap))
@@ -213,7 +230,7 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
                 sink.add_transcript(t[:, 0].astype(np.uint8), t[:, 1], t[:, 2], t[:, 3], off[tx], len(ref[tx]),
                                     np.frombuffer(alt, dtype=np.uint8), res_len, ho, hl)
             sink.end_haplotype()
-            if device_build and hap % 2 == 1 and (sink.result_bytes() >= slice_bytes or hap + 1 == lists.n_haplotypes):
+            if device_build and hap % 2 == 1 and (sink.result_bytes() >= slice_bytes or hap + 1 == n_haplotypes):
                 flush(hap // 2 + 1)                                    # a proband is complete; the slice is full (or the last one)
         if device_build:
             while inflight:
