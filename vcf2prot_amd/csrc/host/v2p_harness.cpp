@@ -434,6 +434,12 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     if (v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
     const uint64_t T = v2p_csq_tables_n_transcripts(tb);
     const double t_tables = since(tt);
+    // (the leading arguments v2p_decode_stats and v2p_decode_groups share -- the decode, the tables, the transcript names -- then each call's own)
+    auto with_tables = [&](auto fn, auto... own) {
+        return fn(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
+                  v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
+                  text, v2p_csq_tables_transcript_begin(tb), v2p_csq_tables_transcript_len(tb), own...);
+    };
     // -s / --stats (main.rs:39-45): the three tables counted on the device from the lists the decode left there
     double t_stats = 0;
     float sms[2] = {0, 0};
@@ -443,10 +449,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     if (stats) {
         const auto ts = clk::now();
         st_proband.assign(S, 0); st_type.assign(22 * S, 0); st_tx.assign(T + 1, 0);
-        const int rc = v2p_decode_stats(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
-                                        v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
-                                        text, v2p_csq_tables_transcript_begin(tb), v2p_csq_tables_transcript_len(tb),
-                                        st_proband.data(), st_type.data(), st_tx.data(), nullptr, &sinfo);
+        const int rc = with_tables(v2p_decode_stats, st_proband.data(), st_type.data(), st_tx.data(), nullptr, &sinfo);
         // (a refused list is completed from the grouping below, which reports its abort if it has one)
         if (rc != V2P_OK && !(rc == V2P_ERR_DUPLICATE_POS && sinfo.n_refused)) {
             std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw()));
@@ -475,9 +478,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     float gms[5] = {0, 0, 0, 0, 0};
     bool device_groups = !host_groups;
     if (device_groups) {
-        const int rc = v2p_decode_groups(ctx.raw(), dec, v2p_csq_tables_rank(tb), v2p_csq_tables_flags(tb), v2p_csq_tables_mut_pos(tb), v2p_csq_tables_ref_pos(tb),
-                                         v2p_csq_tables_ident(tb), v2p_csq_tables_extra_begin(tb), v2p_csq_tables_extra(tb), v2p_csq_tables_n_consequences(tb), T,
-                                         text, v2p_csq_tables_transcript_begin(tb), v2p_csq_tables_transcript_len(tb), &gcaps, &ginfo);
+        const int rc = with_tables(v2p_decode_groups, &gcaps, &ginfo);
         if (rc != V2P_OK && !(rc == V2P_ERR_DUPLICATE_POS && ginfo.n_refused)) {      // (with refused lists the host path reports the smallest aborting list)
             std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw()));
             v2p_csq_tables_destroy(tb);

@@ -38,15 +38,6 @@ namespace {
 
 thread_local std::string g_init_error;
 
-// V2P_DEBUG_POISON=1 (a debugging aid like the reference's DEBUG_* switches; read once): every device buffer is filled with 0xA5 whenever a
-// call (re)sizes it -- also when the allocation is reused -- so that nothing can lean on what fresh or recycled memory happens to hold
-// (tools/fuzz_*.py and the GPU suite run clean under it; one bug of that kind was found without it)
-static bool debug_poison()
-{
-    static const bool on = [] { const char* e = getenv("V2P_DEBUG_POISON"); return e && e[0] == '1'; }();
-    return on;
-}
-
 struct DevBuf {
     uint8_t* base = nullptr;
     size_t cap = 0;

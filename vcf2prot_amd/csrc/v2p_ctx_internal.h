@@ -1,7 +1,9 @@
-// v2p_ctx_internal.h -- what other translation units of libvcf2prot_hip.so may do with a v2p_ctx (defined in v2p_api.hip).
+// v2p_ctx_internal.h -- what other translation units of libvcf2prot_hip.so may do with a v2p_ctx (defined in v2p_api.hip), and the
+// owners of device memory and events they share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <string>
 
 struct v2p_ctx;
@@ -12,4 +14,48 @@ int ctx_device(v2p_ctx* c);
 int ctx_fail(v2p_ctx* c, int code, const std::string& msg, int64_t index);
 void ctx_lock(v2p_ctx* c);
 void ctx_unlock(v2p_ctx* c);
+
+// V2P_DEBUG_POISON=1 (a debugging aid like the reference's DEBUG_* switches; read once): every device buffer is filled with 0xA5 whenever a
+// call (re)sizes it -- also when the allocation is reused -- so that nothing can lean on what fresh or recycled memory happens to hold
+// (tools/fuzz_*.py and the GPU suite run clean under it; one bug of that kind was found without it)
+inline bool debug_poison()
+{
+    static const bool on = [] { const char* e = getenv("V2P_DEBUG_POISON"); return e && e[0] == '1'; }();
+    return on;
+}
+
+// One device allocation and its owner.  alloc(n) is a hipMalloc of exactly n bytes -- no slack, nothing kept for reuse -- poisoned under
+// debug_poison(); whatever the owner held before is freed first.
+class DevMem {
+    void* p_ = nullptr;
+public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DevMem() { reset(); }
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc(&p_, n);
+        if (e != hipSuccess) p_ = nullptr;
+        else if (debug_poison() && n) { (void)hipDeviceSynchronize(); (void)hipMemset(p_, 0xA5, n); (void)hipDeviceSynchronize(); }
+        return e;
+    }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    template <class T> T* get() const { return static_cast<T*>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
+// N events, created by create() and destroyed with their owner
+template <int N> class Events {
+    hipEvent_t e_[N] = {};
+public:
+    Events() = default;
+    Events(const Events&) = delete;
+    ~Events() { for (hipEvent_t x : e_) if (x) (void)hipEventDestroy(x); }
+    hipError_t create() {
+        for (hipEvent_t& x : e_) if (!x) { const hipError_t e = hipEventCreate(&x); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return e_[k]; }
+};
 }  // namespace v2p

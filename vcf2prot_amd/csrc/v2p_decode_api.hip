@@ -3,8 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -19,88 +20,53 @@
 
 using namespace v2p;
 
-struct v2p_decode {
-    v2p_ctx* ctx = nullptr;
-    uint64_t n_samples = 0, n_records = 0, n_ids = 0;
-    uint64_t n_text = 0;              // text bytes (v2p_decode_inflate)
-    uint8_t* d_text = nullptr;        // [256 pad | text | 256 pad]
-    uint64_t* d_rows = nullptr;       // row_begin | row_end
-    uint32_t* d_csq = nullptr;        // csq_begin | sup_pairs | sup_bits
-    uint8_t* d_work = nullptr;
-    uint64_t* d_hap_begin = nullptr;
-    uint32_t* d_ids = nullptr;
-    uint64_t* d_status = nullptr;
-    std::vector<uint64_t> hap_begin;
-    float ms[4] = {0, 0, 0, 0};
-    float ms_inflate[3] = {0, 0, 0};  // upload of the members, inflate kernel, text to the host
-    float ms_stats[2] = {0, 0};       // v2p_decode_stats: upload of the tables, kernel
-    std::vector<uint64_t> refused;    // lists the last v2p_decode_stats refused
-    // the file-wide tables of v2p_decode_stats / v2p_decode_groups on the device, kept while the next call brings the same ones
-    std::vector<StatsRec> tab_rec;
-    std::vector<uint32_t> tab_extra_begin, tab_extra;
-    StatsRec* d_tab_rec = nullptr;
-    uint32_t* d_tab_extra_begin = nullptr;
-    uint32_t* d_tab_extra = nullptr;
-    // v2p_decode_groups: the grouped CSR on the device until the next call
-    uint64_t* d_hap_group_begin = nullptr;    // [n_haps + 1], then the member bases [n_haps + 1]
-    uint32_t* d_group_transcript = nullptr;
-    uint64_t* d_group_member_begin = nullptr;
-    uint32_t* d_member_ids = nullptr;
-    uint64_t n_groups = 0, n_members = 0;
-    bool groups_ok = false;
-    float ms_groups[5] = {0, 0, 0, 0, 0};     // upload of the tables, count, scan, emit, download
-    std::vector<uint64_t> groups_refused;
-    void release_groups() {
-        for (void* p : {(void*)d_hap_group_begin, (void*)d_group_transcript, (void*)d_group_member_begin, (void*)d_member_ids})
-            if (p) (void)hipFree(p);
-        d_hap_group_begin = nullptr; d_group_transcript = nullptr; d_group_member_begin = nullptr; d_member_ids = nullptr;
-        n_groups = n_members = 0; groups_ok = false;
-    }
-    void release_tables() {
-        for (void* p : {(void*)d_tab_rec, (void*)d_tab_extra_begin, (void*)d_tab_extra}) if (p) (void)hipFree(p);
-        d_tab_rec = nullptr; d_tab_extra_begin = nullptr; d_tab_extra = nullptr;
-        tab_rec.clear(); tab_extra_begin.clear(); tab_extra.clear();
-    }
-    void release_lists() {
-        for (void* p : {(void*)d_rows, (void*)d_csq, (void*)d_work, (void*)d_hap_begin, (void*)d_ids, (void*)d_status})
-            if (p) (void)hipFree(p);
-        d_rows = nullptr; d_csq = nullptr; d_work = nullptr; d_hap_begin = nullptr; d_ids = nullptr; d_status = nullptr;
-        n_ids = 0;
-        release_groups();
-    }
-    void release() {
-        release_lists();
-        release_tables();
-        if (d_text) (void)hipFree(d_text);
-        d_text = nullptr;
-    }
-};
-
+// The handle's members are grouped by lifetime: the text lives until the destroy, the lists from one decode run to the next, the groups
+// from one v2p_decode_groups to the next or to the end of their lists, the tables until other tables come.
 namespace {
 
-int reason_to_code(uint32_t r)
-{
-    switch (r) {
-        case DEC_MASK_NEGATIVE: return V2P_ERR_MASK_NEGATIVE;
-        case DEC_MASK_PARSE: return V2P_ERR_MASK_PARSE;
-        case DEC_MASK_INDEX: return V2P_ERR_MASK_INDEX;
-        case DEC_COLUMNS: return V2P_ERR_COLUMNS;
-        case DEC_FIELD_TOO_LONG: return V2P_ERR_FIELD_TOO_LONG;
-        case DEC_CAPACITY: return V2P_ERR_CAPACITY;
-        default: return V2P_ERR_INVALID_ARG;
-    }
-}
+struct Lists {
+    DevMem rows, csq;                 // row_begin | row_end; csq_begin | sup_pairs | sup_bits
+    DevMem work, hap_begin, ids, status;
+    uint64_t n_ids = 0;
+    std::vector<uint64_t> host_hap_begin;
+    float ms[4] = {0, 0, 0, 0};
+};
 
-const char* reason_text(uint32_t r)
+// the file-wide tables of v2p_decode_stats / v2p_decode_groups on the device, kept while the next call brings the same ones
+struct Tables {
+    DevMem rec, extra_begin, extra;
+    std::vector<StatsRec> host_rec;
+    std::vector<uint32_t> host_extra_begin, host_extra;
+};
+
+struct Stats {                        // what the last v2p_decode_stats left for its accessors
+    float ms[2] = {0, 0};             // upload of the tables, kernel
+    std::vector<uint64_t> refused;
+};
+
+// v2p_decode_groups: the grouped CSR on the device until the next call
+struct Groups {
+    DevMem hap_group_begin;           // [n_haps + 1], then the member bases [n_haps + 1]
+    DevMem group_transcript, group_member_begin, member_ids;
+    uint64_t n_groups = 0, n_members = 0;
+    bool ok = false;
+    float ms[5] = {0, 0, 0, 0, 0};    // upload of the tables, count, scan, emit, download
+    std::vector<uint64_t> refused;
+};
+
+// a status word's reason (decode_kernels.h) as the ABI's error code and the reference's words
+struct Reason { int code; const char* text; };
+
+Reason reason_of(uint32_t r)
 {
     switch (r) {
-        case DEC_MASK_NEGATIVE: return "An invalid bit mask was encountered (negative; text_parser.rs:210,244)";
-        case DEC_MASK_PARSE: return "bit mask word is not a u32 (MaskDecoder.rs:41,47)";
-        case DEC_MASK_INDEX: return "bit mask selects a consequence the record does not have (vcf_ds.rs:321)";
-        case DEC_COLUMNS: return "record does not have one column per proband (vcf_ds.rs:148)";
-        case DEC_FIELD_TOO_LONG: return "sample column longer than the 4 KiB window after its last ':'";
-        case DEC_CAPACITY: return "multi-word / id capacity exceeded";
-        default: return "decode error";
+        case DEC_MASK_NEGATIVE: return {V2P_ERR_MASK_NEGATIVE, "An invalid bit mask was encountered (negative; text_parser.rs:210,244)"};
+        case DEC_MASK_PARSE: return {V2P_ERR_MASK_PARSE, "bit mask word is not a u32 (MaskDecoder.rs:41,47)"};
+        case DEC_MASK_INDEX: return {V2P_ERR_MASK_INDEX, "bit mask selects a consequence the record does not have (vcf_ds.rs:321)"};
+        case DEC_COLUMNS: return {V2P_ERR_COLUMNS, "record does not have one column per proband (vcf_ds.rs:148)"};
+        case DEC_FIELD_TOO_LONG: return {V2P_ERR_FIELD_TOO_LONG, "sample column longer than the 4 KiB window after its last ':'"};
+        case DEC_CAPACITY: return {V2P_ERR_CAPACITY, "multi-word / id capacity exceeded"};
+        default: return {V2P_ERR_INVALID_ARG, "decode error"};
     }
 }
 
@@ -137,20 +103,40 @@ bool sizes_ok(uint64_t n_records, uint64_t n_samples, uint64_t ovf_words)
     return n_records >= 1 && n_samples >= 1 && n_records < (1ull << 31) && n_samples < (1ull << 30) && ovf_words < (1ull << 31);
 }
 
+uint64_t pow2_floor(uint64_t v) { uint64_t p = 1; while (p * 2 <= v) p *= 2; return p; }
+uint64_t pow2_ceil(uint64_t v) { uint64_t p = 1; while (p < v) p *= 2; return p; }
+
+// what the accessors copy out: milliseconds into the pointers that are not null, the indices of refused lists
+int give_ms(const float* ms, std::initializer_list<float*> out)
+{
+    for (float* p : out) { if (p) *p = *ms; ++ms; }
+    return V2P_OK;
+}
+
+int give_refused(const std::vector<uint64_t>& refused, uint64_t* lists)
+{
+    if (!lists && !refused.empty()) return V2P_ERR_INVALID_ARG;
+    if (!refused.empty()) memcpy(lists, refused.data(), refused.size() * sizeof(uint64_t));
+    return V2P_OK;
+}
+
 }  // namespace
 
-#define DTRY(expr, what) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { d->release(); delete d; \
-    return ctx_fail(ctx, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__), -1); } } while (0)
+struct v2p_decode {
+    v2p_ctx* ctx = nullptr;
+    uint64_t n_samples = 0, n_records = 0;
+    uint64_t n_text = 0;              // text bytes (v2p_decode_inflate)
+    DevMem text;                      // [256 pad | text | 256 pad]
+    float ms_inflate[3] = {0, 0, 0};  // upload of the members, inflate kernel, text to the host
+    Lists lists;
+    Tables tables;
+    Stats stats;
+    Groups groups;
+    void drop_lists() { lists = Lists{}; groups = Groups{}; }     // (the tables and the text stay)
+};
 
-// hipMalloc, and under V2P_DEBUG_POISON=1 (vcf2prot_hip.h: a debugging switch) the allocation filled with 0xA5: no result may depend on
-// what fresh or recycled device memory held
-static hipError_t dmalloc(void** p, size_t n)
-{
-    static const bool poison = [] { const char* e = getenv("V2P_DEBUG_POISON"); return e && e[0] == '1'; }();
-    const hipError_t e = hipMalloc(p, n);
-    if (e == hipSuccess && poison && n) { (void)hipDeviceSynchronize(); (void)hipMemset(*p, 0xA5, n); (void)hipDeviceSynchronize(); }
-    return e;
-}
+#define TRY(expr, what) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
+    return ctx_fail(ctx, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__), -1); } while (0)
 
 // argument checks of the decode calls: sizes, record ranges inside the text, ascending consequence offsets
 static int check_rows(v2p_ctx* ctx, const char* fn, uint64_t n_text, const uint64_t* row_begin, const uint64_t* row_end, uint64_t n_records,
@@ -165,11 +151,8 @@ static int check_rows(v2p_ctx* ctx, const char* fn, uint64_t n_text, const uint6
     return V2P_OK;
 }
 
-#define RTRY(expr, what) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
-    return ctx_fail(ctx, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__), -1); } while (0)
-
-// the lists of d's resident text (d->d_text + 256, d->n_text bytes): rows and consequence tables uploaded, the four kernels, the counts
-// back.  On failure the caller frees what d holds.
+// the lists of d's resident text (d->text + 256, d->n_text bytes): rows and consequence tables uploaded, the four kernels, the counts
+// back.  On failure the caller drops the lists.
 static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begin, const uint64_t* row_end, uint64_t n_records,
                            uint64_t n_samples, const uint32_t* csq_begin, const uint8_t* csq_supported)
 {
@@ -188,25 +171,24 @@ static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begi
     }
 
     hipStream_t st = ctx_stream(ctx);
-    d->release_lists();
+    d->drop_lists();
+    Lists& ls = d->lists;
     d->n_samples = n_samples; d->n_records = n_records;
     const uint64_t n_haps = 2 * n_samples;
     const uint64_t n_text = d->n_text;
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_rows), 2 * n_records * sizeof(uint64_t)), "hipMalloc(rows)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_csq), csq.size() * sizeof(uint32_t)), "hipMalloc(csq)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_hap_begin), (n_haps + 1) * sizeof(uint64_t)), "hipMalloc(hap_begin)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_status), 2 * sizeof(uint64_t)), "hipMalloc(status)");
-    uint8_t* d_text = d->d_text + 256;
-    RTRY(hipMemcpyAsync(d->d_rows, row_begin, n_records * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(row_begin)");
-    RTRY(hipMemcpyAsync(d->d_rows + n_records, row_end, n_records * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(row_end)");
-    RTRY(hipMemcpyAsync(d->d_csq, csq.data(), csq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(csq)");
+    TRY(ls.rows.alloc(2 * n_records * sizeof(uint64_t)), "hipMalloc(rows)");
+    TRY(ls.csq.alloc(csq.size() * sizeof(uint32_t)), "hipMalloc(csq)");
+    TRY(ls.hap_begin.alloc((n_haps + 1) * sizeof(uint64_t)), "hipMalloc(hap_begin)");
+    TRY(ls.status.alloc(2 * sizeof(uint64_t)), "hipMalloc(status)");
+    uint8_t* d_text = d->text.get<uint8_t>() + 256;
+    uint64_t *d_rows = ls.rows.get<uint64_t>(), *d_status = ls.status.get<uint64_t>();
+    uint32_t* d_csq = ls.csq.get<uint32_t>();
+    TRY(hipMemcpyAsync(d_rows, row_begin, n_records * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(row_begin)");
+    TRY(hipMemcpyAsync(d_rows + n_records, row_end, n_records * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(row_end)");
+    TRY(hipMemcpyAsync(d_csq, csq.data(), csq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(csq)");
 
-    struct Events {                                     // destroyed on every exit path
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } evs;
-    hipEvent_t* ev = evs.e;
-    for (int k = 0; k < 5; ++k) RTRY(hipEventCreate(&ev[k]), "hipEventCreate");
+    Events<5> ev;
+    TRY(ev.create(), "hipEventCreate");
     // multi-word masks are rare; start with room for one field in 16 and retry with the exact need if that was short
     uint64_t ovf_words = n_records * n_samples / 4 + (1u << 16);
     if (ovf_words >= (1ull << 31)) ovf_words = (1ull << 31) - 1;
@@ -218,100 +200,143 @@ static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begi
     bool done = false;                                  // set only after the emit pass: a retry that runs out of attempts is an error
     std::string last_reason = "decode: retries exhausted";
     for (int attempt = 0; attempt < 4 && !done; ++attempt) {
-        if (d->d_work) { (void)hipFree(d->d_work); d->d_work = nullptr; }
         const DecodeLayout L = decode_layout(n_records, n_samples, ovf_words);
-        RTRY(dmalloc(reinterpret_cast<void**>(&d->d_work), L.total), "hipMalloc(decode workspace)");
-        RTRY(hipMemsetAsync(d->d_status, 0xFF, sizeof(uint64_t), st), "hipMemset(status)");
+        TRY(ls.work.alloc(L.total), "hipMalloc(decode workspace)");
+        TRY(hipMemsetAsync(d_status, 0xFF, sizeof(uint64_t), st), "hipMemset(status)");
         DecodeArgs a{};
-        fill_args(a, d_text, n_text, d->d_rows, d->d_rows + n_records, n_records, n_samples, d->d_csq, d->d_csq + n_records + 1,
-                  d->d_csq + 2 * n_records + 1, d->d_work, ovf_words, d->d_hap_begin, nullptr, ~0ull, d->d_status);
+        fill_args(a, d_text, n_text, d_rows, d_rows + n_records, n_records, n_samples, d_csq, d_csq + n_records + 1,
+                  d_csq + 2 * n_records + 1, ls.work.get<uint8_t>(), ovf_words, ls.hap_begin.get<uint64_t>(), nullptr, ~0ull, d_status);
         a.parse_threads = parse_threads;
-        RTRY(hipEventRecord(ev[0], st), "hipEventRecord");
-        RTRY(launch_decode(a, st, 1u), "parse_rows_kernel");
-        RTRY(hipEventRecord(ev[1], st), "hipEventRecord");
-        RTRY(launch_decode(a, st, 2u), "count_kernel");
-        RTRY(hipEventRecord(ev[2], st), "hipEventRecord");
-        RTRY(launch_decode(a, st, 4u), "scan kernels");
-        RTRY(hipEventRecord(ev[3], st), "hipEventRecord");
+        TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+        TRY(launch_decode(a, st, 1u), "parse_rows_kernel");
+        TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+        TRY(launch_decode(a, st, 2u), "count_kernel");
+        TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+        TRY(launch_decode(a, st, 4u), "scan kernels");
+        TRY(hipEventRecord(ev[3], st), "hipEventRecord");
         uint64_t status[2] = {~0ull, 0};
-        d->hap_begin.assign(n_haps + 1, 0);
-        RTRY(hipMemcpyAsync(status, d->d_status, sizeof(status), hipMemcpyDeviceToHost, st), "D2H(status)");
-        RTRY(hipMemcpyAsync(d->hap_begin.data(), d->d_hap_begin, (n_haps + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_begin)");
-        RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+        ls.host_hap_begin.assign(n_haps + 1, 0);
+        TRY(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st), "D2H(status)");
+        TRY(hipMemcpyAsync(ls.host_hap_begin.data(), ls.hap_begin.get<uint64_t>(), (n_haps + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_begin)");
+        TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (status[0] != ~0ull) {
             const uint32_t reason = uint32_t(status[0] & 0xFF);
-            last_reason = std::string("decode: ") + reason_text(reason) + " (after a retry)";
+            const Reason why = reason_of(reason);
+            last_reason = std::string("decode: ") + why.text + " (after a retry)";
             if (reason == DEC_CAPACITY && status[1] > ovf_words && status[1] < (1ull << 31)) { ovf_words = status[1]; continue; }
             if (reason == DEC_FIELD_TOO_LONG && parse_threads != 256u) { parse_threads = 256u; continue; }     // the narrow kernels look back 1-2 KiB only
-            rc = ctx_fail(ctx, reason_to_code(reason), std::string("decode: ") + reason_text(reason) + " at record " +
+            rc = ctx_fail(ctx, why.code, std::string("decode: ") + why.text + " at record " +
                           std::to_string((status[0] >> 8) / n_samples) + ", sample " + std::to_string((status[0] >> 8) % n_samples),
                           int64_t(status[0] >> 8));
             break;
         }
-        d->n_ids = d->hap_begin[n_haps];
-        RTRY(dmalloc(reinterpret_cast<void**>(&d->d_ids), (d->n_ids + 64) * sizeof(uint32_t)), "hipMalloc(ids)");
-        a.ids = d->d_ids; a.ids_capacity = d->n_ids;
-        RTRY(launch_decode(a, st, 8u), "emit_kernel");
-        RTRY(hipEventRecord(ev[4], st), "hipEventRecord");
-        RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-        for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&d->ms[k], ev[k], ev[k + 1]);
+        ls.n_ids = ls.host_hap_begin[n_haps];
+        TRY(ls.ids.alloc((ls.n_ids + 64) * sizeof(uint32_t)), "hipMalloc(ids)");
+        a.ids = ls.ids.get<uint32_t>(); a.ids_capacity = ls.n_ids;
+        TRY(launch_decode(a, st, 8u), "emit_kernel");
+        TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+        TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+        for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&ls.ms[k], ev[k], ev[k + 1]);
         done = true;
     }
     if (rc == V2P_OK && !done) rc = ctx_fail(ctx, V2P_ERR_UNSUPPORTED, last_reason, -1);     // never hand back a decode whose emit pass did not run
     return rc;
 }
 
-// the reference's words for an aborting list (low word of the kernels' status[0]: group_stats.h)
-static std::string abort_message(uint32_t why, uint64_t n_tx, const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len)
-{
-    if (why == STATS_ERR_POISON) return "start_lost consequence with fewer than three fields (text_parser.rs:52 would abort)";
-    if (why == STATS_ERR_RANGE) return "consequence id out of range";
-    const uint32_t r = why - 1;
-    return "Encountered a logical error with analyzing mutations in transcript: " +
-           (tx_text && tx_begin && tx_len && r < n_tx ? std::string(reinterpret_cast<const char*>(tx_text) + tx_begin[r], tx_len[r]) : "rank " + std::to_string(r));
-}
+// the seven file-wide table arrays of v2p_decode_stats / v2p_decode_groups and the transcript names, as the caller passed them
+struct TableArgs {
+    const uint32_t *rank, *flags; const uint16_t *mut_pos, *ref_pos; const uint32_t *ident, *extra_begin, *extra; uint64_t n_csq, n_tx;
+    const uint8_t* tx_text; const uint64_t* tx_begin; const uint32_t* tx_len;
+};
 
 // the checks v2p_decode_stats and v2p_decode_groups share on the seven table arrays, one 16-byte row per consequence id, and the rows
 // and the extra CSR on the device: uploaded unless d already holds exactly these tables (*uploaded says which)
-static int prepare_tables(v2p_ctx* ctx, v2p_decode* d, const char* fn, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos,
-                          const uint16_t* ref_pos, const uint32_t* ident, const uint32_t* extra_begin, const uint32_t* extra, uint64_t n_csq,
-                          uint64_t n_tx, hipStream_t st, bool* uploaded)
+static int prepare_tables(v2p_ctx* ctx, v2p_decode* d, const std::string& f, const TableArgs& t, hipStream_t st, bool* uploaded)
 {
-    const std::string f(fn);
+    const uint64_t n_csq = t.n_csq;
     *uploaded = false;
-    if (n_csq >= 0xffffffffull || n_tx > STATS_MAX_RANKS)
+    if (n_csq >= 0xffffffffull || t.n_tx > STATS_MAX_RANKS)
         return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts or 2^32 consequences", -1);
     std::vector<StatsRec> rec(n_csq + 1);
     for (uint64_t i = 0; i < n_csq; ++i) {
-        if (extra_begin[i + 1] < extra_begin[i] || extra_begin[i + 1] - extra_begin[i] > 0xffffu)
+        const uint32_t n_extra_i = t.extra_begin[i + 1] - t.extra_begin[i];
+        if (t.extra_begin[i + 1] < t.extra_begin[i] || n_extra_i > 0xffffu)
             return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": extra_begin must ascend by at most 65535 per consequence", int64_t(i));
-        if ((flags[i] & 1u) && ((flags[i] >> 8 & 0xffu) >= STATS_TYPES || rank[i] == ~0u))
+        if ((t.flags[i] & 1u) && ((t.flags[i] >> 8 & 0xffu) >= STATS_TYPES || t.rank[i] == ~0u))
             return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": a mut_ok consequence needs a type below 22 and a transcript", int64_t(i));
-        if (rank[i] != ~0u && rank[i] >= n_tx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": rank outside the transcripts", int64_t(i));
-        rec[i] = StatsRec{rank[i], (flags[i] & 0xffffu) | (extra_begin[i + 1] - extra_begin[i]) << 16, uint32_t(mut_pos[i]) | uint32_t(ref_pos[i]) << 16, ident[i]};
+        if (t.rank[i] != ~0u && t.rank[i] >= t.n_tx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": rank outside the transcripts", int64_t(i));
+        rec[i] = StatsRec{t.rank[i], (t.flags[i] & 0xffffu) | n_extra_i << 16, uint32_t(t.mut_pos[i]) | uint32_t(t.ref_pos[i]) << 16, t.ident[i]};
     }
     rec[n_csq] = StatsRec{~0u, 0u, 0u, ~0u};
-    const uint64_t n_extra = n_csq ? extra_begin[n_csq] : 0;
+    const uint64_t n_extra = n_csq ? t.extra_begin[n_csq] : 0;
     const uint32_t zero = 0;
-    const uint32_t* eb = n_csq ? extra_begin : &zero;
-    if (d->d_tab_rec && d->tab_rec.size() == rec.size() && d->tab_extra.size() == n_extra &&
-        !memcmp(d->tab_rec.data(), rec.data(), rec.size() * sizeof(StatsRec)) &&
-        !memcmp(d->tab_extra_begin.data(), eb, (n_csq + 1) * sizeof(uint32_t)) &&
-        (!n_extra || !memcmp(d->tab_extra.data(), extra, n_extra * sizeof(uint32_t))))
+    const uint32_t* eb = n_csq ? t.extra_begin : &zero;
+    Tables& tb = d->tables;
+    if (tb.rec && tb.host_rec.size() == rec.size() && tb.host_extra.size() == n_extra &&
+        !memcmp(tb.host_rec.data(), rec.data(), rec.size() * sizeof(StatsRec)) &&
+        !memcmp(tb.host_extra_begin.data(), eb, (n_csq + 1) * sizeof(uint32_t)) &&
+        (!n_extra || !memcmp(tb.host_extra.data(), t.extra, n_extra * sizeof(uint32_t))))
         return V2P_OK;
-    d->release_tables();
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_rec), rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_extra_begin), (n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_tab_extra), (n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
-    d->tab_rec.swap(rec);
-    d->tab_extra_begin.assign(eb, eb + n_csq + 1);
-    d->tab_extra.assign(extra, extra + n_extra);
+    tb = Tables{};
+    TRY(tb.rec.alloc(rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
+    TRY(tb.extra_begin.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
+    TRY(tb.extra.alloc((n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
+    tb.host_rec.swap(rec);
+    tb.host_extra_begin.assign(eb, eb + n_csq + 1);
+    tb.host_extra.assign(t.extra, t.extra + n_extra);
     // (the copies are made from the decode's own vectors: they outlive the stream's work)
-    RTRY(hipMemcpyAsync(d->d_tab_rec, d->tab_rec.data(), d->tab_rec.size() * sizeof(StatsRec), hipMemcpyHostToDevice, st), "H2D(stats rows)");
-    RTRY(hipMemcpyAsync(d->d_tab_extra_begin, d->tab_extra_begin.data(), (n_csq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra_begin)");
-    if (n_extra) RTRY(hipMemcpyAsync(d->d_tab_extra, d->tab_extra.data(), n_extra * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra)");
+    TRY(hipMemcpyAsync(tb.rec.get<void>(), tb.host_rec.data(), tb.host_rec.size() * sizeof(StatsRec), hipMemcpyHostToDevice, st), "H2D(stats rows)");
+    TRY(hipMemcpyAsync(tb.extra_begin.get<void>(), tb.host_extra_begin.data(), (n_csq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra_begin)");
+    if (n_extra) TRY(hipMemcpyAsync(tb.extra.get<void>(), tb.host_extra.data(), n_extra * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(extra)");
     *uploaded = true;
     return V2P_OK;
+}
+
+// How v2p_decode_stats (fn names it) and v2p_decode_groups begin: the decode holds lists, no needed pointer is null (args_ok: the
+// caller's own), the call's `results` (d->stats or d->groups) start afresh, and the tables are on the device between ev[0] and ev[1].
+struct ListCall { hipStream_t st; uint64_t n_haps, max_len; bool uploaded; };
+
+template <int N, class R>
+static int begin_list_call(v2p_ctx* ctx, v2p_decode* d, const char* fn, bool args_ok, const TableArgs& t, R v2p_decode::*results,
+                           Events<N>& ev, ListCall* c)
+{
+    const std::string f(fn);
+    if (!d || d->ctx != ctx || !d->lists.hap_begin || d->lists.host_hap_begin.empty())
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": needs a decode that holds lists (v2p_decode_run / v2p_decode_run_inflated)", -1);
+    if (!args_ok || (t.n_csq && (!t.rank || !t.flags || !t.mut_pos || !t.ref_pos || !t.ident || !t.extra_begin)) ||
+        (t.n_csq && t.extra_begin[t.n_csq] && !t.extra))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    c->st = ctx_stream(ctx);
+    c->n_haps = 2 * d->n_samples;
+    d->*results = R{};
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], c->st), "hipEventRecord");
+    const int rc = prepare_tables(ctx, d, f, t, c->st, &c->uploaded);
+    if (rc != V2P_OK) return rc;
+    TRY(hipEventRecord(ev[1], c->st), "hipEventRecord");
+    const std::vector<uint64_t>& hb = d->lists.host_hap_begin;
+    for (uint64_t h = 0; h < c->n_haps; ++h) c->max_len = std::max(c->max_len, hb[h + 1] - hb[h]);
+    return V2P_OK;
+}
+
+// ... and how they end, on the kernels' status words (group_stats.h): the lists the kernel refused (status[1] of them, flagged in
+// d_flags) into `refused`, then the reference's words for an aborting list (low word of status[0]) if there is one
+static int end_list_call(v2p_ctx* ctx, const ListCall& c, const uint64_t* status, const DevMem& d_flags, std::vector<uint64_t>& refused, const TableArgs& t)
+{
+    if (status[1]) {
+        std::vector<uint32_t> fl(c.n_haps);
+        TRY(hipMemcpy(fl.data(), d_flags.get<void>(), c.n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
+        for (uint64_t h = 0; h < c.n_haps; ++h) if (fl[h]) refused.push_back(h);
+    }
+    if (status[0] == ~0ull) return V2P_OK;
+    const uint32_t why = uint32_t(status[0]), r = why - 1;
+    const std::string msg =
+        why == STATS_ERR_POISON ? "start_lost consequence with fewer than three fields (text_parser.rs:52 would abort)" :
+        why == STATS_ERR_RANGE ? "consequence id out of range" :
+        "Encountered a logical error with analyzing mutations in transcript: " +
+        (t.tx_text && t.tx_begin && t.tx_len && r < t.n_tx ? std::string(reinterpret_cast<const char*>(t.tx_text) + t.tx_begin[r], t.tx_len[r]) : "rank " + std::to_string(r));
+    return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, msg, int64_t(status[0] >> 32));
 }
 
 extern "C" {
@@ -336,6 +361,7 @@ int v2p_decode_launch(void* hip_stream, const uint8_t* d_text, uint64_t n_text,
     return launch_decode(a, reinterpret_cast<hipStream_t>(hip_stream), phases) == hipSuccess ? V2P_OK : V2P_ERR_HIP;
 }
 
+// (in the two calls that make a handle the Guard is declared before it: the handle of a failed call is freed with the context still locked)
 int v2p_decode_run(v2p_ctx* ctx, const uint8_t* text, uint64_t n_text,
                    const uint64_t* row_begin, const uint64_t* row_end, uint64_t n_records, uint64_t n_samples,
                    const uint32_t* csq_begin, const uint8_t* csq_supported, v2p_decode** out)
@@ -349,14 +375,14 @@ int v2p_decode_run(v2p_ctx* ctx, const uint8_t* text, uint64_t n_text,
     if (vrc != V2P_OK) return vrc;
     (void)hipSetDevice(ctx_device(ctx));
     hipStream_t st = ctx_stream(ctx);
-    v2p_decode* d = new (std::nothrow) v2p_decode();
+    std::unique_ptr<v2p_decode> d(new (std::nothrow) v2p_decode());
     if (!d) return ctx_fail(ctx, V2P_ERR_HIP, "out of host memory", -1);
     d->ctx = ctx; d->n_text = n_text;
-    DTRY(dmalloc(reinterpret_cast<void**>(&d->d_text), n_text + 512), "hipMalloc(text)");
-    DTRY(hipMemcpyAsync(d->d_text + 256, text, n_text, hipMemcpyHostToDevice, st), "H2D(text)");
-    const int rc = decode_resident(ctx, d, row_begin, row_end, n_records, n_samples, csq_begin, csq_supported);
-    if (rc != V2P_OK) { d->release(); delete d; return rc; }
-    *out = d;
+    TRY(d->text.alloc(n_text + 512), "hipMalloc(text)");
+    TRY(hipMemcpyAsync(d->text.get<uint8_t>() + 256, text, n_text, hipMemcpyHostToDevice, st), "H2D(text)");
+    const int rc = decode_resident(ctx, d.get(), row_begin, row_end, n_records, n_samples, csq_begin, csq_supported);
+    if (rc != V2P_OK) return rc;
+    *out = d.release();
     return V2P_OK;
 }
 
@@ -365,13 +391,13 @@ int v2p_decode_run_inflated(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_beg
 {
     if (!ctx) return V2P_ERR_INVALID_ARG;
     Guard g(ctx);
-    if (!d || !d->d_text || d->ctx != ctx || !row_begin || !row_end || !csq_begin || !csq_supported)
+    if (!d || !d->text || d->ctx != ctx || !row_begin || !row_end || !csq_begin || !csq_supported)
         return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_run_inflated: null argument or a decode without inflated text", -1);
     const int vrc = check_rows(ctx, "v2p_decode_run_inflated", d->n_text, row_begin, row_end, n_records, n_samples, csq_begin);
     if (vrc != V2P_OK) return vrc;
     (void)hipSetDevice(ctx_device(ctx));
     const int rc = decode_resident(ctx, d, row_begin, row_end, n_records, n_samples, csq_begin, csq_supported);
-    if (rc != V2P_OK) d->release_lists();
+    if (rc != V2P_OK) d->drop_lists();
     return rc;
 }
 
@@ -394,64 +420,58 @@ int v2p_decode_inflate(v2p_ctx* ctx, const uint8_t* gz, uint64_t n_gz, const uin
     for (uint64_t m = 0; m <= n_members; ++m) { offs[m] = member_begin[m]; offs[n_members + 1 + m] = out_begin[m] - out_begin[0]; }
     (void)hipSetDevice(ctx_device(ctx));
     hipStream_t st = ctx_stream(ctx);
-    v2p_decode* d = new (std::nothrow) v2p_decode();
+    std::unique_ptr<v2p_decode> d(new (std::nothrow) v2p_decode());
     if (!d) return ctx_fail(ctx, V2P_ERR_HIP, "out of host memory", -1);
     d->ctx = ctx; d->n_text = n_text;
-    struct Temp {                                       // the members, their offsets and statuses: freed on every exit path
-        uint8_t* gz = nullptr; uint64_t* offs = nullptr; uint32_t* status = nullptr;
-        ~Temp() { for (void* p : {(void*)gz, (void*)offs, (void*)status}) if (p) (void)hipFree(p); }
-    } tmp;
-    struct Events {
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } evs;
-    hipEvent_t* ev = evs.e;
-    for (int k = 0; k < 4; ++k) DTRY(hipEventCreate(&ev[k]), "hipEventCreate");
-    DTRY(dmalloc(reinterpret_cast<void**>(&d->d_text), n_text + 512), "hipMalloc(text)");
-    DTRY(dmalloc(reinterpret_cast<void**>(&tmp.gz), n_gz + 1), "hipMalloc(members)");
-    DTRY(dmalloc(reinterpret_cast<void**>(&tmp.offs), offs.size() * sizeof(uint64_t)), "hipMalloc(member offsets)");
-    DTRY(dmalloc(reinterpret_cast<void**>(&tmp.status), (n_members + 1) * sizeof(uint32_t)), "hipMalloc(member status)");
-    DTRY(hipEventRecord(ev[0], st), "hipEventRecord");
-    if (n_gz) DTRY(hipMemcpyAsync(tmp.gz, gz, n_gz, hipMemcpyHostToDevice, st), "H2D(members)");
-    DTRY(hipMemcpyAsync(tmp.offs, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(member offsets)");
-    DTRY(hipEventRecord(ev[1], st), "hipEventRecord");
-    if (v2p_bgzf_inflate_launch(st, tmp.gz, tmp.offs, tmp.offs + n_members + 1, n_members, d->d_text + 256, tmp.status) != V2P_OK)
-        DTRY(hipGetLastError() == hipSuccess ? hipErrorLaunchFailure : hipGetLastError(), "bgzf_inflate_kernel");
-    DTRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    DevMem d_gz, d_offs, d_member_status;               // the members, their offsets and statuses: freed on every exit path
+    Events<4> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(d->text.alloc(n_text + 512), "hipMalloc(text)");
+    TRY(d_gz.alloc(n_gz + 1), "hipMalloc(members)");
+    TRY(d_offs.alloc(offs.size() * sizeof(uint64_t)), "hipMalloc(member offsets)");
+    TRY(d_member_status.alloc((n_members + 1) * sizeof(uint32_t)), "hipMalloc(member status)");
+    uint8_t* d_text = d->text.get<uint8_t>() + 256;
+    uint64_t* p_offs = d_offs.get<uint64_t>(); uint32_t* p_status = d_member_status.get<uint32_t>();
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    if (n_gz) TRY(hipMemcpyAsync(d_gz.get<void>(), gz, n_gz, hipMemcpyHostToDevice, st), "H2D(members)");
+    TRY(hipMemcpyAsync(p_offs, offs.data(), offs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(member offsets)");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    if (v2p_bgzf_inflate_launch(st, d_gz.get<uint8_t>(), p_offs, p_offs + n_members + 1, n_members, d_text, p_status) != V2P_OK)
+        TRY(hipGetLastError() == hipSuccess ? hipErrorLaunchFailure : hipGetLastError(), "bgzf_inflate_kernel");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
     uint32_t first = ~0u;
-    DTRY(hipMemcpyAsync(&first, tmp.status + n_members, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(member status)");
-    DTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    TRY(hipMemcpyAsync(&first, p_status + n_members, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(member status)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (first != ~0u) {
         uint32_t reason = 0;
-        DTRY(hipMemcpy(&reason, tmp.status + first, sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(member status)");
-        d->release(); delete d;
+        TRY(hipMemcpy(&reason, p_status + first, sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(member status)");
         return ctx_fail(ctx, V2P_ERR_GZIP, "corrupt BGZF member " + std::to_string(first) + " at byte " + std::to_string(member_begin[first]) +
                         ": " + infl::reason_text(reason), int64_t(first));
     }
-    if (n_text) DTRY(hipMemcpyAsync(text_out, d->d_text + 256, n_text, hipMemcpyDeviceToHost, st), "D2H(text)");
-    DTRY(hipEventRecord(ev[3], st), "hipEventRecord");
-    DTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (n_text) TRY(hipMemcpyAsync(text_out, d_text, n_text, hipMemcpyDeviceToHost, st), "D2H(text)");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&d->ms_inflate[k], ev[k], ev[k + 1]);
-    *out = d;
+    *out = d.release();
     return V2P_OK;
 }
 
 int v2p_decode_counts(const v2p_decode* d, uint64_t* hap_begin)
 {
     if (!d || !hap_begin) return V2P_ERR_INVALID_ARG;
-    memcpy(hap_begin, d->hap_begin.data(), d->hap_begin.size() * sizeof(uint64_t));
+    memcpy(hap_begin, d->lists.host_hap_begin.data(), d->lists.host_hap_begin.size() * sizeof(uint64_t));
     return V2P_OK;
 }
 
 int v2p_decode_download(v2p_decode* d, uint32_t* ids)
 {
     if (!d) return V2P_ERR_INVALID_ARG;
-    if (!d->n_ids) return V2P_OK;
+    if (!d->lists.n_ids) return V2P_OK;
     if (!ids) return V2P_ERR_INVALID_ARG;
     Guard g(d->ctx);
     (void)hipSetDevice(ctx_device(d->ctx));
     hipStream_t st = ctx_stream(d->ctx);
-    hipError_t e = hipMemcpyAsync(ids, d->d_ids, d->n_ids * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(ids, d->lists.ids.get<void>(), d->lists.n_ids * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e == hipSuccess ? V2P_OK : ctx_fail(d->ctx, V2P_ERR_HIP, std::string("D2H(ids): ") + hipGetErrorString(e), -1);
 }
@@ -459,28 +479,19 @@ int v2p_decode_download(v2p_decode* d, uint32_t* ids)
 int v2p_decode_device(const v2p_decode* d, const uint64_t** d_hap_begin, const uint32_t** d_ids)
 {
     if (!d || !d_hap_begin || !d_ids) return V2P_ERR_INVALID_ARG;
-    *d_hap_begin = d->d_hap_begin;
-    *d_ids = d->d_ids;
+    *d_hap_begin = d->lists.hap_begin.get<uint64_t>();
+    *d_ids = d->lists.ids.get<uint32_t>();
     return V2P_OK;
 }
 
 int v2p_decode_timing(const v2p_decode* d, float* ms_parse, float* ms_count, float* ms_scan, float* ms_emit)
 {
-    if (!d) return V2P_ERR_INVALID_ARG;
-    if (ms_parse) *ms_parse = d->ms[0];
-    if (ms_count) *ms_count = d->ms[1];
-    if (ms_scan) *ms_scan = d->ms[2];
-    if (ms_emit) *ms_emit = d->ms[3];
-    return V2P_OK;
+    return d ? give_ms(d->lists.ms, {ms_parse, ms_count, ms_scan, ms_emit}) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_inflate_timing(const v2p_decode* d, float* ms_h2d, float* ms_inflate, float* ms_d2h)
 {
-    if (!d) return V2P_ERR_INVALID_ARG;
-    if (ms_h2d) *ms_h2d = d->ms_inflate[0];
-    if (ms_inflate) *ms_inflate = d->ms_inflate[1];
-    if (ms_d2h) *ms_d2h = d->ms_inflate[2];
-    return V2P_OK;
+    return d ? give_ms(d->ms_inflate, {ms_h2d, ms_inflate, ms_d2h}) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos,
@@ -490,33 +501,15 @@ int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const ui
 {
     if (!ctx) return V2P_ERR_INVALID_ARG;
     Guard g(ctx);
-    if (!d || d->ctx != ctx || !d->d_hap_begin || d->hap_begin.empty())
-        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: needs a decode that holds lists (v2p_decode_run / v2p_decode_run_inflated)", -1);
-    if (!per_proband || !per_type || (n_tx && !per_transcript) || !info ||
-        (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !extra_begin)) || (n_csq && extra_begin[n_csq] && !extra))
-        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_stats: null argument", -1);
-    const uint64_t S = d->n_samples, n_haps = 2 * S;
-    (void)hipSetDevice(ctx_device(ctx));
-    hipStream_t st = ctx_stream(ctx);
-    struct Temp {                                       // freed on every exit path
-        void* p[2] = {nullptr, nullptr};
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } tmp;
-    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
-    d->refused.clear();
-    d->ms_stats[0] = d->ms_stats[1] = 0;
-    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
-    bool uploaded = false;
-    const int trc = prepare_tables(ctx, d, "v2p_decode_stats", rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, st, &uploaded);
-    if (trc != V2P_OK) return trc;
-    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
-    uint64_t max_len = 0;
-    for (uint64_t h = 0; h < n_haps; ++h) max_len = std::max(max_len, d->hap_begin[h + 1] - d->hap_begin[h]);
+    const TableArgs t{rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, tx_text, tx_begin, tx_len};
+    Events<3> ev;
+    ListCall c{};
+    const int brc = begin_list_call(ctx, d, "v2p_decode_stats", per_proband && per_type && (!n_tx || per_transcript) && info, t, &v2p_decode::stats, ev, &c);
+    if (brc != V2P_OK) return brc;
+    hipStream_t st = c.st;
+    const uint64_t S = d->n_samples, n_haps = c.n_haps, max_len = c.max_len;
     // sizes: the bitmap covers every transcript; the filter gets about 32 bits per id of the longest list inside 64 KiB of LDS, and
     // more LDS (fewer workgroups per CU) only when that leaves fewer than 8 bits per id
-    auto pow2_floor = [](uint64_t v) { uint64_t p = 1; while (p * 2 <= v) p *= 2; return p; };
-    auto pow2_ceil = [](uint64_t v) { uint64_t p = 1; while (p < v) p *= 2; return p; };
     uint32_t W = caps && caps->bitmap_words ? caps->bitmap_words : uint32_t(std::max<uint64_t>(1, (n_tx + 31) / 32));
     uint32_t C = caps && caps->sort_capacity ? caps->sort_capacity : 2048u;
     uint32_t F = caps ? caps->filter_words : 0u;
@@ -536,40 +529,34 @@ int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const ui
     info->bitmap_words = W; info->filter_words = F; info->sort_capacity = C; info->lds_bytes = uint32_t(stats_lds_bytes(W, F, C));
 
     const uint64_t n_out = 23 * S + n_tx + 3;           // per_proband | per_type | per_transcript | status
-    RTRY(dmalloc(&tmp.p[0], n_out * sizeof(uint64_t)), "hipMalloc(stats tables)");
-    RTRY(dmalloc(&tmp.p[1], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
-    uint64_t* d_out = static_cast<uint64_t*>(tmp.p[0]);
-    RTRY(hipMemsetAsync(d_out, 0, n_out * sizeof(uint64_t), st), "hipMemset(stats tables)");
-    RTRY(hipMemsetAsync(d_out + 23 * S + n_tx, 0xFF, sizeof(uint64_t), st), "hipMemset(stats status)");
-    RTRY(hipMemsetAsync(tmp.p[1], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
+    DevMem d_tables, d_refused;                         // freed on every exit path
+    TRY(d_tables.alloc(n_out * sizeof(uint64_t)), "hipMalloc(stats tables)");
+    TRY(d_refused.alloc(n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
+    uint64_t* d_out = d_tables.get<uint64_t>();
+    TRY(hipMemsetAsync(d_out, 0, n_out * sizeof(uint64_t), st), "hipMemset(stats tables)");
+    TRY(hipMemsetAsync(d_out + 23 * S + n_tx, 0xFF, sizeof(uint64_t), st), "hipMemset(stats status)");
+    TRY(hipMemsetAsync(d_refused.get<void>(), 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
     StatsArgs a{};
-    a.hap_begin = d->d_hap_begin; a.ids = d->d_ids; a.n_haps = uint32_t(n_haps);
-    a.rec = d->d_tab_rec; a.extra_begin = d->d_tab_extra_begin; a.extra = d->d_tab_extra; a.n_csq = uint32_t(n_csq);
+    a.hap_begin = d->lists.hap_begin.get<uint64_t>(); a.ids = d->lists.ids.get<uint32_t>(); a.n_haps = uint32_t(n_haps);
+    a.rec = d->tables.rec.get<StatsRec>(); a.extra_begin = d->tables.extra_begin.get<uint32_t>(); a.extra = d->tables.extra.get<uint32_t>();
+    a.n_csq = uint32_t(n_csq);
     a.per_proband = reinterpret_cast<unsigned long long*>(d_out);
     a.per_type = reinterpret_cast<unsigned long long*>(d_out + S);
     a.per_transcript = reinterpret_cast<unsigned long long*>(d_out + 23 * S);
     a.status = reinterpret_cast<unsigned long long*>(d_out + 23 * S + n_tx);
-    a.refused = static_cast<uint32_t*>(tmp.p[1]);
+    a.refused = d_refused.get<uint32_t>();
     a.bitmap_words = W; a.filter_words = F; a.sort_capacity = C;
-    RTRY(launch_group_stats(a, st), "group_stats_kernel");
-    RTRY(hipEventRecord(tmp.e[2], st), "hipEventRecord");
+    TRY(launch_group_stats(a, st), "group_stats_kernel");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
     std::vector<uint64_t> out(n_out);
-    RTRY(hipMemcpyAsync(out.data(), d_out, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(stats tables)");
-    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (uploaded) (void)hipEventElapsedTime(&d->ms_stats[0], tmp.e[0], tmp.e[1]);
-    (void)hipEventElapsedTime(&d->ms_stats[1], tmp.e[1], tmp.e[2]);
+    TRY(hipMemcpyAsync(out.data(), d_out, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(stats tables)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (c.uploaded) (void)hipEventElapsedTime(&d->stats.ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&d->stats.ms[1], ev[1], ev[2]);
     const uint64_t* status = out.data() + 23 * S + n_tx;
     info->n_refused = status[1]; info->n_sorted_members = status[2];
-    if (status[1]) {
-        std::vector<uint32_t> fl(n_haps);
-        RTRY(hipMemcpy(fl.data(), tmp.p[1], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
-        for (uint64_t h = 0; h < n_haps; ++h) if (fl[h]) d->refused.push_back(h);
-    }
-    if (status[0] != ~0ull) {
-        const uint64_t hap = status[0] >> 32;
-        const uint32_t why = uint32_t(status[0]);
-        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, abort_message(why, n_tx, tx_text, tx_begin, tx_len), int64_t(hap));
-    }
+    const int erc = end_list_call(ctx, c, status, d_refused, d->stats.refused, t);
+    if (erc != V2P_OK) return erc;
     memcpy(per_proband, out.data(), S * sizeof(uint64_t));
     memcpy(per_type, out.data() + S, 22 * S * sizeof(uint64_t));
     if (n_tx) memcpy(per_transcript, out.data() + 23 * S, n_tx * sizeof(uint64_t));
@@ -578,17 +565,12 @@ int v2p_decode_stats(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const ui
 
 int v2p_decode_stats_refused(const v2p_decode* d, uint64_t* lists)
 {
-    if (!d || (!lists && !d->refused.empty())) return V2P_ERR_INVALID_ARG;
-    if (!d->refused.empty()) memcpy(lists, d->refused.data(), d->refused.size() * sizeof(uint64_t));
-    return V2P_OK;
+    return d ? give_refused(d->stats.refused, lists) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_kernel)
 {
-    if (!d) return V2P_ERR_INVALID_ARG;
-    if (ms_upload) *ms_upload = d->ms_stats[0];
-    if (ms_kernel) *ms_kernel = d->ms_stats[1];
-    return V2P_OK;
+    return d ? give_ms(d->stats.ms, {ms_upload, ms_kernel}) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos,
@@ -597,33 +579,16 @@ int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const u
 {
     if (!ctx) return V2P_ERR_INVALID_ARG;
     Guard g(ctx);
-    if (!d || d->ctx != ctx || !d->d_hap_begin || d->hap_begin.empty())
-        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: needs a decode that holds lists (v2p_decode_run / v2p_decode_run_inflated)", -1);
-    if (!info || (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !extra_begin)) || (n_csq && extra_begin[n_csq] && !extra))
-        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups: null argument", -1);
-    const uint64_t n_haps = 2 * d->n_samples;
-    (void)hipSetDevice(ctx_device(ctx));
-    hipStream_t st = ctx_stream(ctx);
-    d->release_groups();
-    d->groups_refused.clear();
-    for (float& x : d->ms_groups) x = 0;
-    struct Temp {                                       // freed on every exit path
-        void* p[3] = {nullptr, nullptr, nullptr};
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Temp() { for (void* x : p) if (x) (void)hipFree(x); for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } tmp;
-    for (auto& e : tmp.e) RTRY(hipEventCreate(&e), "hipEventCreate");
-    RTRY(hipEventRecord(tmp.e[0], st), "hipEventRecord");
-    bool uploaded = false;
-    const int trc = prepare_tables(ctx, d, "v2p_decode_groups", rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, st, &uploaded);
-    if (trc != V2P_OK) return trc;
-    RTRY(hipEventRecord(tmp.e[1], st), "hipEventRecord");
-    uint64_t max_len = 0;
-    for (uint64_t h = 0; h < n_haps; ++h) max_len = std::max(max_len, d->hap_begin[h + 1] - d->hap_begin[h]);
+    const TableArgs t{rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, n_csq, n_tx, tx_text, tx_begin, tx_len};
+    Events<5> ev;
+    ListCall c{};
+    const int brc = begin_list_call(ctx, d, "v2p_decode_groups", info != nullptr, t, &v2p_decode::groups, ev, &c);
+    if (brc != V2P_OK) return brc;
+    hipStream_t st = c.st;
+    const uint64_t n_haps = c.n_haps, max_len = c.max_len;
+    Groups& gr = d->groups;
     // sizes: the bitmap covers every transcript; keys for the longest list and an eighth more (extras are rare), at least 2 048, a power of two; the
     // filter gets about 32 bits per id of the longest list.  Whatever does not fit 160 KiB of LDS shrinks, and lists over it are refused.
-    auto pow2_floor = [](uint64_t v) { uint64_t p = 1; while (p * 2 <= v) p *= 2; return p; };
-    auto pow2_ceil = [](uint64_t v) { uint64_t p = 1; while (p < v) p *= 2; return p; };
     const uint64_t lds_max = 160u * 1024u;
     uint64_t W = caps && caps->bitmap_words ? caps->bitmap_words : std::max<uint64_t>(1, (n_tx + 31) / 32);
     uint64_t C = caps && caps->key_capacity ? caps->key_capacity : pow2_ceil(std::max<uint64_t>(2048, max_len + max_len / 8));
@@ -644,58 +609,54 @@ int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const u
     info->bitmap_words = uint32_t(W); info->filter_words = uint32_t(F); info->key_capacity = uint32_t(C);
     info->lds_bytes = uint32_t(groups_lds_bytes(uint32_t(W), uint32_t(F), uint32_t(C)));
 
-    RTRY(dmalloc(&tmp.p[0], 2 * n_haps * sizeof(uint32_t)), "hipMalloc(group counts)");
-    RTRY(dmalloc(&tmp.p[1], n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
-    RTRY(dmalloc(&tmp.p[2], 2 * sizeof(uint64_t)), "hipMalloc(groups status)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_hap_group_begin), 2 * (n_haps + 1) * sizeof(uint64_t)), "hipMalloc(hap_group_begin)");
-    RTRY(hipMemsetAsync(tmp.p[1], 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
-    RTRY(hipMemsetAsync(tmp.p[2], 0, 2 * sizeof(uint64_t), st), "hipMemset(groups status)");
-    RTRY(hipMemsetAsync(tmp.p[2], 0xFF, sizeof(uint64_t), st), "hipMemset(groups status)");
+    DevMem d_counts, d_refused, d_status;               // freed on every exit path
+    TRY(d_counts.alloc(2 * n_haps * sizeof(uint32_t)), "hipMalloc(group counts)");
+    TRY(d_refused.alloc(n_haps * sizeof(uint32_t)), "hipMalloc(refused)");
+    TRY(d_status.alloc(2 * sizeof(uint64_t)), "hipMalloc(groups status)");
+    TRY(gr.hap_group_begin.alloc(2 * (n_haps + 1) * sizeof(uint64_t)), "hipMalloc(hap_group_begin)");
+    uint64_t* d_hap_group_begin = gr.hap_group_begin.get<uint64_t>();
+    TRY(hipMemsetAsync(d_refused.get<void>(), 0, n_haps * sizeof(uint32_t), st), "hipMemset(refused)");
+    TRY(hipMemsetAsync(d_status.get<void>(), 0, 2 * sizeof(uint64_t), st), "hipMemset(groups status)");
+    TRY(hipMemsetAsync(d_status.get<void>(), 0xFF, sizeof(uint64_t), st), "hipMemset(groups status)");
     GroupsArgs a{};
-    a.hap_begin = d->d_hap_begin; a.ids = d->d_ids; a.n_haps = uint32_t(n_haps);
-    a.rec = d->d_tab_rec; a.extra_begin = d->d_tab_extra_begin; a.extra = d->d_tab_extra; a.n_csq = uint32_t(n_csq);
-    a.counts = static_cast<uint32_t*>(tmp.p[0]); a.refused = static_cast<uint32_t*>(tmp.p[1]);
-    a.status = static_cast<unsigned long long*>(tmp.p[2]);
-    a.hap_group_begin = reinterpret_cast<unsigned long long*>(d->d_hap_group_begin);
+    a.hap_begin = d->lists.hap_begin.get<uint64_t>(); a.ids = d->lists.ids.get<uint32_t>(); a.n_haps = uint32_t(n_haps);
+    a.rec = d->tables.rec.get<StatsRec>(); a.extra_begin = d->tables.extra_begin.get<uint32_t>(); a.extra = d->tables.extra.get<uint32_t>();
+    a.n_csq = uint32_t(n_csq);
+    a.counts = d_counts.get<uint32_t>(); a.refused = d_refused.get<uint32_t>();
+    a.status = d_status.get<unsigned long long>();
+    a.hap_group_begin = reinterpret_cast<unsigned long long*>(d_hap_group_begin);
     a.hap_member_begin = a.hap_group_begin + n_haps + 1;
     a.bitmap_words = uint32_t(W); a.filter_words = uint32_t(F); a.key_capacity = uint32_t(C);
-    RTRY(launch_groups_count(a, st), "group_csr_kernel (count)");
-    RTRY(hipEventRecord(tmp.e[2], st), "hipEventRecord");
-    RTRY(launch_groups_scan(a, st), "group_csr_scan_kernel");
-    RTRY(hipEventRecord(tmp.e[3], st), "hipEventRecord");
+    TRY(launch_groups_count(a, st), "group_csr_kernel (count)");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(launch_groups_scan(a, st), "group_csr_scan_kernel");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
     uint64_t status[2] = {~0ull, 0}, totals[2] = {0, 0};
-    RTRY(hipMemcpyAsync(status, tmp.p[2], sizeof(status), hipMemcpyDeviceToHost, st), "D2H(groups status)");
-    RTRY(hipMemcpyAsync(&totals[0], d->d_hap_group_begin + n_haps, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group total)");
-    RTRY(hipMemcpyAsync(&totals[1], d->d_hap_group_begin + 2 * n_haps + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(member total)");
-    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (uploaded) (void)hipEventElapsedTime(&d->ms_groups[0], tmp.e[0], tmp.e[1]);
-    (void)hipEventElapsedTime(&d->ms_groups[1], tmp.e[1], tmp.e[2]);
-    (void)hipEventElapsedTime(&d->ms_groups[2], tmp.e[2], tmp.e[3]);
+    TRY(hipMemcpyAsync(status, d_status.get<void>(), sizeof(status), hipMemcpyDeviceToHost, st), "D2H(groups status)");
+    TRY(hipMemcpyAsync(&totals[0], d_hap_group_begin + n_haps, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group total)");
+    TRY(hipMemcpyAsync(&totals[1], d_hap_group_begin + 2 * n_haps + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(member total)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (c.uploaded) (void)hipEventElapsedTime(&gr.ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&gr.ms[1], ev[1], ev[2]);
+    (void)hipEventElapsedTime(&gr.ms[2], ev[2], ev[3]);
     info->n_refused = status[1];
-    if (status[1]) {
-        std::vector<uint32_t> fl(n_haps);
-        RTRY(hipMemcpy(fl.data(), tmp.p[1], n_haps * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(refused)");
-        for (uint64_t h = 0; h < n_haps; ++h) if (fl[h]) d->groups_refused.push_back(h);
-    }
-    if (status[0] != ~0ull) {
-        d->release_groups();
-        return ctx_fail(ctx, V2P_ERR_DUPLICATE_POS, abort_message(uint32_t(status[0]), n_tx, tx_text, tx_begin, tx_len), int64_t(status[0] >> 32));
-    }
-    d->n_groups = totals[0]; d->n_members = totals[1];
+    const int erc = end_list_call(ctx, c, status, d_refused, gr.refused, t);
+    if (erc != V2P_OK) { gr.hap_group_begin.reset(); return erc; }     // an abort leaves no CSR; its refused lists and timings stay
+    gr.n_groups = totals[0]; gr.n_members = totals[1];
     info->n_groups = totals[0]; info->n_members = totals[1];
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_group_transcript), (d->n_groups + 1) * sizeof(uint32_t)), "hipMalloc(group_transcript)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_group_member_begin), (d->n_groups + 1) * sizeof(uint64_t)), "hipMalloc(group_member_begin)");
-    RTRY(dmalloc(reinterpret_cast<void**>(&d->d_member_ids), (d->n_members + 1) * sizeof(uint32_t)), "hipMalloc(member_ids)");
-    a.group_transcript = d->d_group_transcript;
-    a.group_member_begin = reinterpret_cast<unsigned long long*>(d->d_group_member_begin);
-    a.member_ids = d->d_member_ids;
-    a.n_groups = d->n_groups; a.n_members = d->n_members;
-    RTRY(hipEventRecord(tmp.e[3], st), "hipEventRecord");
-    RTRY(launch_groups_emit(a, st), "group_csr_kernel (emit)");
-    RTRY(hipEventRecord(tmp.e[4], st), "hipEventRecord");
-    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    (void)hipEventElapsedTime(&d->ms_groups[3], tmp.e[3], tmp.e[4]);
-    d->groups_ok = true;
+    TRY(gr.group_transcript.alloc((gr.n_groups + 1) * sizeof(uint32_t)), "hipMalloc(group_transcript)");
+    TRY(gr.group_member_begin.alloc((gr.n_groups + 1) * sizeof(uint64_t)), "hipMalloc(group_member_begin)");
+    TRY(gr.member_ids.alloc((gr.n_members + 1) * sizeof(uint32_t)), "hipMalloc(member_ids)");
+    a.group_transcript = gr.group_transcript.get<uint32_t>();
+    a.group_member_begin = gr.group_member_begin.get<unsigned long long>();
+    a.member_ids = gr.member_ids.get<uint32_t>();
+    a.n_groups = gr.n_groups; a.n_members = gr.n_members;
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    TRY(launch_groups_emit(a, st), "group_csr_kernel (emit)");
+    TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&gr.ms[3], ev[3], ev[4]);
+    gr.ok = true;
     return V2P_OK;
 }
 
@@ -704,47 +665,39 @@ int v2p_decode_groups_download(v2p_decode* d, uint64_t* hap_group_begin, uint32_
     if (!d) return V2P_ERR_INVALID_ARG;
     Guard g(d->ctx);
     v2p_ctx* ctx = d->ctx;
-    if (!d->groups_ok) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups_download: needs a successful v2p_decode_groups on this decode", -1);
-    if (!hap_group_begin || !group_member_begin || (d->n_groups && !group_transcript) || (d->n_members && !member_ids))
+    Groups& gr = d->groups;
+    if (!gr.ok) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups_download: needs a successful v2p_decode_groups on this decode", -1);
+    if (!hap_group_begin || !group_member_begin || (gr.n_groups && !group_transcript) || (gr.n_members && !member_ids))
         return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_groups_download: null argument", -1);
     (void)hipSetDevice(ctx_device(ctx));
     hipStream_t st = ctx_stream(ctx);
-    struct Events {
-        hipEvent_t e[2] = {nullptr, nullptr};
-        ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } evs;
-    for (auto& e : evs.e) RTRY(hipEventCreate(&e), "hipEventCreate");
-    RTRY(hipEventRecord(evs.e[0], st), "hipEventRecord");
-    RTRY(hipMemcpyAsync(hap_group_begin, d->d_hap_group_begin, (2 * d->n_samples + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_group_begin)");
-    RTRY(hipMemcpyAsync(group_member_begin, d->d_group_member_begin, (d->n_groups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group_member_begin)");
-    if (d->n_groups) RTRY(hipMemcpyAsync(group_transcript, d->d_group_transcript, d->n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(group_transcript)");
-    if (d->n_members) RTRY(hipMemcpyAsync(member_ids, d->d_member_ids, d->n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(member_ids)");
-    RTRY(hipEventRecord(evs.e[1], st), "hipEventRecord");
-    RTRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    (void)hipEventElapsedTime(&d->ms_groups[4], evs.e[0], evs.e[1]);
+    Events<2> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    TRY(hipMemcpyAsync(hap_group_begin, gr.hap_group_begin.get<void>(), (2 * d->n_samples + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_group_begin)");
+    TRY(hipMemcpyAsync(group_member_begin, gr.group_member_begin.get<void>(), (gr.n_groups + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(group_member_begin)");
+    if (gr.n_groups) TRY(hipMemcpyAsync(group_transcript, gr.group_transcript.get<void>(), gr.n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(group_transcript)");
+    if (gr.n_members) TRY(hipMemcpyAsync(member_ids, gr.member_ids.get<void>(), gr.n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H(member_ids)");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&gr.ms[4], ev[0], ev[1]);
     return V2P_OK;
 }
 
 int v2p_decode_groups_refused(const v2p_decode* d, uint64_t* lists)
 {
-    if (!d || (!lists && !d->groups_refused.empty())) return V2P_ERR_INVALID_ARG;
-    if (!d->groups_refused.empty()) memcpy(lists, d->groups_refused.data(), d->groups_refused.size() * sizeof(uint64_t));
-    return V2P_OK;
+    return d ? give_refused(d->groups.refused, lists) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download)
 {
-    if (!d) return V2P_ERR_INVALID_ARG;
-    float* out[5] = {ms_upload, ms_count, ms_scan, ms_emit, ms_download};
-    for (int k = 0; k < 5; ++k) if (out[k]) *out[k] = d->ms_groups[k];
-    return V2P_OK;
+    return d ? give_ms(d->groups.ms, {ms_upload, ms_count, ms_scan, ms_emit, ms_download}) : V2P_ERR_INVALID_ARG;
 }
 
 void v2p_decode_destroy(v2p_decode* d)
 {
     if (!d) return;
     (void)hipSetDevice(ctx_device(d->ctx));
-    d->release();
     delete d;
 }
 

@@ -142,6 +142,42 @@ def _host():
     return lib
 
 
+def _check(ctx, rc, abort=False):
+    """Raises the V2PError of a failed call on `ctx` (engine.Context): its last message and index.  With `abort`, the abort of a list
+    (V2P_ERR_DUPLICATE_POS) is returned, not raised -- the call's other results stand beside it -- and None after a call that succeeded."""
+    if rc == 0:
+        return None
+    lib = _hip()
+    err = N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    if abort and rc == V2P_ERR_DUPLICATE_POS:
+        return err
+    raise err
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def _table_args(ctx, resident, tables):
+    """The fourteen leading arguments v2p_decode_stats and v2p_decode_groups share: context, decode, the seven table arrays, their two
+    sizes, the text and the transcript names in it.  `tables` is a CsqTables or anything with its arrays."""
+    return (ctx._h, resident._h, _ptr(tables.rank), _ptr(tables.flags), _ptr(tables.mut_pos), _ptr(tables.ref_pos), _ptr(tables.ident),
+            tables.extra_begin.ctypes.data, _ptr(tables.extra), tables.n_consequences, tables.n_transcripts, tables._idx.text.ctypes.data,
+            _ptr(tables.transcript_begin), _ptr(tables.transcript_len))
+
+
+class _DecodeHandle:
+    """Owner of one v2p_decode (self._h): close() destroys it, once."""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _hip().v2p_decode_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 def _arr(ptr, n, dtype):
     """A copy of a library-owned array (the handle may be closed while the array is still in use)."""
     if n == 0:
@@ -218,7 +254,7 @@ def input_format(data) -> str:
     return "bgzf" if is_bgzf(data) else "gzip" if b == b"\x1f\x8b" else "text"
 
 
-class InflatedText:
+class InflatedText(_DecodeHandle):
     """The text of a BGZF file inflated on the GPU (v2p_decode_inflate), resident for decode_bitmasks."""
 
     def __init__(self, ctx, h, n_text: int):
@@ -228,14 +264,6 @@ class InflatedText:
         t = [c_float() for _ in range(3)]
         _hip().v2p_decode_inflate_timing(self._h, *[ctypes.byref(x) for x in t])
         return dict(zip(("h2d", "inflate", "d2h"), (x.value for x in t)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _hip().v2p_decode_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
 def inflate_bgzf(ctx, gz):
@@ -250,12 +278,11 @@ def inflate_bgzf(ctx, gz):
     h = c_void_p()
     rc = lib.v2p_decode_inflate(ctx._h, buf.ctypes.data if buf.size else None, buf.size, mb.ctypes.data, ob.ctypes.data, mb.size - 1,
                                 text.ctypes.data, ctypes.byref(h))
-    if rc != 0:
-        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    _check(ctx, rc)
     return text[:int(ob[-1] - ob[0])].tobytes(), InflatedText(ctx, h, int(ob[-1] - ob[0]))
 
 
-class ResidentLists:
+class ResidentLists(_DecodeHandle):
     """The decode's lists left on the device (decode_resident): what cohort_stats counts without the ids crossing the link.  download()
     gives the HaplotypeLists; close() frees the device memory."""
 
@@ -274,20 +301,11 @@ class ResidentLists:
         return dict(zip(("parse", "count", "scan", "emit"), (x.value for x in t)))
 
     def download(self) -> HaplotypeLists:
-        lib = _hip()
         ids = np.zeros(int(self.hap_begin[-1]), dtype=np.uint32)
-        rc = lib.v2p_decode_download(self._h, ids.ctypes.data if ids.size else None)
-        if rc != 0:
-            raise N.V2PError(rc, lib.v2p_last_error(self.ctx._h).decode())
+        rc = _hip().v2p_decode_download(self._h, _ptr(ids))
+        if rc != 0:                   # (no index: the call names none)
+            raise N.V2PError(rc, _hip().v2p_last_error(self.ctx._h).decode())
         return HaplotypeLists(self.hap_begin.copy(), ids, self.timing_ms())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _hip().v2p_decode_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
 def decode_resident(ctx, idx: VcfIndex, inflated: "InflatedText" = None) -> ResidentLists:
@@ -318,8 +336,7 @@ def _decode_run(ctx, idx: VcfIndex, inflated: "InflatedText" = None):
         h = c_void_p()
         rc = lib.v2p_decode_run(ctx._h, idx.text.ctypes.data, idx.text.size, idx.row_begin.ctypes.data, idx.row_end.ctypes.data,
                                 idx.n_records, idx.n_samples, idx.csq_begin.ctypes.data, idx.csq_supported.ctypes.data, ctypes.byref(h))
-    if rc != 0:
-        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    _check(ctx, rc)
     return h
 
 
@@ -466,28 +483,17 @@ def device_groups_csr(ctx, resident: ResidentLists, tables, caps=None):
     refused lists, info dict, error or None).  `tables` is a CsqTables or anything with its arrays.  Refused lists have no groups in the
     CSR; an abort (error, V2P_ERR_DUPLICATE_POS) leaves no CSR."""
     lib = _hip()
-    T = tables.n_transcripts
     info = v2p_groups_info()
     c = v2p_groups_caps(*caps) if caps is not None else None
-    ptr = lambda a: a.ctypes.data if a.size else None
-    rc = lib.v2p_decode_groups(ctx._h, resident._h, ptr(tables.rank), ptr(tables.flags), ptr(tables.mut_pos), ptr(tables.ref_pos),
-                               ptr(tables.ident), tables.extra_begin.ctypes.data, ptr(tables.extra), tables.n_consequences, T,
-                               tables._idx.text.ctypes.data, ptr(tables.transcript_begin), ptr(tables.transcript_len),
-                               ctypes.byref(c) if c is not None else None, ctypes.byref(info))
-    err = None
-    if rc == V2P_ERR_DUPLICATE_POS:
-        err = N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
-    elif rc != 0:
-        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    rc = lib.v2p_decode_groups(*_table_args(ctx, resident, tables), ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    err = _check(ctx, rc, abort=True)
     refused = np.zeros(int(info.n_refused), np.uint64)
-    lib.v2p_decode_groups_refused(resident._h, ptr(refused))
+    lib.v2p_decode_groups_refused(resident._h, _ptr(refused))
     csr = None
     if err is None:
         csr = (np.zeros(resident.n_haplotypes + 1, np.uint64), np.zeros(int(info.n_groups), np.uint32),
                np.zeros(int(info.n_groups) + 1, np.uint64), np.zeros(int(info.n_members), np.uint32))
-        rc = lib.v2p_decode_groups_download(resident._h, csr[0].ctypes.data, ptr(csr[1]), csr[2].ctypes.data, ptr(csr[3]))
-        if rc != 0:
-            raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+        _check(ctx, lib.v2p_decode_groups_download(resident._h, csr[0].ctypes.data, _ptr(csr[1]), csr[2].ctypes.data, _ptr(csr[3])))
     t = [c_float() for _ in range(5)]
     lib.v2p_decode_groups_timing(resident._h, *[ctypes.byref(x) for x in t])
     inf = {k: int(getattr(info, k)) for k, _ in v2p_groups_info._fields_}
@@ -531,19 +537,11 @@ def device_stats(ctx, resident: ResidentLists, tables: CsqTables, caps=None):
     pp, pt, px = np.zeros(S, np.uint64), np.zeros((S, 22), np.uint64), np.zeros(max(T, 1), np.uint64)
     info = v2p_stats_info()
     c = v2p_stats_caps(*caps) if caps is not None else None
-    idx = tables._idx
-    ptr = lambda a: a.ctypes.data if a.size else None
-    rc = lib.v2p_decode_stats(ctx._h, resident._h, ptr(tables.rank), ptr(tables.flags), ptr(tables.mut_pos), ptr(tables.ref_pos),
-                              ptr(tables.ident), tables.extra_begin.ctypes.data, ptr(tables.extra), tables.n_consequences, T,
-                              idx.text.ctypes.data, ptr(tables.transcript_begin), ptr(tables.transcript_len),
-                              pp.ctypes.data, pt.ctypes.data, px.ctypes.data, ctypes.byref(c) if c is not None else None, ctypes.byref(info))
-    err = None
-    if rc == V2P_ERR_DUPLICATE_POS:
-        err = N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
-    elif rc != 0:
-        raise N.V2PError(rc, lib.v2p_last_error(ctx._h).decode(), int(lib.v2p_last_error_index(ctx._h)))
+    rc = lib.v2p_decode_stats(*_table_args(ctx, resident, tables), pp.ctypes.data, pt.ctypes.data, px.ctypes.data,
+                              ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    err = _check(ctx, rc, abort=True)
     refused = np.zeros(int(info.n_refused), np.uint64)
-    lib.v2p_decode_stats_refused(resident._h, ptr(refused))
+    lib.v2p_decode_stats_refused(resident._h, _ptr(refused))
     t = [c_float(), c_float()]
     lib.v2p_decode_stats_timing(resident._h, ctypes.byref(t[0]), ctypes.byref(t[1]))
     inf = {k: int(getattr(info, k)) for k, _ in v2p_stats_info._fields_}
