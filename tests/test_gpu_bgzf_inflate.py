@@ -16,24 +16,9 @@ GUARD = 4096
 
 
 def _launch(z: bytes, mb, ob):
-    """v2p_bgzf_inflate_launch on device buffers of the HIP runtime (through ctypes: torch cannot start on a device this process's
-    library already holds); d_out sits between two guard regions of 0xA5.  Returns (out, status, guards untouched)"""
-    from hip_util import DevBuf, hip
-    from vcf2prot_amd import _native as N
-    n = len(mb) - 1
-    total = int(ob[-1])
-    d_in = DevBuf.of(np.frombuffer(z + bytes(1), np.uint8))
-    d_off = DevBuf.of(np.concatenate([np.asarray(mb, np.uint64), np.asarray(ob, np.uint64)]))
-    buf = DevBuf(total + 2 * GUARD, fill=0xA5)
-    d_status = DevBuf(4 * (n + 1), fill=0x5A)
-    rc = N.hip_lib().v2p_bgzf_inflate_launch(None, d_in.ptr, d_off.ptr, d_off.ptr + 8 * (n + 1), n, buf.ptr + GUARD, d_status.ptr)
-    assert rc == 0 and hip().hipDeviceSynchronize() == 0
-    host = buf.download()
-    status = d_status.download().view(np.uint32).copy()
-    for b in (d_in, d_off, buf, d_status):
-        b.free()
-    guards = bool((host[:GUARD] == 0xA5).all() and (host[GUARD + total:] == 0xA5).all())
-    return host[GUARD:GUARD + total], status, guards
+    """hip_util.inflate_launch: d_out between two guard regions of 0xA5.  Returns (out, status, guards untouched)"""
+    from hip_util import inflate_launch
+    return inflate_launch(z, mb, ob, guard=GUARD)
 
 
 def test_valid_corpus_through_the_launcher_and_the_decode(built, gpu_ctx):
