@@ -414,7 +414,8 @@ int  v2p_pipeline_submit(v2p_pipeline* p,
                          const v2p_chunk* chunks, uint64_t n_chunks,
                          const uint8_t* payload, uint64_t n_payload,
                          uint64_t out_bytes, uint32_t* ticket);
-/* blocks until the submission's results are in host memory; *result stays valid until release */
+/* blocks until the submission's results are in host memory; *result stays valid until release.  One ticket's wait, result_info and
+ * release belong to one thread at a time. */
 int  v2p_pipeline_wait(v2p_pipeline* p, uint32_t ticket, const uint8_t** result, uint64_t* n);
 /* a stream slice that has been waited for: where its haplotypes start inside *result ([n_haps + 1], res_counter of
  * haplotype_instruction.rs:90,132), its digests (NULL without V2P_SUBMIT_DIGESTS), its host-side times; any pointer may be NULL */

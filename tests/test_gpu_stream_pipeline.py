@@ -181,3 +181,227 @@ def test_slots_tables_and_busy(built, gpu_ctx):
             pipe.release(t)
     finally:
         pipe.close()
+
+
+# ---- the slots' life: what a caller may do with a ticket, in and out of order ----------------------------------------------------
+
+def _cut(stream, a, b):
+    """haplotypes a .. b of a (non-FASTA) random stream as a stream of its own (views of its arrays)"""
+    from stream_util import Stream
+    k = stream.keep
+    hb, tb, ab = k[0].astype(np.int64), k[4].astype(np.int64), k[5].astype(np.int64)
+    t0, t1 = int(hb[a]), int(hb[b])
+    k0, k1, a0, a1 = int(tb[t0]), int(tb[t1]), int(ab[t0]), int(ab[t1])
+    return Stream(hb[a:b + 1] - t0, k[1][t0:t1], k[2][t0:t1], k[3][t0:t1], tb[t0:t1 + 1] - k0, ab[t0:t1 + 1] - a0,
+                  k[6][k0:k1], k[7][k0:k1], k[8][k0:k1], k[9][k0:k1], k[10][a0:a1])
+
+
+@pytest.fixture(scope="module")
+def two_slices():
+    """test_slots_tables_and_busy's stream, cut into two different haplotype ranges: (proteome, [(a, b, slice)] * 2, expected haplotypes)"""
+    rng = np.random.default_rng(17)
+    proteome, stream, want = random_stream(rng, n_haps=40, n_ref_tx=10, shape="mix", window=4096)
+    return proteome, [(a, b, _cut(stream, a, b)) for a, b in ((0, 23), (23, 40))], want
+
+
+def _offsets(want, a, b):
+    return np.concatenate([[0], np.cumsum([want[h].size for h in range(a, b)])]).astype(np.uint64)
+
+
+def _check_slice(pipe, t, a, b, want, out=None):
+    """the ticket's result is haplotypes a .. b: result_info's offsets, the bytes of the first, a middle and the last haplotype"""
+    out = pipe.wait(t) if out is None else out
+    hob = pipe.result_info(t)["hap_out_begin"]
+    assert np.array_equal(hob, _offsets(want, a, b))
+    assert out.size == int(hob[-1])
+    for h in (a, (a + b) // 2, b - 1):
+        assert np.array_equal(out[int(hob[h - a]):int(hob[h - a + 1])], want[h]), h
+
+
+def _roundtrip(pipe, sl, want):
+    a, b, st = sl
+    t = pipe.submit_stream(st, 0, False)
+    assert t >= 0
+    _check_slice(pipe, t, a, b, want)
+    pipe.release(t)
+
+
+def test_release_without_a_wait_then_reuse(built, gpu_ctx, two_slices):
+    """A result nobody waited for is released while its copies may still run; the slot's next slice (other haplotypes, other sizes)
+    comes home whole."""
+    from vcf2prot_amd.engine import Pipeline
+    proteome, (sa, sb), want = two_slices
+    gpu_ctx.upload_proteome(proteome)
+    pipe = Pipeline(gpu_ctx, 1)
+    try:
+        t = pipe.submit_stream(sa[2], 0, False)
+        pipe.release(t)
+        t2 = pipe.submit_stream(sb[2], 0, False)
+        assert t2 == t == 0
+        _check_slice(pipe, t2, sb[0], sb[1], want)
+        pipe.release(t2)
+    finally:
+        pipe.close()
+
+
+@pytest.mark.parametrize("bgzf", [False, True])
+def test_wait_twice(built, gpu_ctx, two_slices, bgzf):
+    """A second wait on a ticket answers as the first did, and the tables still answer."""
+    import gzip
+    from vcf2prot_amd import bgzf as bgzf_mod
+    from vcf2prot_amd.engine import Pipeline
+    proteome, (sa, _), want = two_slices
+    a, b, st = sa
+    gpu_ctx.upload_proteome(proteome)
+    pipe = Pipeline(gpu_ctx, 2)
+    try:
+        t = pipe.submit_stream(st, 0, False, bgzf)
+        first = pipe.wait(t).copy()
+        second = pipe.wait(t)
+        assert second.size == first.size and np.array_equal(second, first)
+        hob = pipe.result_info(t)["hap_out_begin"]
+        assert np.array_equal(hob, _offsets(want, a, b))
+        if bgzf:
+            zb = pipe.bgzf_info(t)
+            assert zb.size == b - a + 1 and int(zb[-1]) == first.size
+            z = second.tobytes()
+            for h in (a, (a + b) // 2, b - 1):
+                assert gzip.decompress(z[int(zb[h - a]):int(zb[h - a + 1])] + bgzf_mod.EOF_BLOCK) == want[h].tobytes(), h
+        else:
+            _check_slice(pipe, t, a, b, want, out=second)
+        pipe.release(t)
+    finally:
+        pipe.close()
+
+
+def _refused(call):
+    from vcf2prot_amd._native import V2PError
+    with pytest.raises(V2PError) as e:
+        call()
+    assert e.value.code == -10, e.value.code
+
+
+def test_misuse_is_err_state_and_the_pipeline_lives_on(built, gpu_ctx, coracle, two_slices):
+    """What a ticket does not allow is V2P_ERR_STATE; after each refusal an ordinary submit, wait and release gives the right bytes."""
+    from vcf2prot_amd.cohort import Cohort
+    from vcf2prot_amd.engine import Pipeline
+    proteome, (sa, sb), want = two_slices
+    gpu_ctx.upload_proteome(proteome)
+    pipe = Pipeline(gpu_ctx, 2)
+    try:
+        _refused(lambda: pipe.wait(1))                                  # a ticket never submitted
+        _roundtrip(pipe, sb, want)
+        t = pipe.submit_stream(sa[2], 0, False)
+        _refused(lambda: pipe.result_info(t))                           # before the wait
+        _roundtrip(pipe, sb, want)
+        _check_slice(pipe, t, sa[0], sa[1], want)
+        _refused(lambda: pipe.bgzf_info(t))                             # submitted without bgzf
+        _roundtrip(pipe, sb, want)
+        _refused(lambda: pipe.reserve(1 << 20, 1 << 20))                # a slot holds a result
+        _roundtrip(pipe, sb, want)
+        _check_slice(pipe, t, sa[0], sa[1], want)                       # ... and holds it still
+        pipe.release(t)
+    finally:
+        pipe.close()
+    # packed submissions: a cohort's images and slices
+    c = Cohort.preset("C3", n_samples=6)
+    gpu_ctx.upload_proteome(c.proteome())
+    img = c.pack(0, 3, n_threads=2)
+    pipe = Pipeline(gpu_ctx, 1)
+
+    def stream_roundtrip():
+        st = c.txstream(3, 6, n_threads=1)
+        t = pipe.submit_stream(st, 0, False)
+        st.close()
+        out = pipe.wait(t)
+        hob = pipe.result_info(t)["hap_out_begin"]
+        for i in range(3):
+            assert np.array_equal(out[int(hob[i]):int(hob[i + 1])], oracle_hap(c, coracle, 3 + i)), i
+        pipe.release(t)
+
+    def packed_is_whole(t):
+        out = pipe.wait(t)
+        for i in range(3):
+            assert np.array_equal(out[int(img.hap_out_begin[i]):int(img.hap_out_begin[i + 1])], oracle_hap(c, coracle, i)), i
+    try:
+        t = pipe.submit(img.desc, img.chunks, img.payload, img.out_bytes)
+        pipe.wait(t)
+        _refused(lambda: pipe.result_info(t))                           # a packed submission has no tables
+        packed_is_whole(t)
+        pipe.release(t)
+        stream_roundtrip()
+        t = pipe.submit(img.desc, img.chunks, img.payload, img.out_bytes)
+        _refused(lambda: pipe.submit(img.desc, img.chunks, img.payload, img.out_bytes))     # slot `next` is unreleased
+        packed_is_whole(t)
+        pipe.release(t)
+        stream_roundtrip()
+    finally:
+        pipe.close()
+
+
+def test_a_slice_the_runner_refuses(built, gpu_ctx, coracle):
+    """C4's transcripts are no tile image (test_gpu_tiles.py): the runner's refusal reaches the waiter, the slot is released and takes
+    the same slice under the routing rule."""
+    from vcf2prot_amd._native import V2PError
+    from vcf2prot_amd.cohort import Cohort
+    from vcf2prot_amd.engine import Pipeline
+    c = Cohort.preset("C4")
+    gpu_ctx.upload_proteome(c.proteome())
+    stream = c.txstream(7, 19, n_threads=4)
+    pipe = Pipeline(gpu_ctx, 1)
+    try:
+        t = pipe.submit_stream(stream, 9, False)
+        with pytest.raises(V2PError) as e:
+            pipe.wait(t)
+        assert e.value.code == -9
+        pipe.release(t)
+        t2 = pipe.submit_stream(stream, 0, False)
+        assert t2 == t
+        out = pipe.wait(t2)
+        hob = pipe.result_info(t2)["hap_out_begin"]
+        assert np.array_equal(out[int(hob[3]):int(hob[4])], oracle_hap(c, coracle, 10))
+        pipe.release(t2)
+    finally:
+        pipe.close()
+        stream.close()
+
+
+def test_packed_and_stream_submissions_alternate(built, gpu_ctx, coracle):
+    """Host-packed images and stream slices share the slots of one pipeline: each slot carries one kind, then the other."""
+    from vcf2prot_amd.cohort import Cohort
+    from vcf2prot_amd.engine import Pipeline
+    c = Cohort.preset("C3", n_samples=6)
+    gpu_ctx.upload_proteome(c.proteome())
+    pipe = Pipeline(gpu_ctx, 2)
+
+    def submit(kind, h):
+        if kind == "packed":
+            img = c.pack(h, h + 3, n_threads=2)
+            return pipe.submit(img.desc, img.chunks, img.payload, img.out_bytes), kind, h, img.hap_out_begin
+        st = c.txstream(h, h + 3, n_threads=1)
+        t = pipe.submit_stream(st, 0, False)
+        st.close()
+        return t, kind, h, None
+
+    def collect(job):
+        t, kind, h, hob = job
+        out = pipe.wait(t)
+        if kind == "stream":
+            hob = pipe.result_info(t)["hap_out_begin"]
+        for i in range(3):
+            assert np.array_equal(out[int(hob[i]):int(hob[i + 1])], oracle_hap(c, coracle, h + i)), (kind, h + i)
+        pipe.release(t)
+        return t
+    try:
+        j0, j1 = submit("packed", 0), submit("stream", 3)
+        assert (j0[0], j1[0]) == (0, 1)
+        collect(j0)
+        j2 = submit("stream", 6)                                        # slot 0: a packed image, then a slice
+        assert j2[0] == 0
+        collect(j1)
+        j3 = submit("packed", 9)                                        # slot 1: a slice, then a packed image
+        assert j3[0] == 1
+        collect(j2)
+        collect(j3)
+    finally:
+        pipe.close()

@@ -31,6 +31,7 @@
 #include "v2p_ctx_internal.h"
 #include "bgzf_kernels.h"
 #include "bgzf_format.hpp"
+#include "pipe_slots.hpp"
 
 using namespace v2p;
 
@@ -3133,8 +3134,10 @@ int v2p_batch_scribble(v2p_batch* b, int byte)
 //                                the counts block the runner, nobody else), and the arena travels into the slot's pinned result buffer on
 //                                the slot's second stream.  What the reference does per sample (get_g_rep(..).execute(engine), then the
 //                                bytes to the host: personalized_genome.rs:61-69, parts/exec.rs:23-42) with nothing packed on the host.
+// A slot's life -- whose it is, who may touch its fields -- is the board's (pipe_slots.hpp: the states, the lock rule); every function
+// below touches a slot's fields only while the board says the slot is its caller's.
 
-enum : int { SLOT_FREE = 0, SLOT_QUEUED = 1, SLOT_LAUNCHED = 2, SLOT_FAILED = 3 };
+using SlotState = pipe_slots::State;
 
 struct PipeSlot {
     hipStream_t stream = nullptr;
@@ -3144,11 +3147,8 @@ struct PipeSlot {
     PinnedBuf h_in, h_out;
     uint64_t out_bytes = 0;
     unsigned long long status = STATUS_CLEAN;
-    bool busy = false;        // holds a result the caller has not released
-    bool in_flight = false;   // work was enqueued on `stream` and `done` has not been waited for
+    bool is_stream = false;                // what was submitted: a slice of the stream, or a packed image
     // ---- stream submissions ----
-    bool is_stream = false;
-    int state = SLOT_FREE;                 // (under v2p_pipeline::pmu)
     v2p_stream* rs = nullptr;              // the slice on the device: buffers kept from submission to submission
     v2p_batch* batch = nullptr;            // ... and its image / arena
     StreamLayout lay{};
@@ -3165,19 +3165,24 @@ struct PipeSlot {
     uint64_t o_status = 0, o_digests = 0;  // where the status word and the digests sit in h_out
     uint64_t o_zbegin = 0, z_bytes = 0;    // V2P_SUBMIT_BGZF: where hap_z_begin sits in h_out; the members' total (known at the wait)
     double t_stage_ms = 0, t_queue_ms = 0, t_gpu_ms = 0;
+    // whatever was enqueued on the slot has ended: its staging and result buffers are nobody's (what a slot owes before it is FREE)
+    hipError_t drain() const
+    {
+        hipError_t e = stream ? hipStreamSynchronize(stream) : hipSuccess;
+        if (e == hipSuccess && d2h) e = hipStreamSynchronize(d2h);
+        return e;
+    }
 };
 
 struct v2p_pipeline {
-    v2p_ctx* ctx = nullptr;
+    v2p_pipeline(v2p_ctx* c, uint32_t n_slots) : ctx(c), slots(n_slots), board(n_slots) {}
+    v2p_ctx* ctx;
     std::vector<PipeSlot> slots;
-    uint32_t next = 0;
+    pipe_slots::Board board;
     // stream submissions
-    std::mutex pmu;
-    std::condition_variable cv;
-    std::vector<uint32_t> jobs;            // slots queued for the runner, in submission order
-    bool stop = false;
+    std::once_flag runner_started;
     std::thread runner;
-    uint32_t copy_threads = 8;
+    std::atomic<uint32_t> copy_threads{8};
 };
 
 static void pipeline_runner(v2p_pipeline* p);
@@ -3187,10 +3192,8 @@ int v2p_pipeline_create(v2p_ctx* c, uint32_t n_slots, v2p_pipeline** out)
     if (!c || !out || n_slots == 0 || n_slots > 16) return V2P_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    v2p_pipeline* p = new (std::nothrow) v2p_pipeline();
+    v2p_pipeline* p = new (std::nothrow) v2p_pipeline(c, n_slots);
     if (!p) return c->fail(V2P_ERR_HIP, "out of host memory");
-    p->ctx = c;
-    p->slots.resize(n_slots);
     for (PipeSlot& s : p->slots) {
         hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
@@ -3204,8 +3207,7 @@ void v2p_pipeline_destroy(v2p_pipeline* p)
 {
     if (!p) return;
     if (p->runner.joinable()) {
-        { std::lock_guard<std::mutex> lk(p->pmu); p->stop = true; }
-        p->cv.notify_all();
+        p->board.stop();
         p->runner.join();
     }
     (void)hipSetDevice(p->ctx->device);
@@ -3223,31 +3225,16 @@ void v2p_pipeline_destroy(v2p_pipeline* p)
     delete p;
 }
 
-int v2p_pipeline_submit(v2p_pipeline* p,
-                        const uint64_t* desc, uint64_t n_desc,
-                        const v2p_chunk* chunks, uint64_t n_chunks,
-                        const uint8_t* payload, uint64_t n_payload,
-                        uint64_t out_bytes, uint32_t* ticket)
+// a packed image onto a slot its caller has claimed (context held): staged, uploaded, stitched, on its way home, `done` recorded
+static int packed_onto_slot(v2p_ctx* c, PipeSlot& s,
+                            const uint64_t* desc, uint64_t n_desc,
+                            const v2p_chunk* chunks, uint64_t n_chunks,
+                            const uint8_t* payload, uint64_t n_payload, uint64_t out_bytes)
 {
-    if (!p || !ticket || (n_desc && !desc) || (n_chunks && !chunks) || (n_payload && !payload)) return V2P_ERR_INVALID_ARG;
-    v2p_ctx* c = p->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (n_chunks > 0xFFFFFFFFull) return c->fail(V2P_ERR_UNSUPPORTED, "more than 2^32 chunks in one image");
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    uint32_t t;
-    {
-        std::lock_guard<std::mutex> pl(p->pmu);
-        t = p->next;
-        if (p->slots[t].busy) return c->fail(V2P_ERR_STATE, "pipeline slot still holds an unreleased result");
-    }
-    PipeSlot& s = p->slots[t];
     {
         const int rc = check_packed(c, n_desc, reinterpret_cast<const Chunk*>(chunks), n_chunks, nullptr, 0, out_bytes);
         if (rc) return rc;
     }
-    // the slot's staging and device buffers are about to be rewritten (and possibly reallocated): whatever was
-    // enqueued on it before -- a submit that failed half way, a result released without a wait -- must be done
-    if (s.in_flight) { HIP_TRY(c, hipStreamSynchronize(s.stream), "hipStreamSynchronize(slot)"); if (s.d2h) HIP_TRY(c, hipStreamSynchronize(s.d2h), "hipStreamSynchronize(slot)"); s.in_flight = false; }
     const size_t b_desc = size_t(n_desc) * 8, b_chunks = size_t(n_chunks) * sizeof(Chunk);
     const size_t o_chunks = (b_desc + 15) & ~size_t(15), o_payload = (o_chunks + b_chunks + 15) & ~size_t(15);
     HIP_TRY(c, s.h_in.ensure(o_payload + n_payload), "hipHostMalloc(in)");
@@ -3265,7 +3252,6 @@ int v2p_pipeline_submit(v2p_pipeline* p,
             order_chunks_for_xcds(reinterpret_cast<Chunk*>(s.h_in.p + o_chunks), n_chunks, desc, n_desc, c->proteome_len);
     }
     if (n_payload) memcpy(s.h_in.p + o_payload, payload, n_payload);
-    s.in_flight = true;       // from here on the stream may hold work that reads h_in / writes h_out
     s.is_stream = false;
     if (b_desc) HIP_TRY(c, hipMemcpyAsync(s.d_desc.ptr(), s.h_in.p, b_desc, hipMemcpyHostToDevice, s.stream), "H2D(desc)");
     if (b_chunks) HIP_TRY(c, hipMemcpyAsync(s.d_chunks.ptr(), s.h_in.p + o_chunks, b_chunks, hipMemcpyHostToDevice, s.stream), "H2D(chunks)");
@@ -3279,11 +3265,27 @@ int v2p_pipeline_submit(v2p_pipeline* p,
     HIP_TRY(c, hipMemcpyAsync(s.h_out.p + ((out_bytes + 7) & ~7ull), s.d_status.ptr(), sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream), "D2H(status)");
     HIP_TRY(c, hipEventRecord(s.done, s.stream), "hipEventRecord");
     s.out_bytes = out_bytes; s.o_status = (out_bytes + 7) & ~7ull;
-    {
-        std::lock_guard<std::mutex> pl(p->pmu);
-        s.busy = true; s.state = SLOT_LAUNCHED; s.rc = V2P_OK;
-        p->next = (t + 1) % uint32_t(p->slots.size());
-    }
+    s.rc = V2P_OK;
+    return V2P_OK;
+}
+
+int v2p_pipeline_submit(v2p_pipeline* p,
+                        const uint64_t* desc, uint64_t n_desc,
+                        const v2p_chunk* chunks, uint64_t n_chunks,
+                        const uint8_t* payload, uint64_t n_payload,
+                        uint64_t out_bytes, uint32_t* ticket)
+{
+    if (!p || !ticket || (n_desc && !desc) || (n_chunks && !chunks) || (n_payload && !payload)) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = p->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_chunks > 0xFFFFFFFFull) return c->fail(V2P_ERR_UNSUPPORTED, "more than 2^32 chunks in one image");
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    uint32_t t;
+    if (!p->board.claim_next(&t)) return c->fail(V2P_ERR_STATE, "pipeline slot still holds an unreleased result");
+    PipeSlot& s = p->slots[t];
+    const int rc = packed_onto_slot(c, s, desc, n_desc, chunks, n_chunks, payload, n_payload, out_bytes);
+    if (rc) { (void)s.drain(); p->board.unclaim(t); return rc; }     // (refused half way: what it enqueued ends before the slot is free)
+    p->board.launch(t);
     *ticket = t;
     return V2P_OK;
 }
@@ -3319,12 +3321,17 @@ int v2p_pipeline_reserve(v2p_pipeline* p, uint64_t stream_bytes, uint64_t out_by
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     if (copy_threads) p->copy_threads = copy_threads > 64 ? 64 : copy_threads;
-    for (PipeSlot& s : p->slots) {
-        if (s.busy || s.in_flight) return c->fail(V2P_ERR_STATE, "v2p_pipeline_reserve: a slot is in use");
-        if (stream_bytes) HIP_TRY(c, s.h_in.ensure(stream_bytes), "hipHostMalloc(in)");
-        if (out_bytes) HIP_TRY(c, s.h_out.ensure(bgzf::bound(out_bytes, 0) + 64), "hipHostMalloc(out)");   // (room for V2P_SUBMIT_BGZF's members)
-    }
-    return V2P_OK;
+    // every slot claimed while its buffers are resized: submitters find no free slot meanwhile
+    if (!p->board.claim_all()) return c->fail(V2P_ERR_STATE, "v2p_pipeline_reserve: a slot is in use");
+    const int rc = [&]() -> int {
+        for (PipeSlot& s : p->slots) {
+            if (stream_bytes) HIP_TRY(c, s.h_in.ensure(stream_bytes), "hipHostMalloc(in)");
+            if (out_bytes) HIP_TRY(c, s.h_out.ensure(bgzf::bound(out_bytes, 0) + 64), "hipHostMalloc(out)");   // (room for V2P_SUBMIT_BGZF's members)
+        }
+        return V2P_OK;
+    }();
+    p->board.unclaim_all();
+    return rc;
 }
 
 int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int kernel, unsigned flags, uint32_t* ticket)
@@ -3334,21 +3341,9 @@ int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int k
     if (kernel != 0 && kernel != 6 && kernel != 7 && kernel != 9) { std::lock_guard<std::mutex> lk(c->mu); return c->fail(V2P_ERR_INVALID_ARG, "a stream slice builds rows images (kernel 6, 7), a tile image (9) or what the routing rule picks (0)"); }
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t t;
-    {
-        std::lock_guard<std::mutex> pl(p->pmu);
-        // the first free slot from `next` on (one submitter that releases in order sees them round-robin; workers that release as they
-        // finish take whichever is free); every slot in use: V2P_BUSY, nothing staged -- wait for a ticket, release it, submit again
-        const uint32_t ns = uint32_t(p->slots.size());
-        uint32_t k = 0;
-        while (k < ns && p->slots[(p->next + k) % ns].busy) ++k;
-        if (k == ns) return V2P_BUSY;
-        t = (p->next + k) % ns;
-        p->slots[t].busy = true;                       // claimed: concurrent submitters take the slots behind it
-        p->slots[t].state = SLOT_FREE;
-        p->next = (t + 1) % ns;
-    }
+    if (!p->board.claim_first_free(&t)) return V2P_BUSY;      // every slot in use, nothing staged: wait for a ticket, release it, submit again
     PipeSlot& s = p->slots[t];
-    auto unclaim = [&](int rc) { std::lock_guard<std::mutex> pl(p->pmu); s.busy = false; return rc; };
+    auto unclaim = [&](int rc) { (void)s.drain(); p->board.unclaim(t); return rc; };      // (whatever this call enqueued ends before the slot is free)
     auto hip_unclaim = [&](hipError_t e, const char* what) { std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->hip_fail(e, what)); };
     (void)hipSetDevice(c->device);
     if (!s.d2h || !s.ev_h2d || !s.ev_exec || !s.rs || !s.batch) {               // (a slot's first stream submission)
@@ -3361,8 +3356,6 @@ int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int k
         if (!s.batch) { s.batch = new (std::nothrow) v2p_batch(); if (s.batch) { s.batch->ctx = c; s.batch->grow = true; } }
         if (!s.rs || !s.batch) { std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->fail(V2P_ERR_HIP, "out of host memory")); }
     }
-    // a result released without a wait, a submission that failed half way: the slot's streams must be idle before its buffers are rewritten
-    if (s.in_flight) { (void)hipStreamSynchronize(s.stream); (void)hipStreamSynchronize(s.d2h); s.in_flight = false; }
     if (!slice->hap_tx_begin) { std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->fail(V2P_ERR_INVALID_ARG, "null argument")); }
     const bool fasta_shape = slice->tx_header_off && slice->tx_header_len;
     const StreamLayout L = stream_layout(slice->n_haps, slice->n_tx, slice->n_tasks, fasta_shape);
@@ -3415,22 +3408,14 @@ int v2p_pipeline_submit_stream(v2p_pipeline* p, const v2p_txstream* slice, int k
     s.rc = V2P_OK; s.err.clear(); s.err_index = -1; s.is_stream = true;
     s.t_stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     // ---- H2D on the slot's stream: two copies from pinned memory, truly asynchronous ----
-    s.in_flight = true;
     hipError_t e = hipSuccess;
     if (L.total) e = hipMemcpyAsync(s.rs->buf.ptr(), s.h_in.p, L.total, hipMemcpyHostToDevice, s.stream);
     if (e == hipSuccess && slice->n_alt) e = hipMemcpyAsync(s.rs->alt.ptr(), s.h_in.p + o_alt, slice->n_alt, hipMemcpyHostToDevice, s.stream);
     if (e == hipSuccess) e = hipEventRecord(s.ev_h2d, s.stream);
     if (e != hipSuccess) return hip_unclaim(e, "H2D(stream slice)");
-    {
-        std::unique_lock<std::mutex> pl(p->pmu);
-        if (!p->runner.joinable()) {
-            try { p->runner = std::thread(pipeline_runner, p); }
-            catch (...) { pl.unlock(); std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->fail(V2P_ERR_HIP, "no thread for the pipeline's runner")); }
-        }
-        s.state = SLOT_QUEUED;
-        p->jobs.push_back(t);
-    }
-    p->cv.notify_all();
+    try { std::call_once(p->runner_started, [&] { p->runner = std::thread(pipeline_runner, p); }); }
+    catch (...) { std::lock_guard<std::mutex> lk(c->mu); return unclaim(c->fail(V2P_ERR_HIP, "no thread for the pipeline's runner")); }
+    p->board.enqueue(t);
     *ticket = t;
     return V2P_OK;
 }
@@ -3442,13 +3427,7 @@ static void pipeline_runner(v2p_pipeline* p)
     v2p_ctx* c = p->ctx;
     for (;;) {
         uint32_t t;
-        {
-            std::unique_lock<std::mutex> pl(p->pmu);
-            p->cv.wait(pl, [&] { return p->stop || !p->jobs.empty(); });
-            if (p->jobs.empty()) return;               // (stop: what is queued is still run -- its waiters are owed an answer)
-            t = p->jobs.front();
-            p->jobs.erase(p->jobs.begin());
-        }
+        if (!p->board.take(&t)) return;                // (stop: what is queued is still run -- its waiters are owed an answer)
         PipeSlot& s = p->slots[t];
         const auto t0 = std::chrono::steady_clock::now();
         int rc = V2P_OK;
@@ -3510,23 +3489,19 @@ static void pipeline_runner(v2p_pipeline* p)
                 hip(hipEventRecord(s.ev_exec, c->stream), "hipEventRecord");
                 hip(hipStreamWaitEvent(s.d2h, s.ev_exec, 0), "hipStreamWaitEvent");
                 // the way home: arena, status word, digests -- into pinned memory, on a stream of the slot's own (the next slice's H2D and its
-                // one call run beside it)
+                // one call run beside it); the result buffer was sized from the slice's tables
+                if (rc == V2P_OK && b->out_bytes != s.out_bytes) rc = c->fail(V2P_ERR_STATE, "a slice's arena is not the sum of its transcripts' result sizes");
                 if (rc == V2P_OK && zb) hip(hipMemcpyAsync(s.h_out.p + s.o_zbegin, zb, 8 * (b->n_haps + 1), hipMemcpyDeviceToHost, s.d2h), "D2H(bgzf offsets)");
                 else if (rc == V2P_OK && b->out_bytes) hip(hipMemcpyAsync(s.h_out.p, b->d_out.ptr(), b->out_bytes, hipMemcpyDeviceToHost, s.d2h), "D2H(out)");
                 if (rc == V2P_OK) hip(hipMemcpyAsync(s.h_out.p + s.o_status, b->d_status.ptr(), 8, hipMemcpyDeviceToHost, s.d2h), "D2H(status)");
                 if (rc == V2P_OK && (s.sflags & V2P_SUBMIT_DIGESTS) && b->n_haps) hip(hipMemcpyAsync(s.h_out.p + s.o_digests, b->d_digest.ptr(), b->n_haps * 8, hipMemcpyDeviceToHost, s.d2h), "D2H(digests)");
                 hip(hipEventRecord(s.done, s.d2h), "hipEventRecord");
-                if (rc == V2P_OK && b->out_bytes != s.out_bytes) rc = c->fail(V2P_ERR_STATE, "a slice's arena is not the sum of its transcripts' result sizes");
             }
             if (rc != V2P_OK) { s.err = c->err; s.err_index = c->err_index; }
         }
-        {
-            std::lock_guard<std::mutex> pl(p->pmu);
-            s.rc = rc;
-            s.t_gpu_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            s.state = rc == V2P_OK ? SLOT_LAUNCHED : SLOT_FAILED;
-        }
-        p->cv.notify_all();
+        s.rc = rc;
+        s.t_gpu_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        p->board.finish(t, rc == V2P_OK);
     }
 }
 
@@ -3535,35 +3510,31 @@ int v2p_pipeline_wait(v2p_pipeline* p, uint32_t ticket, const uint8_t** result, 
     if (!p || ticket >= p->slots.size() || !result || !n) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = p->ctx;
     PipeSlot& s = p->slots[ticket];
-    {
-        std::unique_lock<std::mutex> pl(p->pmu);
-        if (!s.busy) { pl.unlock(); std::lock_guard<std::mutex> lk(c->mu); return c->fail(V2P_ERR_STATE, "nothing submitted on this ticket"); }
-        p->cv.wait(pl, [&] { return s.state == SLOT_LAUNCHED || s.state == SLOT_FAILED; });       // (a stream slice: the runner has taken it through the one call)
-        if (s.state == SLOT_FAILED) {
-            const int rc = s.rc;
-            pl.unlock();
-            std::lock_guard<std::mutex> lk(c->mu);
-            return c->fail(rc, s.err, s.err_index);
-        }
-    }
+    const SlotState state = p->board.settled(ticket);         // (a stream slice: the runner has taken it through the one call)
+    if (state == SlotState::FREE) { std::lock_guard<std::mutex> lk(c->mu); return c->fail(V2P_ERR_STATE, "nothing submitted on this ticket"); }
+    if (state == SlotState::FAILED) { std::lock_guard<std::mutex> lk(c->mu); return c->fail(s.rc, s.err, s.err_index); }
+    const bool first = state == SlotState::LAUNCHED;          // (READY: waited for before -- the same answer again)
     // (the context is NOT held while the copies finish: submitters and the runner go on)
     (void)hipSetDevice(c->device);
-    const hipError_t e = hipEventSynchronize(s.done);
+    const hipError_t e = first ? hipEventSynchronize(s.done) : hipSuccess;
     if (e != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(e, "hipEventSynchronize"); }
     unsigned long long st;
     memcpy(&st, s.h_out.p + s.o_status, sizeof st);
     uint64_t n_res = s.out_bytes;
     if (s.is_stream && (s.sflags & V2P_SUBMIT_BGZF) && st == STATUS_CLEAN) {
-        // the members' size is known now: copy just them, on the slot's way home
-        const uint64_t* zb = reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_zbegin);
-        n_res = zb[s.n_haps];
-        hipError_t ze = n_res > s.o_status ? hipErrorInvalidValue : hipSuccess;
-        if (ze == hipSuccess && n_res) ze = hipMemcpyAsync(s.h_out.p, s.batch->d_z.ptr(), n_res, hipMemcpyDeviceToHost, s.d2h);
-        if (ze == hipSuccess) ze = hipStreamSynchronize(s.d2h);
-        if (ze != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(ze, "D2H(bgzf members)"); }
-        s.z_bytes = n_res;
+        if (first) {
+            // the members' size is known now: copy just them, on the slot's way home
+            const uint64_t* zb = reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_zbegin);
+            n_res = zb[s.n_haps];
+            hipError_t ze = n_res > s.o_status ? hipErrorInvalidValue : hipSuccess;
+            if (ze == hipSuccess && n_res) ze = hipMemcpyAsync(s.h_out.p, s.batch->d_z.ptr(), n_res, hipMemcpyDeviceToHost, s.d2h);
+            if (ze == hipSuccess) ze = hipStreamSynchronize(s.d2h);
+            if (ze != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(ze, "D2H(bgzf members)"); }
+            s.z_bytes = n_res;
+        }
+        n_res = s.z_bytes;
     }
-    s.in_flight = false;
+    if (first) p->board.ready(ticket);
     *result = s.h_out.p;
     *n = n_res;
     if (st != STATUS_CLEAN) {
@@ -3579,8 +3550,7 @@ int v2p_pipeline_result_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** 
     if (!p || ticket >= p->slots.size()) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = p->ctx;
     PipeSlot& s = p->slots[ticket];
-    std::lock_guard<std::mutex> pl(p->pmu);
-    if (!s.busy || !s.is_stream || s.state != SLOT_LAUNCHED || s.in_flight) { std::lock_guard<std::mutex> lk(c->mu); return c->fail(V2P_ERR_STATE, "v2p_pipeline_result_info: a stream slice that has been waited for"); }
+    if (p->board.peek(ticket) != SlotState::READY || !s.is_stream) { std::lock_guard<std::mutex> lk(c->mu); return c->fail(V2P_ERR_STATE, "v2p_pipeline_result_info: a stream slice that has been waited for"); }
     if (hap_out_begin) *hap_out_begin = s.hap_out_begin.data();
     if (n_haps) *n_haps = s.n_haps;
     if (digests) *digests = (s.sflags & V2P_SUBMIT_DIGESTS) ? reinterpret_cast<const uint64_t*>(s.h_out.p + s.o_digests) : nullptr;
@@ -3593,8 +3563,7 @@ int v2p_pipeline_bgzf_info(v2p_pipeline* p, uint32_t ticket, const uint64_t** ha
     if (!p || ticket >= p->slots.size()) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = p->ctx;
     PipeSlot& s = p->slots[ticket];
-    std::lock_guard<std::mutex> pl(p->pmu);
-    if (!s.busy || !s.is_stream || s.state != SLOT_LAUNCHED || s.in_flight || !(s.sflags & V2P_SUBMIT_BGZF)) {
+    if (p->board.peek(ticket) != SlotState::READY || !s.is_stream || !(s.sflags & V2P_SUBMIT_BGZF)) {
         std::lock_guard<std::mutex> lk(c->mu);
         return c->fail(V2P_ERR_STATE, "v2p_pipeline_bgzf_info: a V2P_SUBMIT_BGZF stream slice that has been waited for");
     }
@@ -3608,21 +3577,15 @@ int v2p_pipeline_release(v2p_pipeline* p, uint32_t ticket)
     if (!p || ticket >= p->slots.size()) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = p->ctx;
     PipeSlot& s = p->slots[ticket];
-    {
-        // released without a wait: a queued slice is taken through the one call first, then the copies into / out of the pinned buffers must end
-        std::unique_lock<std::mutex> pl(p->pmu);
-        if (s.busy && s.is_stream) p->cv.wait(pl, [&] { return s.state == SLOT_LAUNCHED || s.state == SLOT_FAILED; });
-    }
-    if (s.in_flight) {
+    // released without a wait: a queued slice is taken through the one call first, then the copies into / out of the pinned buffers must end
+    const SlotState state = p->board.settled(ticket);
+    if (state == SlotState::FREE) return V2P_OK;
+    if (state != SlotState::READY) {
         (void)hipSetDevice(c->device);
-        hipError_t e = hipSuccess;
-        if (s.state == SLOT_LAUNCHED) e = hipEventSynchronize(s.done);
-        else { e = hipStreamSynchronize(s.stream); if (e == hipSuccess && s.d2h) e = hipStreamSynchronize(s.d2h); }
+        const hipError_t e = state == SlotState::LAUNCHED ? hipEventSynchronize(s.done) : s.drain();
         if (e != hipSuccess) { std::lock_guard<std::mutex> lk(c->mu); return c->hip_fail(e, "hipEventSynchronize"); }
-        s.in_flight = false;
     }
-    std::lock_guard<std::mutex> pl(p->pmu);
-    s.busy = false; s.state = SLOT_FREE;
+    p->board.release(ticket);
     return V2P_OK;
 }
 
