@@ -19,9 +19,13 @@
  *   (5) grouping on the device   v2p_decode_groups produces the grouped CSR of (3) on the GPU from the id lists the decode left
  *                         there; v2p_groups_from_csr (host) wraps it, with the tables of (4), into the v2p_groups of (3).
  *
+ *   (6) steps 4a / 4b on the device   v2p_decode_tasks_count / _emit turn the grouped CSR of (5), where it lies, into a resident transcript
+ *                         stream (v2p_stream, include/vcf2prot_hip.h): nothing per haplotype crosses the link between the VCF text and
+ *                         the FASTA bytes.
+ *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
- * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4) and the v2p_decode_groups* calls of (5); libv2p_cohort.so
- * (plain C++) exports the rest.
+ * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4), the v2p_decode_groups* calls of (5) and the v2p_decode_tasks* calls of
+ * (6); libv2p_cohort.so (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -51,6 +55,7 @@ struct v2p_ctx;                                   /* include/vcf2prot_hip.h */
 #ifndef V2P_ERR_GZIP
 #define V2P_ERR_GZIP            (-28)   /* a BGZF member that does not inflate (v2p_decode_inflate, include/v2p_cohort.h)  */
 #endif
+#define V2P_ERR_TASKS           (-29)   /* an abort of step 4a / 4b (instruction.rs panics, transcript_instructions.rs:57-144,305,479,386-421) */
 
 /* ---------------------------------------------------------------------------------------------------------
  * (1) record index (host)
@@ -197,6 +202,11 @@ const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t);
 const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t);                  /* [n_consequences] identity class of drop_replicate's dedup_by, ~0u if not mut_ok */
 const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t);            /* [n_consequences + 1] CSR of ... */
 const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t);                  /* ... the OTHER transcript ranks whose id occurs in the text, ascending */
+/* the amino-acid strings of every mut_ok consequence (what v2p_groups_mutation_view hands out), for readers that do not see the VCF text:
+ * ref_aa = aa[aa_begin[i], + aa_ref_len[i]), mut_aa = the rest up to aa_begin[i + 1]; both empty where the consequence is not mut_ok */
+const uint8_t*  v2p_csq_tables_aa(const v2p_csq_tables* t);                     /* [aa_begin[n_consequences]] */
+const uint64_t* v2p_csq_tables_aa_begin(const v2p_csq_tables* t);               /* [n_consequences + 1] */
+const uint32_t* v2p_csq_tables_aa_ref_len(const v2p_csq_tables* t);             /* [n_consequences] */
 
 /* The three tables read off the grouped CSR of a successful v2p_groups_build over 2 * n_samples lists.  per_proband[n_samples],
  * per_type[22 * n_samples], per_transcript[v2p_groups_n_transcripts]. */
@@ -240,7 +250,12 @@ int  v2p_decode_stats_timing(const v2p_decode* d, float* ms_upload, float* ms_ke
  *
  * Policy of the callers in this repository (v2p_harness vcf, pipeline.vcf_to_fasta): the tables are built once per file; the CSR comes
  * from v2p_decode_groups and the ids stay on the device.  Only if a list was refused are the ids downloaded, and then the WHOLE file
- * goes through v2p_groups_build_from_tables, the host path on the same tables.
+ * goes through v2p_groups_build_from_tables, the host path on the same tables.  Steps 4a / 4b run on the host from the downloaded CSR
+ * unless the caller opts into (6) (pipeline.vcf_to_fasta(device_tasks=True), --device-tasks), which needs the CSR of the device path.
+ * With (6) the callers count once, cut proband ranges of about slice_bytes of arena from the per-haplotype sizes and, range after range, emit,
+ * build and execute with kernel 0 and read the text back.  The host loop takes the WHOLE file when the grouping fell back to the host or the
+ * host builder was asked for; a single range whose one-call build returns V2P_ERR_UNSUPPORTED is downloaded (v2p_stream_download) and goes
+ * through the host builder alone, the other ranges stay on the device.
  * ------------------------------------------------------------------------------------------------------- */
 
 /* (3)'s per-haplotype phase on tables that already exist: v2p_groups_build = v2p_csq_tables_build + this.  The tables are not
@@ -287,6 +302,49 @@ int  v2p_decode_groups_refused(const v2p_decode* d, uint64_t* lists);
 /* milliseconds of the last v2p_decode_groups / _download on d (HIP events): the upload of the tables (0 when the decode held them),
  * the count launch, the scan, the emit launch, the download of the CSR */
 int  v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (6) steps 4a and 4b on the device: the grouped CSR of the last successful v2p_decode_groups on d becomes the transcript stream that
+ * include/v2p_step4a.h + v2p_step4b.h would have made of it on the host and v2p_stream_upload would have made resident.  A work item is one
+ * output transcript of one haplotype: a group of the CSR, or with a slot list (-a / --write_all_proteins) one (haplotype, slot).
+ *
+ * A transcript is left out where the reference skips it: not in the reference FASTA (tx_proteome_off < 0), V2P_4A_SKIP, V2P_4B_MUST_BE_LAST;
+ * with a slot list the latter two, and a slot without a group, are one code-0 Task of the whole reference.  Where the reference aborts
+ * (V2P_4A_PANIC, V2P_4B_UNSUPPORTED / _ARITHMETIC, INSPECT_TXP with V2P_4A_INSPECT_INS_GEN) the count returns V2P_ERR_TASKS with
+ * v2p_last_error_index(ctx) = the smallest aborting haplotype list and v2p_last_error(ctx) = "instruction generation for transcript X",
+ * "task generation for transcript X (rc)" or "size mismatched / non-contiguous tasks in transcript X", X the first such transcript of that
+ * list in stream order.  Stream fields narrow to 32 bits as the host's stream narrows them.
+ * ------------------------------------------------------------------------------------------------------- */
+struct v2p_stream;                                /* include/vcf2prot_hip.h */
+
+typedef struct v2p_tasks_info {
+    uint64_t n_items;                             /* lanes of the count launch */
+    uint64_t n_tx, n_tasks, n_alt, out_bytes;     /* the whole file's stream (zeros on an abort) */
+} v2p_tasks_info;
+
+/* The count launch and its scans.  Host pointers.  aa / aa_begin / aa_ref_len: the v2p_csq_tables_aa* columns of the tables the CSR was made
+ * from (n_consequences of them); uploaded once and kept on d, as the tables of (5) are.  The per-transcript arrays have one entry per
+ * transcript rank (n_transcripts), or per slot (n_slots) when slot_rank is given: where the transcript's reference lies in the resident
+ * proteome (negative: the reference FASTA does not have it), its length, the header-table offsets of its record headers for the first and
+ * the second haplotype of a proband and their common length (v2p_upload_reference comes first: they are checked against it).  slot_rank
+ * [n_slots]: the sorted union of the reference's and the file's transcript names, each slot's rank in the file or ~0u; NULL, 0 without -a.
+ * tx_text / tx_begin / tx_len name the ranks in error messages (may be NULL).  flags: V2P_4A_INSPECT_INS_GEN | V2P_4A_PANIC_INSPECT_ERR.
+ * hap_tx / hap_tasks / hap_alt / hap_bytes [2 * n_samples]: transcripts, Tasks, alt bytes and arena (FASTA) bytes of every haplotype list --
+ * a caller cuts its slices from these before anything is emitted.  V2P_ERR_STATE unless d holds the CSR of a successful v2p_decode_groups. */
+int  v2p_decode_tasks_count(struct v2p_ctx* ctx, v2p_decode* d,
+                            const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len, uint64_t n_consequences,
+                            const int64_t* tx_proteome_off, const uint32_t* tx_ref_len, const uint64_t* tx_header_off_1, const uint64_t* tx_header_off_2,
+                            const uint32_t* tx_header_len, uint64_t n_transcripts, const uint32_t* slot_rank, uint64_t n_slots,
+                            const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len, uint32_t flags,
+                            uint64_t* hap_tx, uint64_t* hap_tasks, uint64_t* hap_alt, uint64_t* hap_bytes, v2p_tasks_info* info);
+/* The emit launch: haplotype lists [h0, h1) of the last successful v2p_decode_tasks_count on d as a resident stream of their own (h0 == h1:
+ * a stream without haplotypes).  The stream owns its memory: it survives v2p_decode_destroy, batches attach to it and are orphaned by
+ * v2p_stream_destroy exactly as with an uploaded stream, and v2p_batch_build_and_execute routes it as it routes its uploaded twin (the
+ * same sample of transcripts is taken on the device). */
+int  v2p_decode_tasks_emit(struct v2p_ctx* ctx, v2p_decode* d, uint64_t h0, uint64_t h1, struct v2p_stream** out);
+/* milliseconds of the last v2p_decode_tasks_count / _emit on d (HIP events): the upload of the amino-acid and per-transcript tables (0 when
+ * the decode held them), the count launch, the scans, the last emit (launch, routing sample, tile tables) */
+int  v2p_decode_tasks_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

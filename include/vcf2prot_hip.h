@@ -277,6 +277,11 @@ int  v2p_stream_upload(v2p_ctx* ctx, const v2p_txstream* s, v2p_stream** out);
  * consumes its tapes, gir.rs:197,230-234.) */
 void v2p_stream_destroy(v2p_stream* s);
 int  v2p_stream_counts(const v2p_stream* s, uint64_t* n_haps, uint64_t* n_tx, uint64_t* n_tasks, uint64_t* out_bytes);
+/* A resident stream's arrays back in host memory (tests and tools; a stream made by v2p_decode_tasks_emit, include/v2p_frontend.h, has never
+ * been there).  With host->hap_tx_begin NULL the four counts of *host are filled in and nothing is copied.  Otherwise the counts must be the
+ * stream's and every pointer of *host names a WRITABLE array of the size v2p_txstream gives it (the offset arrays with their closing entry, no
+ * slack needed); tx_header_off / tx_header_len may both be NULL. */
+int  v2p_stream_download(const v2p_stream* s, v2p_txstream* host);
 /* the one-piece builder on a resident stream, no H2D: kernel 6 / 7 (rows images), 9 (a TILE image, see v2p_batch_build_and_execute), 0: by the
  * routing rule -- a wave image from 24 result bytes per Task, below a tile image where the form takes the stream, else a dense rows image */
 int  v2p_batch_build_from_stream(v2p_batch* b, const v2p_stream* s, int kernel, float* build_ms);

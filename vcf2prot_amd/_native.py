@@ -66,6 +66,7 @@ HIP_API = {
     "v2p_batch_download_image": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_stream_upload": (c_int, [c_void_p, c_void_p, POINTER(c_void_p)]),
     "v2p_stream_destroy": (None, [c_void_p]),
+    "v2p_stream_download": (c_int, [c_void_p, c_void_p]),
     "v2p_stream_counts": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_batch_build_from_stream": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_float)]),
     "v2p_batch_build_and_execute": (c_int, [c_void_p, c_void_p, c_int, c_uint32]),

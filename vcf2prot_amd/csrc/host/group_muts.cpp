@@ -109,6 +109,9 @@ struct Table {
     std::vector<uint32_t> rank;                  // own transcript rank, ~0u if split failed
     std::vector<uint32_t> ident;                 // identity class of drop_replicate's dedup_by (vcf_ds.rs:399-406)
     std::vector<uint32_t> extra_begin, extra;    // other transcript ranks whose id occurs in the consequence text
+    std::vector<uint8_t> aa;                     // ref_aa then mut_aa of every mut_ok consequence, back to back
+    std::vector<uint64_t> aa_begin;              // [n_csq + 1] where a consequence's two strings begin in aa
+    std::vector<uint32_t> aa_ref_len;            // [n_csq] bytes of ref_aa; the rest up to aa_begin[i + 1] is mut_aa
     std::vector<std::string_view> names;
 };
 
@@ -166,6 +169,17 @@ void build_tables(Table& T, const v2p_vcf_index* x, const uint8_t* text_u8, uint
     T.flags.assign(n_csq, 0u);
     T.mut_pos.assign(n_csq, 0);
     T.ref_pos.assign(n_csq, 0);
+    T.aa_begin.assign(n_csq + 1, 0);
+    T.aa_ref_len.assign(n_csq, 0);
+    for (uint64_t i = 0; i < n_csq; ++i) {       // the strings v2p_groups_mutation_view hands out, for readers that do not see the text
+        const Parsed& p = T.parsed[i];
+        T.aa_begin[i] = T.aa.size();
+        if (!p.mut_ok) continue;
+        T.aa_ref_len[i] = uint32_t(p.ref_aa.size());
+        T.aa.insert(T.aa.end(), p.ref_aa.begin(), p.ref_aa.end());
+        T.aa.insert(T.aa.end(), p.mut_aa.begin(), p.mut_aa.end());
+    }
+    T.aa_begin[n_csq] = T.aa.size();
     {
         std::unordered_map<std::string, uint32_t> classes;
         std::string key;
@@ -394,6 +408,9 @@ const uint16_t* v2p_csq_tables_ref_pos(const v2p_csq_tables* t) { return t ? t->
 const uint32_t* v2p_csq_tables_ident(const v2p_csq_tables* t) { return t ? t->T.ident.data() : nullptr; }
 const uint32_t* v2p_csq_tables_extra_begin(const v2p_csq_tables* t) { return t ? t->T.extra_begin.data() : nullptr; }
 const uint32_t* v2p_csq_tables_extra(const v2p_csq_tables* t) { return t ? t->T.extra.data() : nullptr; }
+const uint8_t* v2p_csq_tables_aa(const v2p_csq_tables* t) { return t ? t->T.aa.data() : nullptr; }
+const uint64_t* v2p_csq_tables_aa_begin(const v2p_csq_tables* t) { return t ? t->T.aa_begin.data() : nullptr; }
+const uint32_t* v2p_csq_tables_aa_ref_len(const v2p_csq_tables* t) { return t ? t->T.aa_ref_len.data() : nullptr; }
 
 int v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text_u8, const uint64_t* hap_begin, const uint32_t* ids,
                      uint64_t n_haps, uint32_t n_threads, v2p_groups** out)

@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            the per-transcript grouping comes from the GPU (v2p_decode_groups); --host-groups, or a list the kernel
 //                                            refuses, sends the whole file through the host grouping on the same tables -- same bytes;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
@@ -362,7 +362,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -487,7 +487,12 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         }
         if (rc != V2P_OK || ginfo.n_refused) device_groups = false;
     }
-    if (device_groups) {
+    // --device-tasks: steps 4a / 4b run on the CSR where the grouping kernel left it (include/v2p_frontend.h part 6); it is not downloaded,
+    // and the decode and the tables live until the last slice is emitted.  A grouping that fell back to the host (a refused list,
+    // --host-groups) and --host-build take the host loop below: same bytes.
+    const bool tasks_on_device = device_tasks && device_groups && !host_build && !(stats && sinfo.n_refused);     // (refused statistics are read off the host's groups)
+    if (tasks_on_device) {
+    } else if (device_groups) {
         std::vector<uint64_t> c_hgb(2 * S + 1), c_gmb(ginfo.n_groups + 1);
         std::vector<uint32_t> c_gtx(ginfo.n_groups + 1), c_mid(ginfo.n_members + 1);
         if (v2p_decode_groups_download(dec, c_hgb.data(), c_gtx.data(), c_gmb.data(), c_mid.data()) != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
@@ -504,8 +509,10 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         }
     }
     v2p_decode_groups_timing(dec, &gms[0], &gms[1], &gms[2], &gms[3], &gms[4]);
-    v2p_decode_destroy(dec);
-    v2p_csq_tables_destroy(tb);
+    if (!tasks_on_device) {
+        v2p_decode_destroy(dec);
+        v2p_csq_tables_destroy(tb);
+    }
     t_group = t_tables + since(t0); t0 = clk::now();     // the file-wide tables and the per-haplotype phase, as v2p_groups_build had them
     if (stats) {
         const auto ts = clk::now();
@@ -522,7 +529,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         t0 = clk::now();
     }
     // resident reference: the transcripts the file touches + their two record headers
-    const uint64_t n_tx = v2p_groups_n_transcripts(g);
+    const uint64_t n_tx = tasks_on_device ? T : v2p_groups_n_transcripts(g);
     std::vector<std::string> names(n_tx);
     std::vector<int64_t> tx_off(n_tx, -1);
     std::vector<uint64_t> tx_len(n_tx, 0), hdr_off(2 * n_tx, 0);
@@ -531,7 +538,8 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     std::map<std::string, RefTx> all;                              // -a: every transcript of the reference, sorted like the groups
     for (uint64_t r = 0; r < n_tx; ++r) {
         uint64_t b, n;
-        v2p_groups_transcript(g, r, &b, &n);
+        if (tasks_on_device) v2p_csq_tables_transcript(tb, r, &b, &n);
+        else v2p_groups_transcript(g, r, &b, &n);
         names[r] = vcf.substr(b, n);
     }
     auto place = [&](const std::string& name, const std::string& seq, int64_t rank) {
@@ -661,6 +669,103 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         batch_result(chk, fb, st.n_haps, bgzf, bytes, hob);
         v2p_batch_destroy(fb);
     };
+    uint64_t n_slices = 0, n_fallback = 0;
+    // the two lines every run ends with; tasks_json says where steps 4a / 4b ran
+    auto report = [&](const std::string& tasks_json) {
+        char stats_seconds[48] = "";
+        if (stats) std::snprintf(stats_seconds, sizeof(stats_seconds), ", \"stats\": %.4f", t_stats);
+        char tables_seconds[48];
+        std::snprintf(tables_seconds, sizeof(tables_seconds), ", \"tables\": %.4f", t_tables);
+        std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
+                    (unsigned long long)written, outdir);
+        std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
+                    "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f%s%s}, "
+                    "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}, \"input_format\": \"%s\", "
+                    "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}",
+                    (unsigned long long)R, (unsigned long long)S, (unsigned long long)written, (unsigned long long)n_slices, (unsigned long long)n_fallback,
+                    t_read, t_index, t_decode, t_group, t_build, t_exec, t_write,
+                    since(t_start), t_inflate, stats_seconds, tables_seconds, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
+        if (stats)
+            std::printf(", \"stats_ms\": {\"upload\": %.3f, \"kernel\": %.3f, \"refused_lists\": %llu, \"sorted_members\": %llu, \"lds_bytes\": %u}",
+                        sms[0], sms[1], (unsigned long long)sinfo.n_refused, (unsigned long long)sinfo.n_sorted_members, sinfo.lds_bytes);
+        std::printf(", \"groups\": {\"path\": \"%s\", \"n_refused\": %llu, \"key_capacity\": %u, \"lds_bytes\": %u, \"ms_upload\": %.3f, \"ms_count\": %.3f, "
+                    "\"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f}", device_groups ? "device" : "host", (unsigned long long)ginfo.n_refused,
+                    ginfo.key_capacity, ginfo.lds_bytes, gms[0], gms[1], gms[2], gms[3], gms[4]);
+        std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
+    };
+    if (tasks_on_device) {
+        // ---- steps 4a / 4b on the device: count, cut proband ranges of about slice_bytes of arena from the per-haplotype sizes, then per
+        // range emit -> v2p_batch_build_and_execute -> download (or BGZF) -> write, one range after the other.  A range the one call refuses
+        // (V2P_ERR_UNSUPPORTED) is downloaded as a stream and goes through the host builder, like a refused slice of the host loop. ----
+        std::vector<int64_t> e_off; std::vector<uint32_t> e_len, e_hlen, e_rank; std::vector<uint64_t> e_h1, e_h2;
+        auto entry = [&](int64_t off, uint64_t len, uint64_t h1, uint64_t h2, size_t name_len, int64_t rank) {
+            e_off.push_back(off); e_len.push_back(uint32_t(len)); e_h1.push_back(h1); e_h2.push_back(h2); e_hlen.push_back(uint32_t(name_len + 4));
+            e_rank.push_back(rank < 0 ? ~0u : uint32_t(rank));
+        };
+        if (write_all) for (const auto& kv : all) entry(int64_t(kv.second.off), kv.second.len, kv.second.hdr[0], kv.second.hdr[1], kv.first.size(), kv.second.rank);
+        else for (uint64_t r = 0; r < n_tx; ++r) entry(tx_off[r], tx_len[r], hdr_off[2 * r], hdr_off[2 * r + 1], names[r].size(), int64_t(r));
+        const uint32_t flags = no_test ? 0u : (V2P_4A_INSPECT_INS_GEN | V2P_4A_PANIC_INSPECT_ERR);     // cli.rs:275-368
+        if (const char* e = std::getenv("V2P_TASKS_SLICE_BYTES")) slice_bytes = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+        std::vector<uint64_t> h_tx(2 * S), h_tasks(2 * S), h_alt(2 * S), h_bytes(2 * S);
+        v2p_tasks_info tinfo{};
+        const auto tc = clk::now();
+        const int crc = v2p_decode_tasks_count(ctx.raw(), dec, v2p_csq_tables_aa(tb), v2p_csq_tables_aa_begin(tb), v2p_csq_tables_aa_ref_len(tb),
+                                               v2p_csq_tables_n_consequences(tb), e_off.data(), e_len.data(), e_h1.data(), e_h2.data(), e_hlen.data(), T,
+                                               write_all ? e_rank.data() : nullptr, write_all ? e_rank.size() : 0, text, v2p_csq_tables_transcript_begin(tb),
+                                               v2p_csq_tables_transcript_len(tb), flags, h_tx.data(), h_tasks.data(), h_alt.data(), h_bytes.data(), &tinfo);
+        if (crc != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); return 101; }
+        const double t_count = since(tc);
+        double t_emit = 0, t_run = 0, t_back = 0;
+        std::vector<uint8_t> bytes; std::vector<uint64_t> hob;
+        uint64_t s0 = 0, acc = 0;
+        for (uint64_t sm = 0; sm < S; ++sm) {
+            acc += h_bytes[2 * sm] + h_bytes[2 * sm + 1];
+            if (acc < slice_bytes && sm + 1 != S) continue;
+            auto te = clk::now();
+            v2p_stream* rs = nullptr;
+            chk(v2p_decode_tasks_emit(ctx.raw(), dec, 2 * s0, 2 * sm + 2, &rs));
+            t_emit += since(te); te = clk::now();
+            int rc = v2p_batch_build_and_execute(b, rs, 0, 0);
+            if (rc == V2P_OK) rc = v2p_batch_sync(b);
+            t_run += since(te); te = clk::now();
+            if (rc == V2P_ERR_UNSUPPORTED) {
+                TxStreamHost tx;
+                v2p_txstream st{};
+                chk(v2p_stream_download(rs, &st));
+                tx.hap_tx_begin.assign(st.n_haps + 1, 0); tx.off.assign(st.n_tx, 0); tx.ref_len.assign(st.n_tx, 0); tx.res_len.assign(st.n_tx, 0);
+                tx.task_begin.assign(st.n_tx + 1, 0); tx.alt_begin.assign(st.n_tx + 1, 0); tx.hdr_off.assign(st.n_tx, 0); tx.hdr_len.assign(st.n_tx, 0);
+                tx.code.assign(st.n_tasks + 64, 0); tx.sp.assign(st.n_tasks + 64, 0); tx.ln.assign(st.n_tasks + 64, 0); tx.sr.assign(st.n_tasks + 64, 0);
+                tx.alt.assign(st.n_alt + 64, 0); tx.padded = true;
+                st = tx.view();
+                chk(v2p_stream_download(rs, &st));
+                blocking_slice(tx, bytes, hob);
+                ++n_fallback;
+            } else {
+                chk(rc);
+                batch_result(chk, b, 2 * (sm + 1 - s0), bgzf, bytes, hob);
+            }
+            t_back += since(te);
+            if (!write_probands(s0, sm + 1, bytes.data(), hob.data())) return 101;
+            chk(v2p_batch_reset(b));
+            v2p_stream_destroy(rs);
+            ++n_slices; s0 = sm + 1; acc = 0;
+        }
+        float tms[4] = {0, 0, 0, 0};
+        v2p_decode_tasks_timing(dec, &tms[0], &tms[1], &tms[2], &tms[3]);
+        v2p_decode_destroy(dec);
+        v2p_csq_tables_destroy(tb);
+        t_build = t_count + t_emit; t_exec = t_run; t_write = t_back + t_write_acc;
+        char tj[512];
+        std::snprintf(tj, sizeof tj, "{\"path\": \"device\", \"items\": %llu, \"transcripts\": %llu, \"tasks\": %llu, \"alt_bytes\": %llu, \"slice_bytes\": %llu, "
+                      "\"seconds\": {\"count\": %.4f, \"emit\": %.4f, \"build_execute\": %.4f, \"d2h\": %.4f}, "
+                      "\"ms_upload\": %.3f, \"ms_count\": %.3f, \"ms_scan\": %.3f, \"ms_emit_last\": %.3f}",
+                      (unsigned long long)tinfo.n_items, (unsigned long long)tinfo.n_tx, (unsigned long long)tinfo.n_tasks, (unsigned long long)tinfo.n_alt,
+                      (unsigned long long)slice_bytes, t_count, t_emit, t_run, t_back, tms[0], tms[1], tms[2], tms[3]);
+        report(tj);
+        v2p_batch_destroy(b);
+        v2p_vcf_index_destroy(idx);
+        return 0;
+    }
     // ---- the pipeline ----
     constexpr uint32_t SLOTS = 3;
     v2p_pipeline* pipe = nullptr;
@@ -670,7 +775,6 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     struct PipeGuard { v2p_pipeline*& p; ~PipeGuard() { if (p) { v2p_pipeline_destroy(p); p = nullptr; } } } pipe_guard{pipe};
     struct Job { uint32_t ticket; uint64_t s0, s1; std::unique_ptr<TxStreamHost> tx; };
     std::vector<Job> inflight;
-    uint64_t n_slices = 0, n_fallback = 0;
     auto finish = [&](Job& j) -> bool {
         const uint8_t* bytes = nullptr; uint64_t n = 0, nh = 0;
         const uint64_t* hob = nullptr;
@@ -787,26 +891,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         t_exec = since(t0) - (t_write_acc - w0); t0 = clk::now();
     }
     t_write = host_build ? since(t0) : t_write_acc;
-    char stats_seconds[48] = "";
-    if (stats) std::snprintf(stats_seconds, sizeof(stats_seconds), ", \"stats\": %.4f", t_stats);
-    char tables_seconds[48];
-    std::snprintf(tables_seconds, sizeof(tables_seconds), ", \"tables\": %.4f", t_tables);
-    std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
-                (unsigned long long)written, outdir);
-    std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
-                "\"decode_incl_h2d\": %.4f, \"grouping\": %.4f, \"steps_4a_4b_5\": %.4f, \"h2d_step6_sync\": %.4f, \"d2h_write\": %.4f, \"total\": %.4f, \"inflate\": %.4f%s%s}, "
-                "\"decode_kernels_ms\": {\"parse\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f}, \"input_format\": \"%s\", "
-                "\"inflate_ms\": {\"h2d\": %.3f, \"kernel\": %.3f, \"d2h\": %.3f}",
-                (unsigned long long)R, (unsigned long long)S, (unsigned long long)written, (unsigned long long)n_slices, (unsigned long long)n_fallback,
-                t_read, t_index, t_decode, t_group, t_build, t_exec, t_write,
-                since(t_start), t_inflate, stats_seconds, tables_seconds, kms[0], kms[1], kms[2], kms[3], input_format, ims[0], ims[1], ims[2]);
-    if (stats)
-        std::printf(", \"stats_ms\": {\"upload\": %.3f, \"kernel\": %.3f, \"refused_lists\": %llu, \"sorted_members\": %llu, \"lds_bytes\": %u}",
-                    sms[0], sms[1], (unsigned long long)sinfo.n_refused, (unsigned long long)sinfo.n_sorted_members, sinfo.lds_bytes);
-    std::printf(", \"groups\": {\"path\": \"%s\", \"n_refused\": %llu, \"key_capacity\": %u, \"lds_bytes\": %u, \"ms_upload\": %.3f, \"ms_count\": %.3f, "
-                "\"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f}", device_groups ? "device" : "host", (unsigned long long)ginfo.n_refused,
-                ginfo.key_capacity, ginfo.lds_bytes, gms[0], gms[1], gms[2], gms[3], gms[4]);
-    std::printf("}\n");
+    report("{\"path\": \"host\"}");
     v2p_batch_destroy(b);
     v2p_groups_destroy(g);
     v2p_vcf_index_destroy(idx);
@@ -909,20 +994,21 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
             no_test |= !std::strcmp(argv[i], "--no-test");
             host_build |= !std::strcmp(argv[i], "--host-build");
             host_groups |= !std::strcmp(argv[i], "--host-groups");
+            device_tasks |= !std::strcmp(argv[i], "--device-tasks");
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

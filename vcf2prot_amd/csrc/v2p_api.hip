@@ -2049,6 +2049,37 @@ static void stream_attach(v2p_batch* b, const v2p_stream* st)
 static int rows_mode_for(const v2p_stream* st, int kernel);
 static int build_tiles(v2p_batch* b, const v2p_stream* st, bool execute, bool* fallback, float* build_ms, uint32_t n_slices = 1);
 
+// res_counter per tile and per haplotype of a stream whose arrays, hap_out_begin and routing statistics are in place: the tile tables of the
+// image kind a call with kernel = 0 builds (a call that asks for the other kind makes its own), enqueued on the context's stream
+static int stream_tile_tables(v2p_ctx* c, v2p_stream* st)
+{
+    int rc = V2P_OK;
+    st->out_bytes = st->hap_out_begin.back();
+    const uint32_t K = rows_pick_k(st->v, rows_mode_for(st, 0));
+    const uint64_t n_tiles = st->v.n_tx ? (st->v.n_tx + K - 1) / K : 1;
+    auto up8 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+    const uint64_t o_tbytes = 0, o_tbase = up8(n_tiles * 8), o_hap = o_tbase + up8((n_tiles + 1) * 8), o_scan = o_hap + up8((st->v.n_haps + 1) * 8),
+                   o_end = o_scan + up8(rows_scan_scratch_entries(n_tiles) * 8);
+    if (st->tiles.ensure_exact(o_end) != hipSuccess) { (void)hipGetLastError(); }    // (no room: the calls make their own tables)
+    else {
+        RowsArgs a;
+        rows_args_of(st->v, c, K, n_tiles, a);
+        uint8_t* const d = st->tiles.ptr();
+        a.tile_bytes = reinterpret_cast<uint64_t*>(d + o_tbytes); a.tile_res_base = reinterpret_cast<uint64_t*>(d + o_tbase);
+        a.hap_out_begin = reinterpret_cast<uint64_t*>(d + o_hap);
+        a.status = nullptr;                                    // (a tile of more than 2 GiB is found again, and reported, by the parse)
+        hipError_t e = launch_rows_tile_bytes(a, reinterpret_cast<uint64_t*>(d + o_scan), c->stream);
+        if (e == hipSuccess) e = launch_rows_hap_begin(a, c->stream);
+        if (e != hipSuccess) rc = c->hip_fail(e, "launch(tile tables)");
+        else {
+            st->tile_K = K; st->n_tiles = n_tiles; st->tile_res_base = a.tile_res_base; st->d_hap_out_begin = a.hap_out_begin;
+            st->h_tile_res_base.assign(n_tiles + 1, 0);
+            if (hipMemcpyAsync(st->h_tile_res_base.data(), a.tile_res_base, (n_tiles + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { (void)hipGetLastError(); st->h_tile_res_base.clear(); }
+        }
+    }
+    return rc;
+}
+
 int v2p_stream_upload(v2p_ctx* c, const v2p_txstream* s, v2p_stream** out)
 {
     if (!c || !s || !out) return V2P_ERR_INVALID_ARG;
@@ -2082,32 +2113,7 @@ int v2p_stream_upload(v2p_ctx* c, const v2p_txstream* s, v2p_stream** out)
         if (crc != V2P_OK) rc = c->fail(crc, cerr.msg, cerr.index);                    // (the check's verdict first: it is what the caller can act on)
         else if (rc == V2P_OK) stream_item_stats(s, st->v);
     }
-    if (rc == V2P_OK) {
-        // the tile tables of the image kind a call with kernel = 0 builds (a call that asks for the other kind makes its own)
-        st->out_bytes = st->hap_out_begin.back();
-        const uint32_t K = rows_pick_k(st->v, rows_mode_for(st, 0));
-        const uint64_t n_tiles = st->v.n_tx ? (st->v.n_tx + K - 1) / K : 1;
-        auto up8 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
-        const uint64_t o_tbytes = 0, o_tbase = up8(n_tiles * 8), o_hap = o_tbase + up8((n_tiles + 1) * 8), o_scan = o_hap + up8((st->v.n_haps + 1) * 8),
-                       o_end = o_scan + up8(rows_scan_scratch_entries(n_tiles) * 8);
-        if (st->tiles.ensure_exact(o_end) != hipSuccess) { (void)hipGetLastError(); }    // (no room: the calls make their own tables)
-        else {
-            RowsArgs a;
-            rows_args_of(st->v, c, K, n_tiles, a);
-            uint8_t* const d = st->tiles.ptr();
-            a.tile_bytes = reinterpret_cast<uint64_t*>(d + o_tbytes); a.tile_res_base = reinterpret_cast<uint64_t*>(d + o_tbase);
-            a.hap_out_begin = reinterpret_cast<uint64_t*>(d + o_hap);
-            a.status = nullptr;                                    // (a tile of more than 2 GiB is found again, and reported, by the parse)
-            hipError_t e = launch_rows_tile_bytes(a, reinterpret_cast<uint64_t*>(d + o_scan), c->stream);
-            if (e == hipSuccess) e = launch_rows_hap_begin(a, c->stream);
-            if (e != hipSuccess) rc = c->hip_fail(e, "launch(tile tables)");
-            else {
-                st->tile_K = K; st->n_tiles = n_tiles; st->tile_res_base = a.tile_res_base; st->d_hap_out_begin = a.hap_out_begin;
-                st->h_tile_res_base.assign(n_tiles + 1, 0);
-                if (hipMemcpyAsync(st->h_tile_res_base.data(), a.tile_res_base, (n_tiles + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { (void)hipGetLastError(); st->h_tile_res_base.clear(); }
-            }
-        }
-    }
+    if (rc == V2P_OK) rc = stream_tile_tables(c, st);
     if (rc == V2P_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = c->fail(V2P_ERR_HIP, "hipStreamSynchronize");
     if (rc != V2P_OK) { st->buf.release(); st->alt.release(); st->tiles.release(); delete st; return rc; }
     *out = st;
@@ -2135,6 +2141,88 @@ int v2p_stream_counts(const v2p_stream* st, uint64_t* n_haps, uint64_t* n_tx, ui
     if (n_tx) *n_tx = st->v.n_tx;
     if (n_tasks) *n_tasks = st->v.n_tasks;
     if (out_bytes) *out_bytes = st->out_bytes;
+    return V2P_OK;
+}
+
+// ---- a resident stream born on the device (v2p_ctx_internal.h): the arrays are a kernel's to write -----------------------------
+}  // extern "C"
+namespace v2p {
+int stream_born_alloc(v2p_ctx* c, uint64_t n_haps, uint64_t n_tx, uint64_t n_tasks, uint64_t n_alt, v2p_stream** out, StreamArrays* arrays)
+{
+    *out = nullptr;
+    v2p_stream* st = new (std::nothrow) v2p_stream();
+    if (!st) return c->fail(V2P_ERR_HIP, "out of host memory");
+    st->ctx = c;
+    const StreamLayout L = stream_layout(n_haps, n_tx, n_tasks, true);
+    hipError_t e = st->buf.ensure(L.total);
+    if (e == hipSuccess) e = st->alt.ensure(n_alt);
+    if (e == hipSuccess) e = hipMemsetAsync(st->buf.ptr(), 0, L.total, c->stream);
+    if (e == hipSuccess && n_alt) e = hipMemsetAsync(st->alt.ptr(), 0, n_alt, c->stream);
+    if (e != hipSuccess) { st->buf.release(); st->alt.release(); delete st; return c->hip_fail(e, "hipMalloc(stream)"); }
+    v2p_txstream shape{};
+    shape.n_haps = n_haps; shape.n_tx = n_tx; shape.n_tasks = n_tasks; shape.n_alt = n_alt;
+    stream_view(&shape, L, true, st->buf.ptr(), st->alt.ptr(), st->v);
+    uint8_t* const d = st->buf.ptr();
+    auto u64 = [&](uint64_t o) { return reinterpret_cast<unsigned long long*>(d + o); };
+    auto u32 = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(d + o); };
+    *arrays = StreamArrays{u64(L.o_hap), u64(L.o_poff), u32(L.o_rlen), u32(L.o_res), u64(L.o_tb), u64(L.o_ab), d + L.o_code, u32(L.o_sp), u32(L.o_ln), u32(L.o_sr),
+                           st->alt.ptr(), u64(L.o_hoff), u32(L.o_hlen)};
+    *out = st;
+    return V2P_OK;
+}
+
+int stream_born_finish(v2p_ctx* c, v2p_stream* st, const uint64_t* hap_out_begin, const double* stats)
+{
+    st->hap_out_begin.assign(hap_out_begin, hap_out_begin + st->v.n_haps + 1);
+    st->v.items_mean = stats[0]; st->v.items_var = stats[1]; st->v.desc_mean = stats[2]; st->v.desc_var = stats[3]; st->v.len_mean = stats[4]; st->v.len_var = stats[5];
+    int rc = stream_tile_tables(c, st);
+    if (rc == V2P_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = c->fail(V2P_ERR_HIP, "hipStreamSynchronize");
+    return rc;
+}
+
+void stream_born_drop(v2p_stream* st)
+{
+    if (!st) return;
+    (void)hipStreamSynchronize(st->ctx->stream);
+    st->buf.release(); st->alt.release(); st->tiles.release();
+    delete st;
+}
+
+int ctx_check_transcript(v2p_ctx* c, uint64_t proteome_off, uint32_t ref_len, uint64_t header_off, uint32_t header_len, std::string* why)
+{
+    if (proteome_off + ref_len > c->proteome_len || proteome_off + ref_len < proteome_off) { *why = "transcript outside the resident proteome"; return V2P_ERR_SRC_OOB; }
+    if (header_len && (header_off + header_len > c->headers_len || header_off + header_len < header_off)) { *why = "record header outside the resident header table"; return V2P_ERR_SRC_OOB; }
+    if (header_len && c->headers_host[header_off + header_len - 1] != '\n') { *why = "a record header must end in a line feed"; return V2P_ERR_INVALID_ARG; }
+    return V2P_OK;
+}
+}  // namespace v2p
+extern "C" {
+
+int v2p_stream_download(const v2p_stream* st, v2p_txstream* host)
+{
+    if (!st || !host) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = st->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const DevStreamView& v = st->v;
+    if (!host->hap_tx_begin) { host->n_haps = v.n_haps; host->n_tx = v.n_tx; host->n_tasks = v.n_tasks; host->n_alt = v.n_alt; return V2P_OK; }
+    if (host->n_haps != v.n_haps || host->n_tx != v.n_tx || host->n_tasks != v.n_tasks || host->n_alt != v.n_alt)
+        return c->fail(V2P_ERR_INVALID_ARG, "v2p_stream_download: the counts are not the stream's (call it with null arrays first)");
+    if ((v.n_tx && (!host->tx_proteome_off || !host->tx_ref_len || !host->tx_res_len || !host->tx_task_begin || !host->tx_alt_begin)) ||
+        (v.n_tasks && (!host->code || !host->start_pos || !host->length || !host->start_pos_res)) || (v.n_alt && !host->alt) ||
+        ((host->tx_header_off == nullptr) != (host->tx_header_len == nullptr)))
+        return c->fail(V2P_ERR_INVALID_ARG, "v2p_stream_download: null argument");
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    struct Piece { const void* dst; const void* src; uint64_t bytes; };
+    const Piece pc[] = {
+        {host->hap_tx_begin, v.hap_tx_begin, (v.n_haps + 1) * 8}, {host->tx_proteome_off, v.tx_proteome_off, v.n_tx * 8},
+        {host->tx_ref_len, v.tx_ref_len, v.n_tx * 4}, {host->tx_res_len, v.tx_res_len, v.n_tx * 4},
+        {host->tx_task_begin, v.tx_task_begin, v.n_tx ? (v.n_tx + 1) * 8 : 0}, {host->tx_alt_begin, v.tx_alt_begin, v.n_tx ? (v.n_tx + 1) * 8 : 0},
+        {host->code, v.code, v.n_tasks}, {host->start_pos, v.start_pos, v.n_tasks * 4}, {host->length, v.length, v.n_tasks * 4},
+        {host->start_pos_res, v.start_pos_res, v.n_tasks * 4}, {host->alt, v.alt, v.n_alt},
+        {host->tx_header_off, v.fasta ? v.tx_header_off : nullptr, v.n_tx * 8}, {host->tx_header_len, v.fasta ? v.tx_header_len : nullptr, v.n_tx * 4}};
+    for (const Piece& p : pc)
+        if (p.bytes && p.dst && p.src) HIP_TRY(c, hipMemcpyAsync(const_cast<void*>(p.dst), p.src, p.bytes, hipMemcpyDeviceToHost, c->stream), "D2H(stream)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     return V2P_OK;
 }
 

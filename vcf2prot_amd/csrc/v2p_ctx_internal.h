@@ -7,6 +7,7 @@
 #include <string>
 
 struct v2p_ctx;
+struct v2p_stream;
 
 namespace v2p {
 hipStream_t ctx_stream(v2p_ctx* c);
@@ -14,6 +15,22 @@ int ctx_device(v2p_ctx* c);
 int ctx_fail(v2p_ctx* c, int code, const std::string& msg, int64_t index);
 void ctx_lock(v2p_ctx* c);
 void ctx_unlock(v2p_ctx* c);
+
+// A resident transcript stream (v2p_stream, include/vcf2prot_hip.h) whose arrays are written by kernels, not uploaded
+// (v2p_decode_tasks_emit).  All three are called with the context locked.
+struct StreamArrays {                  // device pointers into the stream's one allocation (stream_layout) and its alt bytes
+    unsigned long long *hap_tx_begin, *tx_proteome_off; uint32_t *tx_ref_len, *tx_res_len; unsigned long long *tx_task_begin, *tx_alt_begin;
+    uint8_t* code; uint32_t *start_pos, *length, *start_pos_res; uint8_t* alt; unsigned long long* tx_header_off; uint32_t* tx_header_len;
+};
+// a FASTA stream of these sizes, every byte of its allocation zero (the slack behind the Task arrays with it), enqueued on the context's stream
+int stream_born_alloc(v2p_ctx* c, uint64_t n_haps, uint64_t n_tx, uint64_t n_tasks, uint64_t n_alt, v2p_stream** out, StreamArrays* arrays);
+// the three host-side things of a stream: hap_out_begin[n_haps + 1] and the routing statistics {items, descriptors, arena bytes} x {mean, variance}
+// (stream_item_stats); then the tile tables, as behind an upload.  Waits for the context's stream.
+int stream_born_finish(v2p_ctx* c, v2p_stream* st, const uint64_t* hap_out_begin, const double* stats);
+void stream_born_drop(v2p_stream* st);
+// what the host checks of a transcript before a stream may name it: inside the resident proteome, its record header inside the header table
+// and ending in a line feed.  Returns a V2P_ERR_* code and says why.
+int ctx_check_transcript(v2p_ctx* c, uint64_t proteome_off, uint32_t ref_len, uint64_t header_off, uint32_t header_len, std::string* why);
 
 // V2P_DEBUG_POISON=1 (a debugging aid like the reference's DEBUG_* switches; read once): every device buffer is filled with 0xA5 whenever a
 // call (re)sizes it -- also when the allocation is reused -- so that nothing can lean on what fresh or recycled memory happens to hold

@@ -15,6 +15,7 @@
 #include "decode_kernels.h"
 #include "group_csr.h"
 #include "group_stats.h"
+#include "group_tasks.h"
 #include "inflate_format.hpp"
 #include "v2p_ctx_internal.h"
 
@@ -52,6 +53,25 @@ struct Groups {
     bool ok = false;
     float ms[5] = {0, 0, 0, 0, 0};    // upload of the tables, count, scan, emit, download
     std::vector<uint64_t> refused;
+};
+
+// the amino-acid and per-transcript tables of v2p_decode_tasks_count on the device, kept while the next call brings the same ones
+struct TaskTables {
+    DevMem aa, aa_bytes, tx, slot_rank;
+    std::vector<TaskAa> host_aa;
+    std::vector<uint8_t> host_aa_bytes;
+    std::vector<TaskTx> host_tx;
+    std::vector<uint32_t> host_slot_rank;
+};
+
+// v2p_decode_tasks_count: the items' counts and their prefix sums on the device until the next call or the end of their CSR
+struct Tasks {
+    DevMem counts, kinds, base, block_sums, hap_base, status;
+    TasksArgs args{};                 // what the count launched with: the emit launches with the same
+    std::vector<TaskCount> host_hap_base;      // [n_haps + 1]
+    std::vector<uint64_t> host_first_item;     // [n_haps + 1] every list's first item
+    bool ok = false;
+    float ms[4] = {0, 0, 0, 0};       // upload of the tables, count, scans, the last emit
 };
 
 // a status word's reason (decode_kernels.h) as the ABI's error code and the reference's words
@@ -132,7 +152,9 @@ struct v2p_decode {
     Tables tables;
     Stats stats;
     Groups groups;
-    void drop_lists() { lists = Lists{}; groups = Groups{}; }     // (the tables and the text stay)
+    TaskTables task_tables;
+    Tasks tasks;
+    void drop_lists() { lists = Lists{}; groups = Groups{}; tasks = Tasks{}; }     // (the tables and the text stay)
 };
 
 #define TRY(expr, what) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
@@ -278,6 +300,7 @@ static int prepare_tables(v2p_ctx* ctx, v2p_decode* d, const std::string& f, con
         (!n_extra || !memcmp(tb.host_extra.data(), t.extra, n_extra * sizeof(uint32_t))))
         return V2P_OK;
     tb = Tables{};
+    d->tasks = Tasks{};                                 // (its launches read the rows that go)
     TRY(tb.rec.alloc(rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
     TRY(tb.extra_begin.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
     TRY(tb.extra.alloc((n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
@@ -587,6 +610,7 @@ int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const u
     hipStream_t st = c.st;
     const uint64_t n_haps = c.n_haps, max_len = c.max_len;
     Groups& gr = d->groups;
+    d->tasks = Tasks{};                                 // (counted on the CSR that goes)
     // sizes: the bitmap covers every transcript; keys for the longest list and an eighth more (extras are rare), at least 2 048, a power of two; the
     // filter gets about 32 bits per id of the longest list.  Whatever does not fit 160 KiB of LDS shrinks, and lists over it are refused.
     const uint64_t lds_max = 160u * 1024u;
@@ -692,6 +716,232 @@ int v2p_decode_groups_refused(const v2p_decode* d, uint64_t* lists)
 int v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download)
 {
     return d ? give_ms(d->groups.ms, {ms_upload, ms_count, ms_scan, ms_emit, ms_download}) : V2P_ERR_INVALID_ARG;
+}
+
+// ---- (6) steps 4a / 4b on the device ----------------------------------------------------------------------------------------
+// the reference's words for an aborting item (the harness prints the same for its host loop)
+static std::string tasks_abort_text(uint32_t why, const std::string& name)
+{
+    switch (why) {
+        case TASKS_ABORT_4A: return "instruction generation for transcript " + name;
+        case TASKS_ABORT_4B_UNSUPPORTED: return "task generation for transcript " + name + " (2)";
+        case TASKS_ABORT_4B_ARITHMETIC: return "task generation for transcript " + name + " (3)";
+        case TASKS_ABORT_INSPECT: return "size mismatched / non-contiguous tasks in transcript " + name;
+        default: return "the grouped CSR is malformed at transcript " + name;
+    }
+}
+
+int v2p_decode_tasks_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len, uint64_t n_csq,
+                           const int64_t* tx_proteome_off, const uint32_t* tx_ref_len, const uint64_t* tx_header_off_1, const uint64_t* tx_header_off_2,
+                           const uint32_t* tx_header_len, uint64_t n_transcripts, const uint32_t* slot_rank, uint64_t n_slots,
+                           const uint8_t* tx_text, const uint64_t* tx_begin, const uint32_t* tx_len, uint32_t flags,
+                           uint64_t* hap_tx, uint64_t* hap_tasks, uint64_t* hap_alt, uint64_t* hap_bytes, v2p_tasks_info* info)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f = "v2p_decode_tasks_count";
+    if (!d || d->ctx != ctx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null decode, or one of another context", -1);
+    Groups& gr = d->groups;
+    if (!gr.ok || !d->tables.rec) return ctx_fail(ctx, V2P_ERR_STATE, f + ": needs the CSR of a successful v2p_decode_groups on this decode", -1);
+    const bool write_all = slot_rank != nullptr;
+    const uint64_t n_entries = write_all ? n_slots : n_transcripts;
+    if (!aa_begin || (n_csq && !aa_ref_len) || (n_csq && aa_begin[n_csq] && !aa) || !hap_tx || !hap_tasks || !hap_alt || !hap_bytes || !info ||
+        (n_entries && (!tx_proteome_off || !tx_ref_len || !tx_header_off_1 || !tx_header_off_2 || !tx_header_len)) || (!write_all && n_slots))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    if (n_csq + 1 != d->tables.host_rec.size()) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": n_consequences is not that of the tables the CSR was made from", -1);
+    if (n_transcripts > STATS_MAX_RANKS || n_slots >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts or 2^32 slots", -1);
+    *info = v2p_tasks_info{};
+    // the strings, one row per consequence: inside the bytes, below 2^30 each, their MutatedString kind in the two top bits (mutation_ds.rs:50-76)
+    std::vector<TaskAa> rows(n_csq + 1);
+    auto kind = [](const uint8_t* s, uint32_t n) -> uint32_t { return n == 1 && s[0] == '*' ? 2u : (n && memchr(s, '*', n) ? 1u : 0u); };
+    if (aa_begin[0] != 0) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin does not start at 0", 0);
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        if (aa_begin[i + 1] < aa_begin[i] || aa_begin[i + 1] > aa_begin[n_csq] || aa_begin[i + 1] - aa_begin[i] >= (1u << 30) || aa_ref_len[i] > aa_begin[i + 1] - aa_begin[i])
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin must ascend by less than 2^30 inside the bytes and hold aa_ref_len", int64_t(i));
+        const uint32_t rl = aa_ref_len[i], ml = uint32_t(aa_begin[i + 1] - aa_begin[i]) - rl;
+        rows[i] = TaskAa{aa_begin[i], rl | kind(aa + aa_begin[i], rl) << 30, ml | kind(aa + aa_begin[i] + rl, ml) << 30};
+    }
+    rows[n_csq] = TaskAa{aa_begin[n_csq], 0u, 0u};
+    const uint64_t n_aa = aa_begin[n_csq];
+    std::vector<TaskTx> txs(n_entries + 1, TaskTx{-1, {0, 0}, 0u, 0u});
+    for (uint64_t t = 0; t < n_entries; ++t) {
+        txs[t] = TaskTx{tx_proteome_off[t], {tx_header_off_1[t], tx_header_off_2[t]}, tx_ref_len[t], tx_header_len[t]};
+        if (tx_proteome_off[t] < 0) continue;
+        std::string why;
+        for (int h = 0; h < 2; ++h) {
+            const int rc = ctx_check_transcript(ctx, uint64_t(tx_proteome_off[t]), tx_ref_len[t], txs[t].header_off[h], tx_header_len[t], &why);
+            if (rc != V2P_OK) return ctx_fail(ctx, rc, f + ": " + why + " (entry " + std::to_string(t) + ")", int64_t(t));
+        }
+        if (!tx_header_len[t]) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": a transcript needs its record header (entry " + std::to_string(t) + ")", int64_t(t));
+    }
+    for (uint64_t s = 0; s < n_slots; ++s)
+        if (slot_rank[s] != ~0u && slot_rank[s] >= n_transcripts) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": slot rank outside the transcripts", int64_t(s));
+
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    const uint64_t n_haps = 2 * d->n_samples;
+    d->tasks = Tasks{};
+    Tasks& tk = d->tasks;
+    Events<4> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    TaskTables& tt = d->task_tables;
+    bool uploaded = false;
+    if (!(tt.aa && tt.host_aa.size() == rows.size() && tt.host_aa_bytes.size() == n_aa && tt.host_tx.size() == txs.size() &&
+          tt.host_slot_rank.size() == n_slots && (tt.slot_rank.get<void>() != nullptr) == write_all &&
+          !memcmp(tt.host_aa.data(), rows.data(), rows.size() * sizeof(TaskAa)) && (!n_aa || !memcmp(tt.host_aa_bytes.data(), aa, n_aa)) &&
+          !memcmp(tt.host_tx.data(), txs.data(), txs.size() * sizeof(TaskTx)) &&
+          (!n_slots || !memcmp(tt.host_slot_rank.data(), slot_rank, n_slots * sizeof(uint32_t))))) {
+        tt = TaskTables{};
+        TRY(tt.aa.alloc(rows.size() * sizeof(TaskAa)), "hipMalloc(aa rows)");
+        TRY(tt.aa_bytes.alloc(n_aa + 1), "hipMalloc(aa bytes)");
+        TRY(tt.tx.alloc(txs.size() * sizeof(TaskTx)), "hipMalloc(transcript rows)");
+        if (write_all) TRY(tt.slot_rank.alloc((n_slots + 1) * sizeof(uint32_t)), "hipMalloc(slot ranks)");
+        tt.host_aa.swap(rows);
+        tt.host_aa_bytes.assign(aa, aa + n_aa);
+        tt.host_tx.swap(txs);
+        tt.host_slot_rank.assign(slot_rank, slot_rank + n_slots);
+        // (the copies are made from the decode's own vectors: they outlive the stream's work)
+        TRY(hipMemcpyAsync(tt.aa.get<void>(), tt.host_aa.data(), tt.host_aa.size() * sizeof(TaskAa), hipMemcpyHostToDevice, st), "H2D(aa rows)");
+        if (n_aa) TRY(hipMemcpyAsync(tt.aa_bytes.get<void>(), tt.host_aa_bytes.data(), n_aa, hipMemcpyHostToDevice, st), "H2D(aa bytes)");
+        TRY(hipMemcpyAsync(tt.tx.get<void>(), tt.host_tx.data(), tt.host_tx.size() * sizeof(TaskTx), hipMemcpyHostToDevice, st), "H2D(transcript rows)");
+        if (n_slots) TRY(hipMemcpyAsync(tt.slot_rank.get<void>(), tt.host_slot_rank.data(), n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(slot ranks)");
+        uploaded = true;
+    }
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+
+    const uint64_t n_items = write_all ? n_haps * n_slots : gr.n_groups;
+    TRY(tk.counts.alloc((n_items + 1) * sizeof(TaskCount)), "hipMalloc(task counts)");
+    TRY(tk.kinds.alloc(n_items + 1), "hipMalloc(item kinds)");
+    TRY(tk.base.alloc((n_items + 1) * sizeof(TaskCount)), "hipMalloc(task bases)");
+    TRY(tk.block_sums.alloc((tasks_scan_blocks(n_items) + 1) * sizeof(TaskCount)), "hipMalloc(tile sums)");
+    TRY(tk.hap_base.alloc((n_haps + 1) * sizeof(TaskCount)), "hipMalloc(haplotype bases)");
+    TRY(tk.status.alloc(sizeof(uint64_t)), "hipMalloc(tasks status)");
+    TRY(hipMemsetAsync(tk.status.get<void>(), 0xFF, sizeof(uint64_t), st), "hipMemset(tasks status)");
+    TasksArgs& a = tk.args;
+    a.hap_group_begin = gr.hap_group_begin.get<unsigned long long>(); a.group_transcript = gr.group_transcript.get<uint32_t>();
+    a.group_member_begin = gr.group_member_begin.get<unsigned long long>(); a.member_ids = gr.member_ids.get<uint32_t>();
+    a.n_haps = uint32_t(n_haps); a.n_groups = gr.n_groups; a.n_members = gr.n_members;
+    a.rec = d->tables.rec.get<StatsRec>(); a.aa = tt.aa.get<TaskAa>(); a.n_csq = uint32_t(n_csq); a.aa_bytes = tt.aa_bytes.get<uint8_t>();
+    a.tx = tt.tx.get<TaskTx>(); a.n_tx = uint32_t(n_entries);
+    a.slot_rank = write_all ? tt.slot_rank.get<uint32_t>() : nullptr; a.n_slots = uint32_t(n_slots);
+    a.flags = flags; a.n_items = n_items;
+    a.counts = tk.counts.get<TaskCount>(); a.kinds = tk.kinds.get<uint8_t>(); a.status = tk.status.get<unsigned long long>();
+    a.block_sums = tk.block_sums.get<TaskCount>(); a.base = tk.base.get<TaskCount>(); a.hap_base = tk.hap_base.get<TaskCount>();
+    TRY(launch_tasks_count(a, st), "group_tasks_kernel (count)");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(launch_tasks_scan(a, st), "tasks scan kernels");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    uint64_t status = ~0ull;
+    tk.host_hap_base.assign(n_haps + 1, TaskCount{0, 0, 0, 0});
+    std::vector<uint64_t> hgb(n_haps + 1);
+    TRY(hipMemcpyAsync(&status, tk.status.get<void>(), sizeof(status), hipMemcpyDeviceToHost, st), "D2H(tasks status)");
+    TRY(hipMemcpyAsync(tk.host_hap_base.data(), tk.hap_base.get<void>(), (n_haps + 1) * sizeof(TaskCount), hipMemcpyDeviceToHost, st), "D2H(haplotype bases)");
+    TRY(hipMemcpyAsync(hgb.data(), gr.hap_group_begin.get<void>(), (n_haps + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_group_begin)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (uploaded) (void)hipEventElapsedTime(&tk.ms[0], ev[0], ev[1]);
+    for (int k = 1; k < 3; ++k) (void)hipEventElapsedTime(&tk.ms[k], ev[k], ev[k + 1]);
+    info->n_items = n_items;
+    if (status != ~0ull) {
+        // the smallest item is the smallest haplotype list and, within it, the first transcript in stream order
+        const uint64_t item = status >> 8;
+        uint64_t hap = 0;
+        uint32_t r = ~0u;
+        if (write_all) { hap = item / n_slots; r = slot_rank[item % n_slots]; }
+        else {
+            hap = uint64_t(std::upper_bound(hgb.begin(), hgb.end(), item) - hgb.begin()) - 1;
+            TRY(hipMemcpy(&r, gr.group_transcript.get<uint32_t>() + item, sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(group_transcript)");
+        }
+        const std::string name = tx_text && tx_begin && tx_len && r < n_transcripts ? std::string(reinterpret_cast<const char*>(tx_text) + tx_begin[r], tx_len[r])
+                                                                                     : "rank " + std::to_string(r);
+        return ctx_fail(ctx, V2P_ERR_TASKS, tasks_abort_text(uint32_t(status & 0xffu), name), int64_t(hap));
+    }
+    tk.host_first_item.resize(n_haps + 1);
+    for (uint64_t h = 0; h <= n_haps; ++h) tk.host_first_item[h] = write_all ? h * n_slots : hgb[h];
+    const std::vector<TaskCount>& hb = tk.host_hap_base;
+    for (uint64_t h = 0; h < n_haps; ++h) {
+        hap_tx[h] = hb[h + 1].tx - hb[h].tx; hap_tasks[h] = hb[h + 1].tasks - hb[h].tasks;
+        hap_alt[h] = hb[h + 1].alt - hb[h].alt; hap_bytes[h] = hb[h + 1].arena - hb[h].arena;
+    }
+    info->n_tx = hb[n_haps].tx; info->n_tasks = hb[n_haps].tasks; info->n_alt = hb[n_haps].alt; info->out_bytes = hb[n_haps].arena;
+    tk.ok = true;
+    return V2P_OK;
+}
+
+int v2p_decode_tasks_emit(v2p_ctx* ctx, v2p_decode* d, uint64_t h0, uint64_t h1, v2p_stream** out)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f = "v2p_decode_tasks_emit";
+    if (!out) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    *out = nullptr;
+    if (!d || d->ctx != ctx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null decode, or one of another context", -1);
+    Tasks& tk = d->tasks;
+    if (!tk.ok || !d->groups.ok) return ctx_fail(ctx, V2P_ERR_STATE, f + ": needs a successful v2p_decode_tasks_count on this decode", -1);
+    const uint64_t n_haps = 2 * d->n_samples;
+    if (h0 > h1 || h1 > n_haps) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": haplotype range outside the file", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    const std::vector<TaskCount>& hb = tk.host_hap_base;
+    const uint64_t n_h = h1 - h0;
+    TasksArgs a = tk.args;
+    a.h0 = uint32_t(h0); a.h1 = uint32_t(h1);
+    a.first = hb[h0];
+    a.out_tx = hb[h1].tx - hb[h0].tx; a.out_tasks = hb[h1].tasks - hb[h0].tasks; a.out_alt = hb[h1].alt - hb[h0].alt;
+    DevMem d_hap_out, d_sample;                         // freed on every exit path
+    Events<2> ev;
+    TRY(ev.create(), "hipEventCreate");
+    // the items of the range: groups [hap_group_begin[h0], hap_group_begin[h1]), or with -a every slot of every list
+    a.i0 = std::min(tk.host_first_item[h0], a.n_items); a.i1 = std::min(std::max(tk.host_first_item[h0], tk.host_first_item[h1]), a.n_items);
+    const uint64_t step = a.out_tx > 65536 ? a.out_tx / 65536 : 1;                   // stream_item_stats' sample
+    const uint64_t n_samples = a.out_tx ? (a.out_tx + step - 1) / step : 0;
+    TRY(d_hap_out.alloc((n_h + 1) * sizeof(uint64_t)), "hipMalloc(hap_out_begin)");
+    TRY(d_sample.alloc((n_samples + 1) * sizeof(TaskSample)), "hipMalloc(routing sample)");
+    v2p_stream* s = nullptr;
+    StreamArrays arr{};
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    int rc = stream_born_alloc(ctx, n_h, a.out_tx, a.out_tasks, a.out_alt, &s, &arr);
+    if (rc != V2P_OK) return rc;
+    a.hap_tx_begin = arr.hap_tx_begin; a.hap_out_begin = d_hap_out.get<unsigned long long>();
+    a.tx_proteome_off = arr.tx_proteome_off; a.tx_ref_len = arr.tx_ref_len; a.tx_res_len = arr.tx_res_len;
+    a.tx_task_begin = arr.tx_task_begin; a.tx_alt_begin = arr.tx_alt_begin;
+    a.code = arr.code; a.start_pos = arr.start_pos; a.length = arr.length; a.start_pos_res = arr.start_pos_res; a.alt = arr.alt;
+    a.tx_header_off = arr.tx_header_off; a.tx_header_len = arr.tx_header_len;
+    SampleArgs sa{a.out_tx, step, n_samples, arr.tx_task_begin, arr.code, arr.length, arr.tx_res_len, arr.tx_header_len, d_sample.get<TaskSample>()};
+    std::vector<TaskSample> sample(n_samples);
+    std::vector<uint64_t> hap_out(n_h + 1);
+    hipError_t e = launch_tasks_emit(a, st);
+    if (e == hipSuccess) e = launch_tasks_sample(sa, st);
+    if (e == hipSuccess && n_samples) e = hipMemcpyAsync(sample.data(), d_sample.get<void>(), n_samples * sizeof(TaskSample), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hap_out.data(), d_hap_out.get<void>(), (n_h + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { stream_born_drop(s); return ctx_fail(ctx, V2P_ERR_HIP, std::string("group_tasks_kernel (emit): ") + hipGetErrorString(e), -1); }
+    // stream_item_stats on the sample, summed in its order: a device-born stream is routed as its uploaded twin
+    double stats[6] = {1.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (n_samples) {
+        double sum = 0, sq = 0, dsum = 0, dsq = 0, lsum = 0, lsq = 0, cnt = 0;
+        for (const TaskSample& t : sample) {
+            const uint64_t nt = t.nt, nf = t.nf;
+            const double x = nt ? double(nt) : 1.0;
+            const double dd = (nt > 2 * nf ? double(nt - 2 * nf) : 1.0) + 1.0;
+            const double l = double(t.len);
+            sum += x; sq += x * x; dsum += dd; dsq += dd * dd; lsum += l; lsq += l * l; cnt += 1;
+        }
+        const double m = sum / cnt, dm = dsum / cnt, lm = lsum / cnt;
+        stats[0] = m; stats[1] = sq / cnt - m * m > 0 ? sq / cnt - m * m : 0.0;
+        stats[2] = dm; stats[3] = dsq / cnt - dm * dm > 0 ? dsq / cnt - dm * dm : 0.0;
+        stats[4] = lm; stats[5] = lsq / cnt - lm * lm > 0 ? lsq / cnt - lm * lm : 0.0;
+    }
+    rc = stream_born_finish(ctx, s, hap_out.data(), stats);
+    if (rc != V2P_OK) { stream_born_drop(s); return rc; }
+    if (hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess) (void)hipEventElapsedTime(&tk.ms[3], ev[0], ev[1]);
+    *out = s;
+    return V2P_OK;
+}
+
+int v2p_decode_tasks_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit)
+{
+    return d ? give_ms(d->tasks.ms, {ms_upload, ms_count, ms_scan, ms_emit}) : V2P_ERR_INVALID_ARG;
 }
 
 void v2p_decode_destroy(v2p_decode* d)

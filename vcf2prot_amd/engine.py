@@ -257,6 +257,29 @@ class ResidentStream:
         ctx._check(self._lib.v2p_stream_upload(ctx._h, ctypes.byref(stream.struct), ctypes.byref(h)))
         self._h = h
 
+    @classmethod
+    def adopt(cls, ctx: "Context", handle) -> "ResidentStream":
+        """Owner of a v2p_stream some other call made (frontend.device_tasks_emit)."""
+        rs = cls.__new__(cls)
+        rs.ctx, rs._lib, rs._h = ctx, ctx._lib, handle
+        return rs
+
+    def download(self) -> Dict[str, np.ndarray]:
+        """v2p_stream_download: the stream's arrays by their v2p_txstream names, without slack (tests, tools, and the host builder's fallback)."""
+        from ._cohort_api import TxStreamBuf
+        s = TxStreamBuf()
+        self.ctx._check(self._lib.v2p_stream_download(self._h, ctypes.byref(s)))
+        n_h, n_tx, n_tk, n_alt = int(s.n_haps), int(s.n_tx), int(s.n_tasks), int(s.n_alt)
+        shape = [("hap_tx_begin", n_h + 1, np.uint64), ("tx_proteome_off", n_tx, np.uint64), ("tx_ref_len", n_tx, np.uint32), ("tx_res_len", n_tx, np.uint32),
+                 ("tx_task_begin", n_tx + 1, np.uint64), ("tx_alt_begin", n_tx + 1, np.uint64), ("code", n_tk, np.uint8), ("start_pos", n_tk, np.uint32),
+                 ("length", n_tk, np.uint32), ("start_pos_res", n_tk, np.uint32), ("alt", n_alt, np.uint8), ("tx_header_off", n_tx, np.uint64),
+                 ("tx_header_len", n_tx, np.uint32)]
+        out = {name: np.zeros(n + 1, dt) for name, n, dt in shape}      # (one spare entry: no empty array, no null pointer)
+        for name, _, _ in shape:
+            setattr(s, name, out[name].ctypes.data_as(type(getattr(s, name))))
+        self.ctx._check(self._lib.v2p_stream_download(self._h, ctypes.byref(s)))
+        return {name: out[name][:n] for name, n, _ in shape}
+
     def counts(self) -> Dict[str, int]:
         v = [ctypes.c_uint64() for _ in range(4)]
         self.ctx._check(self._lib.v2p_stream_counts(self._h, *[ctypes.byref(x) for x in v]))

@@ -23,10 +23,10 @@ from . import _native as N
 
 V2P_ERR_MASK_NEGATIVE, V2P_ERR_MASK_PARSE, V2P_ERR_MASK_INDEX, V2P_ERR_COLUMNS = -20, -21, -22, -23
 V2P_ERR_FIELD_TOO_LONG, V2P_ERR_CAPACITY, V2P_ERR_VCF_FORMAT, V2P_ERR_DUPLICATE_POS = -24, -25, -26, -27
-V2P_ERR_GZIP = -28
+V2P_ERR_GZIP, V2P_ERR_TASKS = -28, -29
 N.ERR_NAMES.update({-20: "V2P_ERR_MASK_NEGATIVE", -21: "V2P_ERR_MASK_PARSE", -22: "V2P_ERR_MASK_INDEX", -23: "V2P_ERR_COLUMNS",
                     -24: "V2P_ERR_FIELD_TOO_LONG", -25: "V2P_ERR_CAPACITY", -26: "V2P_ERR_VCF_FORMAT", -27: "V2P_ERR_DUPLICATE_POS",
-                    -28: "V2P_ERR_GZIP"})
+                    -28: "V2P_ERR_GZIP", -29: "V2P_ERR_TASKS"})
 
 
 class v2p_mutation(ctypes.Structure):
@@ -57,6 +57,10 @@ DECODE_API = {
     "v2p_decode_groups_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_decode_groups_refused": (c_int, [c_void_p, c_void_p]),
     "v2p_decode_groups_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "v2p_decode_tasks_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64,
+                                       c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_decode_tasks_emit": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_void_p)]),
+    "v2p_decode_tasks_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -101,6 +105,9 @@ HOST_API = {
     "v2p_csq_tables_ident": (POINTER(c_uint32), [c_void_p]),
     "v2p_csq_tables_extra_begin": (POINTER(c_uint32), [c_void_p]),
     "v2p_csq_tables_extra": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_aa": (POINTER(c_uint8), [c_void_p]),
+    "v2p_csq_tables_aa_begin": (POINTER(c_uint64), [c_void_p]),
+    "v2p_csq_tables_aa_ref_len": (POINTER(c_uint32), [c_void_p]),
 }
 
 
@@ -121,6 +128,10 @@ class v2p_groups_caps(ctypes.Structure):
 class v2p_groups_info(ctypes.Structure):
     _fields_ = [("n_refused", c_uint64), ("n_groups", c_uint64), ("n_members", c_uint64), ("bitmap_words", c_uint32), ("filter_words", c_uint32),
                 ("key_capacity", c_uint32), ("lds_bytes", c_uint32)]
+
+
+class v2p_tasks_info(ctypes.Structure):
+    _fields_ = [("n_items", c_uint64), ("n_tx", c_uint64), ("n_tasks", c_uint64), ("n_alt", c_uint64), ("out_bytes", c_uint64)]
 
 
 _bound = {}
@@ -444,7 +455,13 @@ SUP_TYPE = ("missense", "*missense", "frameshift", "*frameshift", "inframe_inser
 
 class CsqTables:
     """The file-wide per-consequence tables of the grouping rule (v2p_csq_tables_build): rank, flags (bit 0 mut_ok, bit 1 poison,
-    bits 8-15 type), mut_pos, ref_pos, ident, the CSR extra_begin / extra, and the sorted transcript names."""
+    bits 8-15 type), mut_pos, ref_pos, ident, the CSR extra_begin / extra, the sorted transcript names, and the amino-acid strings of the
+    mut_ok consequences (aa, aa_begin, aa_ref_len: ref_aa then mut_aa of consequence i at aa[aa_begin[i]:aa_begin[i + 1]])."""
+
+    def aa_strings(self, i: int):
+        """(ref_aa, mut_aa) of consequence i as bytes"""
+        b, e, r = int(self.aa_begin[i]), int(self.aa_begin[i + 1]), int(self.aa_ref_len[i])
+        return self.aa[b:b + r].tobytes(), self.aa[b + r:e].tobytes()
 
     def __init__(self, idx: VcfIndex, n_threads: int = 0):
         L = self._lib = _host()
@@ -465,6 +482,9 @@ class CsqTables:
         self.extra = _arr(L.v2p_csq_tables_extra(h), int(self.extra_begin[-1]), np.uint32)
         self.transcript_begin = _arr(L.v2p_csq_tables_transcript_begin(h), t, np.uint64)
         self.transcript_len = _arr(L.v2p_csq_tables_transcript_len(h), t, np.uint32)
+        self.aa_begin = _arr(L.v2p_csq_tables_aa_begin(h), n + 1, np.uint64)
+        self.aa_ref_len = _arr(L.v2p_csq_tables_aa_ref_len(h), n, np.uint32)
+        self.aa = _arr(L.v2p_csq_tables_aa(h), int(self.aa_begin[-1]), np.uint8)
 
     def transcript_names(self):
         return [self._idx._bytes[int(b):int(b) + int(n)].decode() for b, n in zip(self.transcript_begin, self.transcript_len)]
@@ -516,6 +536,71 @@ def device_groups(ctx, idx: VcfIndex, resident: ResidentLists, tables: "CsqTable
         g = Groups.from_csr(tables, *csr)
     g.path, g.info = ("host" if refused else "device"), info
     return g
+
+
+class TranscriptInputs:
+    """What steps 4a / 4b need of every transcript (v2p_decode_tasks_count): one entry per transcript rank of the file, or -- with
+    slot_rank, for -a -- per slot of the sorted union of the reference's and the file's names.  proteome_off < 0: not in the reference."""
+
+    def __init__(self, proteome_off, ref_len, header_off_1, header_off_2, header_len, slot_rank=None):
+        self.proteome_off, self.ref_len = np.ascontiguousarray(proteome_off, np.int64), np.ascontiguousarray(ref_len, np.uint32)
+        self.header_off_1, self.header_off_2 = np.ascontiguousarray(header_off_1, np.uint64), np.ascontiguousarray(header_off_2, np.uint64)
+        self.header_len = np.ascontiguousarray(header_len, np.uint32)
+        self.slot_rank = None if slot_rank is None else np.ascontiguousarray(slot_rank, np.uint32)
+
+
+def device_groups_resident(ctx, resident: ResidentLists, tables, caps=None):
+    """v2p_decode_groups alone: the CSR stays on the decode (device_tasks_count reads it there).  (refused lists, info dict, error or None)"""
+    lib = _hip()
+    info = v2p_groups_info()
+    c = v2p_groups_caps(*caps) if caps is not None else None
+    rc = lib.v2p_decode_groups(*_table_args(ctx, resident, tables), ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    err = _check(ctx, rc, abort=True)
+    refused = np.zeros(int(info.n_refused), np.uint64)
+    lib.v2p_decode_groups_refused(resident._h, _ptr(refused))
+    t = [c_float() for _ in range(5)]
+    lib.v2p_decode_groups_timing(resident._h, *[ctypes.byref(x) for x in t])
+    inf = {k: int(getattr(info, k)) for k, _ in v2p_groups_info._fields_}
+    inf["timing_ms"] = dict(zip(("upload", "count", "scan", "emit", "download"), (x.value for x in t)))
+    return refused.astype(np.int64).tolist(), inf, err
+
+
+def device_tasks_count(ctx, resident: ResidentLists, tables, tx: TranscriptInputs, flags: int):
+    """v2p_decode_tasks_count on the CSR the last v2p_decode_groups left on `resident`: {"hap_tx", "hap_tasks", "hap_alt", "hap_bytes":
+    arrays [n_haplotypes]; "info": totals}.  `tables` is a CsqTables or anything with its arrays.  Raises V2PError(V2P_ERR_TASKS) with
+    the smallest aborting haplotype list where the reference aborts."""
+    lib = _hip()
+    n_h = resident.n_haplotypes
+    out = [np.zeros(n_h + 1, np.uint64) for _ in range(4)]
+    info = v2p_tasks_info()
+    slots = tx.slot_rank
+    n_entries = tx.proteome_off.size
+    if slots is None and n_entries != tables.n_transcripts or slots is not None and n_entries != slots.size:
+        raise ValueError("one entry per transcript rank, or per slot")
+    spare = np.zeros(1, np.uint32)
+    rc = lib.v2p_decode_tasks_count(ctx._h, resident._h, _ptr(tables.aa), tables.aa_begin.ctypes.data, _ptr(tables.aa_ref_len), tables.n_consequences,
+                                    _ptr(tx.proteome_off), _ptr(tx.ref_len), _ptr(tx.header_off_1), _ptr(tx.header_off_2), _ptr(tx.header_len),
+                                    tables.n_transcripts, None if slots is None else (_ptr(slots) or spare.ctypes.data), 0 if slots is None else slots.size,
+                                    tables._idx.text.ctypes.data, _ptr(tables.transcript_begin), _ptr(tables.transcript_len), flags,
+                                    *[a.ctypes.data for a in out], ctypes.byref(info))
+    _check(ctx, rc)
+    res = dict(zip(("hap_tx", "hap_tasks", "hap_alt", "hap_bytes"), (a[:n_h] for a in out)))
+    res["info"] = {k: int(getattr(info, k)) for k, _ in v2p_tasks_info._fields_}
+    return res
+
+
+def device_tasks_emit(ctx, resident: ResidentLists, h0: int, h1: int):
+    """v2p_decode_tasks_emit: haplotype lists [h0, h1) of the last device_tasks_count as an engine.ResidentStream of their own."""
+    from .engine import ResidentStream
+    h = c_void_p()
+    _check(ctx, _hip().v2p_decode_tasks_emit(ctx._h, resident._h, h0, h1, ctypes.byref(h)))
+    return ResidentStream.adopt(ctx, h)
+
+
+def device_tasks_timing(resident: ResidentLists) -> dict:
+    t = [c_float() for _ in range(4)]
+    _hip().v2p_decode_tasks_timing(resident._h, *[ctypes.byref(x) for x in t])
+    return dict(zip(("upload", "count", "scan", "emit"), (x.value for x in t)))
 
 
 class CohortStats:

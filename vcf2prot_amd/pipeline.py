@@ -13,7 +13,8 @@ import numpy as np
 
 from . import _native as N
 from . import step4a
-from .frontend import CsqTables, Groups, VcfIndex, decode_resident, device_groups, inflate_bgzf, input_format
+from .frontend import (CsqTables, Groups, TranscriptInputs, VcfIndex, decode_resident, device_groups, device_groups_resident, device_tasks_count,
+                       device_tasks_emit, device_tasks_timing, inflate_bgzf, input_format)
 from .step4b import inspect_transcript_tasks, transcript_g_rep
 
 
@@ -76,9 +77,99 @@ def _proband_bytes(b, k: int, bgzf: bool) -> bytes:
     return b.bgzf_hap(k) + b.bgzf_hap(k + 1) + EOF_BLOCK
 
 
+def resident_reference(names, ref):
+    """The resident reference of a file: the transcripts of `names` the reference FASTA has, back to back in that order, and their two
+    record headers each behind a leading line feed.  (proteome bytes, header bytes, {name: offset}, {(name, haplotype 1 | 2): (offset, length)})"""
+    off, pieces, hdr, hdr_off = {}, [], ["\n"], {}
+    pos, hpos = 0, 1
+    for nm in names:
+        if nm in ref:
+            off[nm] = pos
+            pieces.append(ref[nm])
+            pos += len(ref[nm])
+            for h in (1, 2):
+                text = f">{nm}_{h}\n"
+                hdr_off[(nm, h)] = (hpos, len(text))
+                hdr.append(text)
+                hpos += len(text)
+    proteome = np.frombuffer("".join(pieces).encode(), dtype=np.uint8) if pieces else np.zeros(0, np.uint8)
+    return proteome, np.frombuffer("".join(hdr).encode(), dtype=np.uint8), off, hdr_off
+
+
+def _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report):
+    """vcf_to_fasta with steps 4a / 4b on the device (include/v2p_frontend.h part 6): the grouped CSR never leaves the device.  The
+    per-haplotype arena sizes of the count cut the probands into slices of about slice_bytes; every slice is emitted as a resident stream,
+    built and executed by the one call, and read back -- one slice after the other.  A slice the one call refuses (V2P_ERR_UNSUPPORTED) is
+    downloaded and goes through the host builder, as in the host loop.  None: the grouping refused a list, the host loop takes the file."""
+    from .bgzf import EOF_BLOCK
+    from .txstream import HostTxStream, build_on_device_auto
+    refused, ginfo, err = device_groups_resident(ctx, resident, tables, groups_caps)
+    if refused:
+        return None
+    if err is not None:
+        raise err
+    if report is not None:
+        report["groups"] = dict(ginfo, path="device")
+    file_names = tables.transcript_names()
+    names = sorted(set(file_names) | set(ref), key=lambda x: x.encode()) if write_all else file_names
+    proteome, headers, off, hdr_off = resident_reference(names, ref)
+    ctx.upload_reference(proteome, headers)
+    rank_of = {nm: r for r, nm in enumerate(file_names)}
+    tx = TranscriptInputs([off.get(nm, -1) for nm in names], [len(ref.get(nm, "")) for nm in names],
+                          [hdr_off.get((nm, 1), (0, 0))[0] for nm in names], [hdr_off.get((nm, 2), (0, 0))[0] for nm in names],
+                          [hdr_off.get((nm, 1), (0, 0))[1] for nm in names],
+                          [rank_of.get(nm, 0xFFFFFFFF) for nm in names] if write_all else None)
+    counted = device_tasks_count(ctx, resident, tables, tx, flags)
+    sample_names = idx.sample_names()
+    hap_bytes = counted["hap_bytes"]
+    out: Dict[str, bytes] = {}
+    n_slices = n_fallback = 0
+    b = ctx.batch()
+    try:
+        s0, acc = 0, 0
+        for s in range(len(sample_names)):
+            acc += int(hap_bytes[2 * s]) + int(hap_bytes[2 * s + 1])
+            if acc < slice_bytes and s + 1 != len(sample_names):
+                continue
+            stream = device_tasks_emit(ctx, resident, 2 * s0, 2 * s + 2)
+            try:
+                try:
+                    b.build_and_execute(stream, 0)
+                    b.sync()
+                except N.V2PError as e:
+                    if e.code != -9:
+                        raise
+                    # a slice even the dense rows image refuses: the host builder takes any stream
+                    a = stream.download()
+                    pad = lambda x: np.concatenate([x, np.zeros(64, x.dtype)])
+                    host = HostTxStream([a["hap_tx_begin"], a["tx_proteome_off"], a["tx_ref_len"], a["tx_res_len"], a["tx_task_begin"], a["tx_alt_begin"],
+                                         pad(a["code"]), pad(a["start_pos"]), pad(a["length"]), pad(a["start_pos_res"]), pad(a["alt"]), a["tx_header_off"],
+                                         a["tx_header_len"]], a["hap_tx_begin"].size - 1, a["tx_ref_len"].size, a["code"].size, a["alt"].size, True, 0)
+                    b.reset()
+                    build_on_device_auto(b, host)
+                    b.execute()
+                    b.sync()
+                    n_fallback += 1
+                if bgzf:
+                    b.bgzf()
+                for p in range(s0, s + 1):
+                    out[sample_names[p]] = _proband_bytes(b, 2 * (p - s0), bgzf)
+                b.reset()
+            finally:
+                stream.close()
+            n_slices += 1
+            s0, acc = s + 1, 0
+    finally:
+        b.close()
+    if report is not None:
+        report["tasks"] = dict(counted["info"], path="device", n_slices=n_slices, slices_through_the_host_builder=n_fallback,
+                               timing_ms=device_tasks_timing(resident))
+    return out
+
+
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
                  device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False, host_groups: bool = False,
-                 groups_caps=None, report: dict = None) -> Dict[str, bytes]:
+                 groups_caps=None, report: dict = None, device_tasks: bool = False) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
@@ -91,7 +182,12 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     any other gzip is inflated here.
     The consequences are grouped per transcript on the GPU from the lists the decode left there (frontend.device_groups); if the kernel
     refuses a list, or with host_groups, the ids are downloaded and the whole file is grouped on the host from the same tables -- same
-    bytes.  groups_caps: the kernel's sizes (tests); report: a dict that receives {"groups": {"path": "device" | "host", ...}}."""
+    bytes.  groups_caps: the kernel's sizes (tests); report: a dict that receives {"groups": {"path": "device" | "host", ...}} and
+    {"tasks": {"path": "device" | "host", ...}}.
+    device_tasks (opt-in): steps 4a / 4b run on the GPU too, on the grouped CSR where the grouping kernel left it (_device_tasks): the
+    slices are cut from the count, emitted as resident streams and built and executed one after the other -- same bytes.  It needs the
+    device build and the device grouping: with device_build=False, with host_groups, or when the grouping kernel refuses a list, the host
+    loop below runs the whole file."""
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
     fmt, inflated = input_format(vcf), None
@@ -111,6 +207,10 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         n_haplotypes = resident.n_haplotypes
         tables = CsqTables(idx)
         try:
+            if device_tasks and device_build and not host_groups:
+                out = _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report)
+                if out is not None:
+                    return out
             if host_groups:
                 groups = Groups.from_tables(tables, resident.download())
             else:
@@ -121,24 +221,13 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         resident.close()
     if report is not None:
         report["groups"] = dict(groups.info or {}, path=groups.path)
+        report["tasks"] = {"path": "host"}
     names = [groups.transcript_name(r) for r in range(groups.n_transcripts)]
     if write_all:
         names = sorted(set(names) | set(ref), key=lambda x: x.encode())
     # resident reference: the transcripts the file touches, and their two record headers each
-    off, pieces, hdr, hdr_off = {}, [], ["\n"], {}
-    pos, hpos = 0, 1
-    for nm in names:
-        if nm in ref:
-            off[nm] = pos
-            pieces.append(ref[nm])
-            pos += len(ref[nm])
-            for h in (1, 2):
-                text = f">{nm}_{h}\n"
-                hdr_off[(nm, h)] = (hpos, len(text))
-                hdr.append(text)
-                hpos += len(text)
-    proteome = np.frombuffer("".join(pieces).encode(), dtype=np.uint8) if pieces else np.zeros(0, np.uint8)
-    ctx.upload_reference(proteome, np.frombuffer("".join(hdr).encode(), dtype=np.uint8))
+    proteome, headers, off, hdr_off = resident_reference(names, ref)
+    ctx.upload_reference(proteome, headers)
     sample_names = idx.sample_names()
     out: Dict[str, bytes] = {}
     b = ctx.batch() if not device_build else None
