@@ -23,9 +23,12 @@
  *                         stream (v2p_stream, include/vcf2prot_hip.h): nothing per haplotype crosses the link between the VCF text and
  *                         the FASTA bytes.
  *
+ *   (7) the tables of (4) on the device   v2p_decode_tables_build makes the file-wide consequence tables from the text a decode keeps resident;
+ *                         v2p_csq_tables_from_arrays (host) wraps the downloaded columns into the v2p_csq_tables of (4).
+ *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
- * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4), the v2p_decode_groups* calls of (5) and the v2p_decode_tasks* calls of
- * (6); libv2p_cohort.so (plain C++) exports the rest.
+ * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4), the v2p_decode_groups* calls of (5), the v2p_decode_tasks* calls of
+ * (6) and the v2p_decode_tables* calls of (7); libv2p_cohort.so (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -49,7 +52,8 @@ struct v2p_ctx;                                   /* include/vcf2prot_hip.h */
                                            more -> the reference panics; fewer -> it silently pairs fields with the
                                            wrong consequences, which this engine refuses                             */
 #define V2P_ERR_FIELD_TOO_LONG  (-24)   /* a sample column whose text after the last ':' exceeds 4 KiB             */
-#define V2P_ERR_CAPACITY        (-25)   /* raw launcher only: ids / multi-word capacity too small (needed size reported) */
+#define V2P_ERR_CAPACITY        (-25)   /* raw launcher: ids / multi-word capacity too small; v2p_decode_tables_build: a table
+                                           with fewer slots than keys (needed size reported) */
 #define V2P_ERR_VCF_FORMAT      (-26)   /* readers.rs:113-150      no "#CHROM" line, fewer than 10 columns, no records */
 #define V2P_ERR_DUPLICATE_POS   (-27)   /* vcf_ds.rs:411           two different mutations on one reference position  */
 #ifndef V2P_ERR_GZIP
@@ -345,6 +349,54 @@ int  v2p_decode_tasks_emit(struct v2p_ctx* ctx, v2p_decode* d, uint64_t h0, uint
 /* milliseconds of the last v2p_decode_tasks_count / _emit on d (HIP events): the upload of the amino-acid and per-transcript tables (0 when
  * the decode held them), the count launch, the scans, the last emit (launch, routing sample, tile tables) */
 int  v2p_decode_tasks_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (7) the consequence tables of (4) built on the device, from the text a decode keeps resident (after v2p_decode_run and after
+ * v2p_decode_inflate alike).  The rule is v2p_csq_tables_build's; every column compares equal to it, ident included.  Only the transcript
+ * names are sorted on the host (a few 10^4 of them).  Opt-in for the callers of this repository (pipeline.vcf_to_fasta(device_tables=True),
+ * --device-tables): a failed device build falls back to v2p_csq_tables_build for the whole file.
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* Slot counts of the two open-addressing tables (transcript names; drop_replicate's identity classes), powers of two; 0 = chosen from
+ * the file (twice the keys, so never full). */
+typedef struct v2p_tables_caps {
+    uint32_t name_slots, ident_slots;
+} v2p_tables_caps;
+typedef struct v2p_tables_info {
+    uint64_t n_transcripts, n_extra, n_aa;      /* sizes of tx_begin / tx_len, extra and aa */
+    uint32_t n_lengths;                         /* distinct transcript-name lengths above 0 */
+    uint32_t name_slots, ident_slots;           /* what was launched; after V2P_ERR_CAPACITY: sizes that suffice */
+} v2p_tables_info;
+
+/* Builds the tables on the device of d, which must hold text (with or without lists).  text: the host's copy of that text (the names
+ * are sorted from it); csq_text_begin / csq_text_len / csq_supported: the index's columns, n_consequences of them, uploaded.  The
+ * tables stay on d until the next build or v2p_decode_destroy.  A table that is too small for its keys returns V2P_ERR_CAPACITY with
+ * v2p_last_error_index(ctx) = the smallest consequence without a slot and info's slot counts set to sizes that suffice; a consequence
+ * with more than 65 535 extras returns V2P_ERR_UNSUPPORTED.  Either leaves d as it was before the call, without tables.  caps may be
+ * null; info is filled in either way. */
+int  v2p_decode_tables_build(struct v2p_ctx* ctx, v2p_decode* d, const uint8_t* text,
+                             const uint64_t* csq_text_begin, const uint32_t* csq_text_len, const uint8_t* csq_supported, uint64_t n_consequences,
+                             const v2p_tables_caps* caps, v2p_tables_info* info);
+/* The columns of the last successful build on d, to host arrays sized as the v2p_csq_tables_* accessors say (info gives n_transcripts,
+ * n_extra, n_aa).  tx_begin is the range of the name's occurrence in the consequence of the smallest id that carries it. */
+int  v2p_decode_tables_download(v2p_decode* d, uint64_t* tx_begin, uint32_t* tx_len, uint32_t* rank, uint32_t* flags, uint16_t* mut_pos,
+                                uint16_t* ref_pos, uint32_t* ident, uint32_t* extra_begin, uint32_t* extra, uint8_t* aa, uint64_t* aa_begin,
+                                uint32_t* aa_ref_len);
+/* milliseconds of the last build / download on d (HIP events): the upload of the index's columns, the parse (count, scan, emit), the
+ * names table, the host's sort with the upload of the ranks, the identity classes, the extras (count, scan, emit), the download */
+int  v2p_decode_tables_timing(const v2p_decode* d, float* ms_upload, float* ms_parse, float* ms_names, float* ms_sort, float* ms_ident,
+                              float* ms_extras, float* ms_download);
+
+/* Tables from their columns (e.g. of v2p_decode_tables_download), for every v2p_csq_tables_* / v2p_groups_build_from_tables /
+ * v2p_groups_from_csr call; exported by libv2p_cohort.so.  The columns are copied; text[0, n_text) must stay alive and unchanged while
+ * the tables are used, as for v2p_csq_tables_build.  Returns -1 unless extra_begin and aa_begin ascend from 0, every rank is ~0u or below
+ * n_transcripts, the names lie in the text and ascend strictly bytewise, every mut_ok row has a rank and a type below 22, aa_ref_len
+ * stays inside its consequence's bytes, and every consequence's extras ascend strictly below n_transcripts. */
+int  v2p_csq_tables_from_arrays(const uint8_t* text, uint64_t n_text, uint64_t n_consequences, uint64_t n_transcripts,
+                                const uint64_t* tx_begin, const uint32_t* tx_len, const uint32_t* rank, const uint32_t* flags,
+                                const uint16_t* mut_pos, const uint16_t* ref_pos, const uint32_t* ident, const uint32_t* extra_begin,
+                                const uint32_t* extra, const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len,
+                                v2p_csq_tables** out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

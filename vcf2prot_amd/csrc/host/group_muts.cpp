@@ -389,6 +389,66 @@ int v2p_csq_tables_build(const v2p_vcf_index* x, const uint8_t* text, uint32_t n
     return 0;
 }
 
+int v2p_csq_tables_from_arrays(const uint8_t* text_u8, uint64_t n_text, uint64_t n_csq, uint64_t n_tx, const uint64_t* tx_begin, const uint32_t* tx_len,
+                               const uint32_t* rank, const uint32_t* flags, const uint16_t* mut_pos, const uint16_t* ref_pos, const uint32_t* ident,
+                               const uint32_t* extra_begin, const uint32_t* extra, const uint8_t* aa, const uint64_t* aa_begin,
+                               const uint32_t* aa_ref_len, v2p_csq_tables** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    if ((n_text && !text_u8) || (n_tx && (!tx_begin || !tx_len)) || !extra_begin || !aa_begin ||
+        (n_csq && (!rank || !flags || !mut_pos || !ref_pos || !ident || !aa_ref_len))) return -1;
+    if (extra_begin[0] != 0 || aa_begin[0] != 0) return -1;
+    if ((extra_begin[n_csq] && !extra) || (aa_begin[n_csq] && !aa)) return -1;
+    const char* text = reinterpret_cast<const char*>(text_u8);
+    std::vector<std::string_view> names(n_tx);
+    for (uint64_t r = 0; r < n_tx; ++r) {
+        if (tx_begin[r] > n_text || tx_len[r] > n_text - tx_begin[r]) return -1;
+        names[r] = std::string_view(text + tx_begin[r], tx_len[r]);
+        if (r && !(names[r - 1] < names[r])) return -1;              // sorted and unique, as build_tables leaves them
+    }
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        if (extra_begin[i + 1] < extra_begin[i] || aa_begin[i + 1] < aa_begin[i]) return -1;
+        if (rank[i] != ~0u && rank[i] >= n_tx) return -1;
+        if ((flags[i] & 1u) && (rank[i] == ~0u || (flags[i] >> 8 & 0xffu) >= 22)) return -1;
+        if (aa_ref_len[i] > aa_begin[i + 1] - aa_begin[i]) return -1;
+        for (uint32_t e = extra_begin[i]; e < extra_begin[i + 1]; ++e)
+            if (extra[e] >= n_tx || (e > extra_begin[i] && extra[e] <= extra[e - 1])) return -1;
+    }
+    v2p_csq_tables* t = new (std::nothrow) v2p_csq_tables();
+    if (!t) return -1;
+    Table& T = t->T;
+    T.names = std::move(names);
+    T.tx_begin.assign(tx_begin, tx_begin + n_tx);
+    T.tx_len.assign(tx_len, tx_len + n_tx);
+    T.rank.assign(rank, rank + n_csq);
+    T.flags.assign(flags, flags + n_csq);
+    T.mut_pos.assign(mut_pos, mut_pos + n_csq);
+    T.ref_pos.assign(ref_pos, ref_pos + n_csq);
+    T.ident.assign(ident, ident + n_csq);
+    T.extra_begin.assign(extra_begin, extra_begin + n_csq + 1);
+    T.extra.assign(extra, extra + extra_begin[n_csq]);
+    T.aa.assign(aa, aa + aa_begin[n_csq]);
+    T.aa_begin.assign(aa_begin, aa_begin + n_csq + 1);
+    T.aa_ref_len.assign(aa_ref_len, aa_ref_len + n_csq);
+    T.parsed.resize(n_csq);
+    for (uint64_t i = 0; i < n_csq; ++i) {                           // what parse_csq had left, read back off the columns
+        Parsed& p = T.parsed[i];
+        p.split_ok = rank[i] != ~0u;
+        p.poison = (flags[i] & 2u) != 0;
+        if (p.split_ok) p.tx = T.names[rank[i]];
+        if (!(flags[i] & 1u)) continue;
+        p.mut_ok = true;
+        p.type = int(flags[i] >> 8 & 0xffu);
+        p.ref_pos = ref_pos[i]; p.mut_pos = mut_pos[i];
+        const char* a = reinterpret_cast<const char*>(aa) + aa_begin[i];
+        p.ref_aa.assign(a, aa_ref_len[i]);
+        p.mut_aa.assign(a + aa_ref_len[i], aa_begin[i + 1] - aa_begin[i] - aa_ref_len[i]);
+    }
+    *out = t;
+    return 0;
+}
+
 void v2p_csq_tables_destroy(v2p_csq_tables* t) { delete t; }
 uint64_t v2p_csq_tables_n_consequences(const v2p_csq_tables* t) { return t ? t->T.rank.size() : 0; }
 uint64_t v2p_csq_tables_n_transcripts(const v2p_csq_tables* t) { return t ? t->T.tx_begin.size() : 0; }

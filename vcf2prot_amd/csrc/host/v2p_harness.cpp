@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--device-tables] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            the per-transcript grouping comes from the GPU (v2p_decode_groups); --host-groups, or a list the kernel
 //                                            refuses, sends the whole file through the host grouping on the same tables -- same bytes;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
@@ -362,7 +362,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups, bool device_tasks)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -431,7 +431,37 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     // the file-wide consequence tables, built once: the statistics and the grouping both read them
     const auto tt = clk::now();
     v2p_csq_tables* tb = nullptr;
-    if (v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
+    // --device-tables: built on the device from the text the decode keeps there (include/v2p_frontend.h part 7), downloaded and wrapped;
+    // any failure of the device build falls back to the host build for the whole file: same tables, same bytes
+    bool tables_on_device = false;
+    float tms[7] = {0, 0, 0, 0, 0, 0, 0};
+    v2p_tables_info tinf{};
+    if (device_tables) {
+        const uint64_t n_csq = v2p_vcf_index_n_consequences(idx);
+        auto build = [&](const v2p_tables_caps* caps) {
+            return v2p_decode_tables_build(ctx.raw(), dec, text, v2p_vcf_index_csq_text_begin(idx), v2p_vcf_index_csq_text_len(idx),
+                                           v2p_vcf_index_csq_supported(idx), n_csq, caps, &tinf);
+        };
+        int rc = build(nullptr);
+        if (rc == V2P_ERR_CAPACITY) {                               // automatically chosen sizes: once more with the reported ones
+            const v2p_tables_caps caps{tinf.name_slots, tinf.ident_slots};
+            rc = build(&caps);
+        }
+        if (rc == V2P_OK) {
+            std::vector<uint64_t> c_txb(tinf.n_transcripts + 1), c_aab(n_csq + 1);
+            std::vector<uint32_t> c_txl(tinf.n_transcripts + 1), c_rank(n_csq + 1), c_flags(n_csq + 1), c_ident(n_csq + 1), c_eb(n_csq + 1), c_extra(tinf.n_extra + 1), c_arl(n_csq + 1);
+            std::vector<uint16_t> c_mp(n_csq + 1), c_rp(n_csq + 1);
+            std::vector<uint8_t> c_aa(tinf.n_aa + 1);
+            rc = v2p_decode_tables_download(dec, c_txb.data(), c_txl.data(), c_rank.data(), c_flags.data(), c_mp.data(), c_rp.data(), c_ident.data(),
+                                            c_eb.data(), c_extra.data(), c_aa.data(), c_aab.data(), c_arl.data());
+            if (rc == V2P_OK && v2p_csq_tables_from_arrays(text, vcf.size(), n_csq, tinf.n_transcripts, c_txb.data(), c_txl.data(), c_rank.data(), c_flags.data(),
+                                                           c_mp.data(), c_rp.data(), c_ident.data(), c_eb.data(), c_extra.data(), c_aa.data(), c_aab.data(),
+                                                           c_arl.data(), &tb) == 0)
+                tables_on_device = true;
+            v2p_decode_tables_timing(dec, &tms[0], &tms[1], &tms[2], &tms[3], &tms[4], &tms[5], &tms[6]);
+        }
+    }
+    if (!tables_on_device && v2p_csq_tables_build(idx, text, 0, &tb) != 0) { std::fprintf(stderr, "panicked: the consequence tables could not be built\n"); return 101; }
     const uint64_t T = v2p_csq_tables_n_transcripts(tb);
     const double t_tables = since(tt);
     // (the leading arguments v2p_decode_stats and v2p_decode_groups share -- the decode, the tables, the transcript names -- then each call's own)
@@ -691,6 +721,9 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         std::printf(", \"groups\": {\"path\": \"%s\", \"n_refused\": %llu, \"key_capacity\": %u, \"lds_bytes\": %u, \"ms_upload\": %.3f, \"ms_count\": %.3f, "
                     "\"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f}", device_groups ? "device" : "host", (unsigned long long)ginfo.n_refused,
                     ginfo.key_capacity, ginfo.lds_bytes, gms[0], gms[1], gms[2], gms[3], gms[4]);
+        std::printf(", \"tables\": {\"path\": \"%s\", \"ms_upload\": %.3f, \"ms_parse\": %.3f, \"ms_names\": %.3f, \"ms_sort\": %.3f, \"ms_ident\": %.3f, "
+                    "\"ms_extras\": %.3f, \"ms_download\": %.3f, \"name_slots\": %u, \"ident_slots\": %u}", tables_on_device ? "device" : "host",
+                    tms[0], tms[1], tms[2], tms[3], tms[4], tms[5], tms[6], tinf.name_slots, tinf.ident_slots);
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     };
     if (tasks_on_device) {
@@ -994,7 +1027,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false, device_tables = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -1002,13 +1035,14 @@ int main(int argc, char** argv)
             host_build |= !std::strcmp(argv[i], "--host-build");
             host_groups |= !std::strcmp(argv[i], "--host-groups");
             device_tasks |= !std::strcmp(argv[i], "--device-tasks");
+            device_tables |= !std::strcmp(argv[i], "--device-tables");
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

@@ -13,6 +13,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "../../include/v2p_frontend.h"
 #include "decode_kernels.h"
+#include "csq_tables.h"
 #include "group_csr.h"
 #include "group_stats.h"
 #include "group_tasks.h"
@@ -72,6 +73,15 @@ struct Tasks {
     std::vector<uint64_t> host_first_item;     // [n_haps + 1] every list's first item
     bool ok = false;
     float ms[4] = {0, 0, 0, 0};       // upload of the tables, count, scans, the last emit
+};
+
+// v2p_decode_tables_build: the consequence tables made on the device, until the next build
+struct CsqTablesDev {
+    DevMem rank, flags, mut_pos, ref_pos, ident, extra_begin, extra, aa, aa_begin, aa_ref_len;
+    std::vector<uint64_t> tx_begin; std::vector<uint32_t> tx_len;      // the sorted names (ranges in the text), as the host ranked them
+    uint64_t n = 0, n_extra = 0, n_aa = 0;
+    bool ok = false;
+    float ms[7] = {0, 0, 0, 0, 0, 0, 0};    // upload, parse, names, host sort + rank upload, ident, extras, download
 };
 
 // a status word's reason (decode_kernels.h) as the ABI's error code and the reference's words
@@ -154,6 +164,7 @@ struct v2p_decode {
     Groups groups;
     TaskTables task_tables;
     Tasks tasks;
+    CsqTablesDev csq_tables;          // (made of the text alone: they outlive the lists)
     void drop_lists() { lists = Lists{}; groups = Groups{}; tasks = Tasks{}; }     // (the tables and the text stay)
 };
 
@@ -942,6 +953,237 @@ int v2p_decode_tasks_emit(v2p_ctx* ctx, v2p_decode* d, uint64_t h0, uint64_t h1,
 int v2p_decode_tasks_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit)
 {
     return d ? give_ms(d->tasks.ms, {ms_upload, ms_count, ms_scan, ms_emit}) : V2P_ERR_INVALID_ARG;
+}
+
+int v2p_decode_tables_build(v2p_ctx* ctx, v2p_decode* d, const uint8_t* text, const uint64_t* csq_text_begin, const uint32_t* csq_text_len,
+                            const uint8_t* csq_supported, uint64_t n_csq, const v2p_tables_caps* caps, v2p_tables_info* info)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f("v2p_decode_tables_build");
+    if (!d || d->ctx != ctx || !d->text)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": needs a decode that holds text (v2p_decode_run / v2p_decode_inflate)", -1);
+    if (!info || (d->n_text && !text) || (n_csq && (!csq_text_begin || !csq_text_len || !csq_supported)))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    *info = v2p_tables_info{};
+    if (n_csq >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^32 consequences", -1);
+    for (uint64_t i = 0; i < n_csq; ++i)
+        if (csq_text_begin[i] > d->n_text || csq_text_len[i] > d->n_text - csq_text_begin[i] || csq_text_len[i] >= (1u << 31))
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": consequence range outside the text", int64_t(i));
+    const uint64_t want_names = caps ? caps->name_slots : 0, want_ident = caps ? caps->ident_slots : 0;
+    if ((want_names & (want_names - 1)) || (want_ident & (want_ident - 1)))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": name_slots and ident_slots must be powers of two", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    d->csq_tables = CsqTablesDev{};
+    CsqTablesDev T;                                     // moved onto d when everything succeeded
+    T.n = n_csq;
+    const uint32_t n = uint32_t(n_csq);
+    Events<7> ev;
+    TRY(ev.create(), "hipEventCreate");
+
+    // everything the kernels read is uploaded, zeroed or fully written by an earlier launch
+    DevMem d_begin, d_len, d_sup, d_words, d_aa_count, d_name_begin, d_name_len, d_name_slots, d_name_slot_of, d_rep, d_slot_rank;
+    DevMem d_ident_slots, d_ident_slot_of, d_own, d_label_rank, d_lengths, d_extra_count;
+    TRY(d_begin.alloc((n_csq + 1) * sizeof(uint64_t)), "hipMalloc(csq_text_begin)");
+    TRY(d_len.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(csq_text_len)");
+    TRY(d_sup.alloc(n_csq + 1), "hipMalloc(csq_supported)");
+    TRY(d_words.alloc(8 * sizeof(uint64_t)), "hipMalloc(tables status)");       // status | counters[4] | totals[3]
+    TRY(d_aa_count.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(aa_count)");
+    TRY(d_name_begin.alloc((n_csq + 1) * sizeof(uint64_t)), "hipMalloc(name_begin)");
+    TRY(d_name_len.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(name_len)");
+    TRY(d_name_slot_of.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(name_slot_of)");
+    TRY(d_ident_slot_of.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(ident_slot_of)");
+    TRY(d_own.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(own_label)");
+    TRY(d_label_rank.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(label_rank)");
+    TRY(d_extra_count.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_count)");
+    TRY(T.rank.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(rank)");
+    TRY(T.flags.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(flags)");
+    TRY(T.mut_pos.alloc((n_csq + 1) * sizeof(uint16_t)), "hipMalloc(mut_pos)");
+    TRY(T.ref_pos.alloc((n_csq + 1) * sizeof(uint16_t)), "hipMalloc(ref_pos)");
+    TRY(T.ident.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(ident)");
+    TRY(T.extra_begin.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
+    TRY(T.aa_begin.alloc((n_csq + 1) * sizeof(uint64_t)), "hipMalloc(aa_begin)");
+    TRY(T.aa_ref_len.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(aa_ref_len)");
+    uint64_t* words = d_words.get<uint64_t>();
+    TRY(hipMemsetAsync(words, 0, 8 * sizeof(uint64_t), st), "hipMemset(tables status)");
+    TRY(hipMemsetAsync(words, 0xFF, sizeof(uint64_t), st), "hipMemset(tables status)");
+    TRY(hipMemsetAsync(T.extra_begin.get<void>(), 0, (n_csq + 1) * sizeof(uint32_t), st), "hipMemset(extra_begin)");
+    TRY(hipMemsetAsync(T.aa_begin.get<void>(), 0, (n_csq + 1) * sizeof(uint64_t), st), "hipMemset(aa_begin)");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    if (n_csq) {
+        TRY(hipMemcpyAsync(d_begin.get<void>(), csq_text_begin, n_csq * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(csq_text_begin)");
+        TRY(hipMemcpyAsync(d_len.get<void>(), csq_text_len, n_csq * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(csq_text_len)");
+        TRY(hipMemcpyAsync(d_sup.get<void>(), csq_supported, n_csq, hipMemcpyHostToDevice, st), "H2D(csq_supported)");
+    }
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+
+    CsqArgs a{};
+    a.text = d->text.get<uint8_t>() + 256;
+    a.text_begin = d_begin.get<unsigned long long>(); a.text_len = d_len.get<uint32_t>(); a.supported = d_sup.get<uint8_t>(); a.n = n;
+    a.status = reinterpret_cast<unsigned long long*>(words); a.counters = a.status + 1;
+    unsigned long long* totals = a.status + 5;
+    a.aa_count = d_aa_count.get<uint32_t>(); a.aa_begin = T.aa_begin.get<unsigned long long>();
+    a.flags = T.flags.get<uint32_t>(); a.aa_ref_len = T.aa_ref_len.get<uint32_t>(); a.mut_pos = T.mut_pos.get<uint16_t>(); a.ref_pos = T.ref_pos.get<uint16_t>();
+    a.name_begin = d_name_begin.get<unsigned long long>(); a.name_len = d_name_len.get<uint32_t>();
+    a.name_slot_of = d_name_slot_of.get<uint32_t>(); a.rank = T.rank.get<uint32_t>();
+    a.ident_slot_of = d_ident_slot_of.get<uint32_t>(); a.own_label = d_own.get<uint32_t>(); a.label_rank = d_label_rank.get<uint32_t>();
+    a.ident = T.ident.get<uint32_t>();
+    a.extra_count = d_extra_count.get<uint32_t>(); a.extra_begin = T.extra_begin.get<uint32_t>();
+
+    // parse: count, scan, emit
+    uint64_t host_words[8] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
+    auto read_words = [&]() -> hipError_t {
+        hipError_t e = hipMemcpyAsync(host_words, words, sizeof(host_words), hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    };
+    TRY(launch_csq_parse(a, false, st), "csq_parse_kernel (count)");
+    if (n) TRY(launch_csq_scan(a.aa_count, n, T.aa_begin.get<unsigned long long>(), nullptr, totals + 0, st), "csq_scan_kernel (aa)");
+    TRY(read_words(), "D2H(tables status)");
+    const uint64_t n_split = host_words[1], n_mut = host_words[2];
+    T.n_aa = host_words[5];
+    TRY(T.aa.alloc(T.n_aa + 1), "hipMalloc(aa)");
+    a.aa = T.aa.get<uint8_t>(); a.aa_bytes = T.n_aa;
+    TRY(launch_csq_parse(a, true, st), "csq_parse_kernel (emit)");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+
+    // the two tables' sizes: twice the keys can never fill up
+    const uint64_t auto_names = pow2_ceil(std::max<uint64_t>(64, 2 * n_split)), auto_ident = pow2_ceil(std::max<uint64_t>(64, 2 * n_mut));
+    const uint64_t name_slots = want_names ? want_names : auto_names, ident_slots = want_ident ? want_ident : auto_ident;
+    info->name_slots = uint32_t(name_slots); info->ident_slots = uint32_t(ident_slots);
+    auto too_small = [&](const char* which, int64_t id) {
+        info->name_slots = uint32_t(std::max(name_slots, auto_names)); info->ident_slots = uint32_t(std::max(ident_slots, auto_ident));
+        return ctx_fail(ctx, V2P_ERR_CAPACITY, f + ": the " + which + " table is full; " + std::to_string(info->name_slots) + " name slots and " +
+                        std::to_string(info->ident_slots) + " identity slots suffice", id);
+    };
+    if (name_slots > (1ull << 31) || ident_slots > (1ull << 31)) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^31 slots", -1);
+
+    // names: insert, compact, the host's sort, the ranks
+    TRY(d_name_slots.alloc(name_slots * sizeof(uint32_t)), "hipMalloc(name_slots)");
+    TRY(d_rep.alloc(2 * name_slots * sizeof(uint32_t)), "hipMalloc(representatives)");
+    TRY(d_slot_rank.alloc(name_slots * sizeof(uint32_t)), "hipMalloc(slot_rank)");
+    TRY(hipMemsetAsync(d_name_slots.get<void>(), 0, name_slots * sizeof(uint32_t), st), "hipMemset(name_slots)");
+    TRY(hipMemsetAsync(d_rep.get<void>(), 0, 2 * name_slots * sizeof(uint32_t), st), "hipMemset(representatives)");
+    a.name_slots = d_name_slots.get<uint32_t>(); a.name_mask = uint32_t(name_slots - 1);
+    a.rep_id = d_rep.get<uint32_t>(); a.rep_slot = a.rep_id + name_slots; a.slot_rank = d_slot_rank.get<uint32_t>();
+    TRY(launch_csq_names(a, st), "csq_insert_kernel (names)");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    TRY(read_words(), "D2H(tables status)");
+    if (host_words[0] != ~0ull) return too_small("names", int64_t(host_words[0] >> 8));
+    const uint64_t n_tx = host_words[3];
+    if (n_tx > name_slots || n_tx > n_split) return ctx_fail(ctx, V2P_ERR_HIP, f + ": the names table holds more names than keys", -1);
+    if (n_tx > STATS_MAX_RANKS) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts", -1);
+    std::vector<uint32_t> rep(2 * n_tx), slot_rank(name_slots, ~0u), lengths;
+    if (n_tx) {
+        TRY(hipMemcpy(rep.data(), a.rep_id, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(representatives)");
+        TRY(hipMemcpy(rep.data() + n_tx, a.rep_slot, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H(representatives)");
+    }
+    {
+        // a representative's name is the third '|' field of its consequence, read from the host's text
+        struct Name { std::string_view s; uint32_t slot; };
+        std::vector<Name> names(n_tx);
+        const char* ht = reinterpret_cast<const char*>(text);
+        for (uint64_t k = 0; k < n_tx; ++k) {
+            const uint32_t id = rep[k], slot = rep[n_tx + k];
+            if (id >= n_csq || slot >= name_slots) return ctx_fail(ctx, V2P_ERR_HIP, f + ": a representative outside the consequences", -1);
+            const std::string_view s(ht + csq_text_begin[id], csq_text_len[id]);
+            size_t b = 0;
+            for (int sep = 0; sep < 2 && b != std::string_view::npos; ++sep) { b = s.find('|', b); if (b != std::string_view::npos) ++b; }
+            if (b == std::string_view::npos) return ctx_fail(ctx, V2P_ERR_HIP, f + ": a representative without a transcript field", int64_t(id));
+            const size_t e = std::min(s.find('|', b), s.size());
+            names[k] = Name{s.substr(b, e - b), slot};
+        }
+        std::sort(names.begin(), names.end(), [](const Name& x, const Name& y) { return x.s < y.s; });      // Vec<String>::sort of vcf_tools.rs:126-128
+        T.tx_begin.resize(n_tx); T.tx_len.resize(n_tx);
+        for (uint64_t r = 0; r < n_tx; ++r) {
+            if (r && names[r - 1].s == names[r].s) return ctx_fail(ctx, V2P_ERR_HIP, f + ": one name in two slots", -1);
+            slot_rank[names[r].slot] = uint32_t(r);
+            T.tx_begin[r] = uint64_t(names[r].s.data() - ht); T.tx_len[r] = uint32_t(names[r].s.size());
+            if (T.tx_len[r] && (lengths.empty() || std::find(lengths.begin(), lengths.end(), T.tx_len[r]) == lengths.end())) lengths.push_back(T.tx_len[r]);
+        }
+        std::sort(lengths.begin(), lengths.end());
+    }
+    TRY(d_lengths.alloc((lengths.size() + 1) * sizeof(uint32_t)), "hipMalloc(lengths)");
+    TRY(hipMemcpyAsync(d_slot_rank.get<void>(), slot_rank.data(), name_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(slot_rank)");
+    if (!lengths.empty()) TRY(hipMemcpyAsync(d_lengths.get<void>(), lengths.data(), lengths.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(lengths)");
+    a.lengths = d_lengths.get<uint32_t>(); a.n_lengths = uint32_t(lengths.size());
+    TRY(launch_csq_rank(a, st), "csq_rank_kernel");
+    TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+
+    // identity classes: insert, own labels, scan, ident
+    TRY(d_ident_slots.alloc(ident_slots * sizeof(uint32_t)), "hipMalloc(ident_slots)");
+    TRY(hipMemsetAsync(d_ident_slots.get<void>(), 0, ident_slots * sizeof(uint32_t), st), "hipMemset(ident_slots)");
+    a.ident_slots = d_ident_slots.get<uint32_t>(); a.ident_mask = uint32_t(ident_slots - 1);
+    TRY(launch_csq_ident_insert(a, st), "csq_insert_kernel (ident)");
+    if (n) TRY(launch_csq_scan(a.own_label, n, nullptr, d_label_rank.get<uint32_t>(), totals + 1, st), "csq_scan_kernel (labels)");
+    TRY(launch_csq_ident(a, st), "csq_ident_kernel");
+    TRY(hipEventRecord(ev[5], st), "hipEventRecord");
+
+    // extras: count, scan, emit
+    TRY(launch_csq_extras(a, false, st), "csq_extras_kernel (count)");
+    if (n) TRY(launch_csq_scan(a.extra_count, n, nullptr, T.extra_begin.get<uint32_t>(), totals + 2, st), "csq_scan_kernel (extras)");
+    TRY(read_words(), "D2H(tables status)");
+    if (host_words[0] != ~0ull) {
+        const uint32_t why = uint32_t(host_words[0] & 0xFF);
+        if (why == CSQ_ERR_IDENT_FULL) return too_small("identity", int64_t(host_words[0] >> 8));
+        return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": a consequence names more than 65535 other transcripts", int64_t(host_words[0] >> 8));
+    }
+    T.n_extra = host_words[7];
+    if (T.n_extra >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": more than 2^32 extras", -1);
+    TRY(T.extra.alloc((T.n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
+    TRY(hipMemsetAsync(T.extra.get<void>(), 0, (T.n_extra + 1) * sizeof(uint32_t), st), "hipMemset(extra)");
+    a.extra = T.extra.get<uint32_t>(); a.n_extra = T.n_extra;
+    TRY(launch_csq_extras(a, true, st), "csq_extras_kernel (emit)");
+    TRY(hipEventRecord(ev[6], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    for (int k = 0; k < 6; ++k) (void)hipEventElapsedTime(&T.ms[k], ev[k], ev[k + 1]);
+    info->n_transcripts = n_tx; info->n_extra = T.n_extra; info->n_aa = T.n_aa; info->n_lengths = uint32_t(lengths.size());
+    T.ok = true;
+    d->csq_tables = std::move(T);
+    return V2P_OK;
+}
+
+int v2p_decode_tables_download(v2p_decode* d, uint64_t* tx_begin, uint32_t* tx_len, uint32_t* rank, uint32_t* flags, uint16_t* mut_pos, uint16_t* ref_pos,
+                               uint32_t* ident, uint32_t* extra_begin, uint32_t* extra, uint8_t* aa, uint64_t* aa_begin, uint32_t* aa_ref_len)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* ctx = d->ctx;
+    Guard g(ctx);
+    CsqTablesDev& T = d->csq_tables;
+    if (!T.ok) return ctx_fail(ctx, V2P_ERR_STATE, "v2p_decode_tables_download: no successful v2p_decode_tables_build on this decode", -1);
+    const uint64_t n = T.n, n_tx = T.tx_begin.size();
+    if ((n_tx && (!tx_begin || !tx_len)) || !extra_begin || !aa_begin || (n && (!rank || !flags || !mut_pos || !ref_pos || !ident || !aa_ref_len)) ||
+        (T.n_extra && !extra) || (T.n_aa && !aa))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_tables_download: null argument", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    Events<2> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    auto get = [&](void* dst, const DevMem& src, uint64_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(dst, src.get<void>(), bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    TRY(get(rank, T.rank, n * sizeof(uint32_t)), "D2H(rank)");
+    TRY(get(flags, T.flags, n * sizeof(uint32_t)), "D2H(flags)");
+    TRY(get(mut_pos, T.mut_pos, n * sizeof(uint16_t)), "D2H(mut_pos)");
+    TRY(get(ref_pos, T.ref_pos, n * sizeof(uint16_t)), "D2H(ref_pos)");
+    TRY(get(ident, T.ident, n * sizeof(uint32_t)), "D2H(ident)");
+    TRY(get(extra_begin, T.extra_begin, (n + 1) * sizeof(uint32_t)), "D2H(extra_begin)");
+    TRY(get(extra, T.extra, T.n_extra * sizeof(uint32_t)), "D2H(extra)");
+    TRY(get(aa, T.aa, T.n_aa), "D2H(aa)");
+    TRY(get(aa_begin, T.aa_begin, (n + 1) * sizeof(uint64_t)), "D2H(aa_begin)");
+    TRY(get(aa_ref_len, T.aa_ref_len, n * sizeof(uint32_t)), "D2H(aa_ref_len)");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&T.ms[6], ev[0], ev[1]);
+    if (n_tx) { memcpy(tx_begin, T.tx_begin.data(), n_tx * sizeof(uint64_t)); memcpy(tx_len, T.tx_len.data(), n_tx * sizeof(uint32_t)); }
+    return V2P_OK;
+}
+
+int v2p_decode_tables_timing(const v2p_decode* d, float* ms_upload, float* ms_parse, float* ms_names, float* ms_sort, float* ms_ident, float* ms_extras,
+                             float* ms_download)
+{
+    return d ? give_ms(d->csq_tables.ms, {ms_upload, ms_parse, ms_names, ms_sort, ms_ident, ms_extras, ms_download}) : V2P_ERR_INVALID_ARG;
 }
 
 void v2p_decode_destroy(v2p_decode* d)

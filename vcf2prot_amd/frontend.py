@@ -61,6 +61,9 @@ DECODE_API = {
                                        c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_decode_tasks_emit": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_void_p)]),
     "v2p_decode_tasks_timing": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "v2p_decode_tables_build": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "v2p_decode_tables_download": (c_int, [c_void_p] + [c_void_p] * 12),
+    "v2p_decode_tables_timing": (c_int, [c_void_p] + [POINTER(c_float)] * 7),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -108,6 +111,7 @@ HOST_API = {
     "v2p_csq_tables_aa": (POINTER(c_uint8), [c_void_p]),
     "v2p_csq_tables_aa_begin": (POINTER(c_uint64), [c_void_p]),
     "v2p_csq_tables_aa_ref_len": (POINTER(c_uint32), [c_void_p]),
+    "v2p_csq_tables_from_arrays": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64] + [c_void_p] * 12 + [POINTER(c_void_p)]),
 }
 
 
@@ -128,6 +132,15 @@ class v2p_groups_caps(ctypes.Structure):
 class v2p_groups_info(ctypes.Structure):
     _fields_ = [("n_refused", c_uint64), ("n_groups", c_uint64), ("n_members", c_uint64), ("bitmap_words", c_uint32), ("filter_words", c_uint32),
                 ("key_capacity", c_uint32), ("lds_bytes", c_uint32)]
+
+
+class v2p_tables_caps(ctypes.Structure):
+    _fields_ = [("name_slots", c_uint32), ("ident_slots", c_uint32)]
+
+
+class v2p_tables_info(ctypes.Structure):
+    _fields_ = [("n_transcripts", c_uint64), ("n_extra", c_uint64), ("n_aa", c_uint64), ("n_lengths", c_uint32), ("name_slots", c_uint32),
+                ("ident_slots", c_uint32)]
 
 
 class v2p_tasks_info(ctypes.Structure):
@@ -486,6 +499,39 @@ class CsqTables:
         self.aa_ref_len = _arr(L.v2p_csq_tables_aa_ref_len(h), n, np.uint32)
         self.aa = _arr(L.v2p_csq_tables_aa(h), int(self.aa_begin[-1]), np.uint8)
 
+    COLUMNS = ("transcript_begin", "transcript_len", "rank", "flags", "mut_pos", "ref_pos", "ident", "extra_begin", "extra", "aa", "aa_begin",
+               "aa_ref_len")                                            # the order of v2p_decode_tables_download / v2p_csq_tables_from_arrays
+    COLUMN_DTYPES = (np.uint64, np.uint32, np.uint32, np.uint32, np.uint16, np.uint16, np.uint32, np.uint32, np.uint32, np.uint8, np.uint64, np.uint32)
+
+    path, info = "host", None                                           # from_device sets them: where the tables were made, what was launched
+
+    @classmethod
+    def from_arrays(cls, idx: VcfIndex, **columns) -> "CsqTables":
+        """v2p_csq_tables_from_arrays: tables from their COLUMNS (copied); malformed columns raise V2PError."""
+        t = cls.__new__(cls)
+        L = t._lib = _host()
+        t._idx, t._h = idx, None
+        for k, dt in zip(cls.COLUMNS, cls.COLUMN_DTYPES):
+            setattr(t, k, np.ascontiguousarray(columns[k], dt))
+        t.n_consequences, t.n_transcripts = t.rank.size, t.transcript_begin.size
+        h = c_void_p()
+        rc = L.v2p_csq_tables_from_arrays(idx.text.ctypes.data, idx.text.size, t.n_consequences, t.n_transcripts,
+                                          *[_ptr(getattr(t, k)) for k in cls.COLUMNS], ctypes.byref(h))
+        if rc != 0:
+            raise N.V2PError(rc, "v2p_csq_tables_from_arrays refused the columns")
+        t._h = h
+        return t
+
+    @classmethod
+    def from_device(cls, ctx, idx: VcfIndex, resident, caps=None) -> "CsqTables":
+        """The tables built on the GPU from the text `resident` (InflatedText or ResidentLists of idx) keeps there: v2p_decode_tables_build,
+        v2p_decode_tables_download, v2p_csq_tables_from_arrays.  With automatically chosen sizes a V2P_ERR_CAPACITY is retried once with
+        the sizes the call reported.  .path is "device", .info the sizes and timing_ms."""
+        columns, info = device_tables_columns(ctx, idx, resident, caps)
+        t = cls.from_arrays(idx, **columns)
+        t.path, t.info = "device", info
+        return t
+
     def transcript_names(self):
         return [self._idx._bytes[int(b):int(b) + int(n)].decode() for b, n in zip(self.transcript_begin, self.transcript_len)]
 
@@ -496,6 +542,44 @@ class CsqTables:
 
     def __del__(self):
         self.close()
+
+
+def device_tables_build(ctx, idx: VcfIndex, resident, caps=None) -> dict:
+    """v2p_decode_tables_build alone: the info dict; the tables stay on the decode.  Raises V2PError (its .info holds the reported sizes)."""
+    lib = _hip()
+    info = v2p_tables_info()
+    c = v2p_tables_caps(*caps) if caps is not None else None
+    rc = lib.v2p_decode_tables_build(ctx._h, resident._h, idx.text.ctypes.data if idx.text.size else None, _ptr(idx.csq_text_begin), _ptr(idx.csq_text_len),
+                                     _ptr(idx.csq_supported), idx.n_consequences, ctypes.byref(c) if c is not None else None, ctypes.byref(info))
+    inf = {k: int(getattr(info, k)) for k, _ in v2p_tables_info._fields_}
+    try:
+        _check(ctx, rc)
+    except N.V2PError as e:
+        e.info = inf
+        raise
+    return inf
+
+
+def device_tables_timing(resident) -> dict:
+    t = [c_float() for _ in range(7)]
+    _hip().v2p_decode_tables_timing(resident._h, *[ctypes.byref(x) for x in t])
+    return dict(zip(("upload", "parse", "names", "sort", "ident", "extras", "download"), (x.value for x in t)))
+
+
+def device_tables_columns(ctx, idx: VcfIndex, resident, caps=None):
+    """v2p_decode_tables_build + v2p_decode_tables_download: ({column: array} in CsqTables.COLUMNS order, info dict with timing_ms)."""
+    try:
+        info = device_tables_build(ctx, idx, resident, caps)
+    except N.V2PError as e:
+        if e.code != V2P_ERR_CAPACITY or caps is not None:
+            raise
+        info = device_tables_build(ctx, idx, resident, (e.info["name_slots"], e.info["ident_slots"]))
+    n, t = idx.n_consequences, info["n_transcripts"]
+    sizes = (t, t, n, n, n, n, n, n + 1, info["n_extra"], info["n_aa"], n + 1, n)
+    cols = [np.zeros(k, dt) for k, dt in zip(sizes, CsqTables.COLUMN_DTYPES)]
+    _check(ctx, _hip().v2p_decode_tables_download(resident._h, *[_ptr(c) for c in cols]))
+    info["timing_ms"] = device_tables_timing(resident)
+    return dict(zip(CsqTables.COLUMNS, cols)), info
 
 
 def device_groups_csr(ctx, resident: ResidentLists, tables, caps=None):

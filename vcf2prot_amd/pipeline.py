@@ -167,9 +167,26 @@ def _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes
     return out
 
 
+def _csq_tables(ctx, idx, resident, on_device, report):
+    """The file-wide consequence tables: built on the device when asked for, on the host otherwise and whenever the device build fails."""
+    import time
+    t0 = time.perf_counter()
+    tables = None
+    if on_device:
+        try:
+            tables = CsqTables.from_device(ctx, idx, resident)
+        except N.V2PError:
+            tables = None
+    if tables is None:
+        tables = CsqTables(idx)
+    if report is not None:
+        report["tables"] = dict(tables.info or {}, path=tables.path, ms=(time.perf_counter() - t0) * 1e3)
+    return tables
+
+
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
                  device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False, host_groups: bool = False,
-                 groups_caps=None, report: dict = None, device_tasks: bool = False) -> Dict[str, bytes]:
+                 groups_caps=None, report: dict = None, device_tasks: bool = False, device_tables: bool = False) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
@@ -187,7 +204,10 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     device_tasks (opt-in): steps 4a / 4b run on the GPU too, on the grouped CSR where the grouping kernel left it (_device_tasks): the
     slices are cut from the count, emitted as resident streams and built and executed one after the other -- same bytes.  It needs the
     device build and the device grouping: with device_build=False, with host_groups, or when the grouping kernel refuses a list, the host
-    loop below runs the whole file."""
+    loop below runs the whole file.
+    device_tables (opt-in): the file-wide consequence tables are built on the GPU from the text the decode keeps there
+    (CsqTables.from_device, include/v2p_frontend.h part 7) -- same tables, same bytes.  Any failure of the device build falls back to the
+    host build for the whole file; report receives {"tables": {"path": "device" | "host", "ms": ..., ...}}."""
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
     fmt, inflated = input_format(vcf), None
@@ -205,7 +225,7 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     resident = decode_resident(ctx, idx, inflated)
     try:
         n_haplotypes = resident.n_haplotypes
-        tables = CsqTables(idx)
+        tables = _csq_tables(ctx, idx, resident, device_tables, report)
         try:
             if device_tasks and device_build and not host_groups:
                 out = _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report)
