@@ -51,7 +51,9 @@ struct v2p_ctx;                                   /* include/vcf2prot_hip.h */
 #define V2P_ERR_COLUMNS         (-23)   /* vcf_ds.rs:148           record with a different number of sample columns:
                                            more -> the reference panics; fewer -> it silently pairs fields with the
                                            wrong consequences, which this engine refuses                             */
-#define V2P_ERR_FIELD_TOO_LONG  (-24)   /* a sample column whose text after the last ':' exceeds 4 KiB             */
+#define V2P_ERR_FIELD_TOO_LONG  (-24)   /* a sample column with 4096 bytes or more after its last ':'; also a column without
+                                           ':' of 4096 bytes or more that is not the record's first (the reference reads
+                                           that one as "no consequences").  The same limit at every record width        */
 #define V2P_ERR_CAPACITY        (-25)   /* raw launcher: ids / multi-word capacity too small; v2p_decode_tables_build: a table
                                            with fewer slots than keys (needed size reported) */
 #define V2P_ERR_VCF_FORMAT      (-26)   /* readers.rs:113-150      no "#CHROM" line, fewer than 10 columns, no records */

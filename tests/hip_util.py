@@ -1,4 +1,4 @@
-"""Device buffers for tests that call the launch-level C ABI (v2p_stitch_launch, v2p_bgzf_inflate_launch) directly: the HIP runtime
+"""Device buffers for tests that call the launch-level C ABI (v2p_stitch_launch, v2p_bgzf_inflate_launch, v2p_decode_launch) directly: the HIP runtime
 through ctypes, no torch (initialising torch after the library has taken the device fails on the test boxes)."""
 import ctypes
 
@@ -70,3 +70,53 @@ def inflate_launch(z: bytes, mb, ob, out_offset: int = 0, guard: int = 4096):
         b.free()
     guards = bool((host[:lo + first] == 0xA5).all() and (host[lo + total:] == 0xA5).all() and (words[n + 1:] == 0x5A5A5A5A).all())
     return host[lo:lo + total], words[:n + 1], guards
+
+
+def decode_launch(text: bytes, row_begin, row_end, n_samples: int, csq_begin, csq_supported, ids_capacity: int, ovf_words: int = 8192,
+                  misalign: int = 0, guard: int = 4096):
+    """v2p_decode_launch (include/v2p_frontend.h) on device buffers of the HIP runtime, as its contract words them: d_text sits `misalign`
+    bytes behind a 16-byte boundary with exactly 16 bytes of padding either side, and the padding is text that would decode
+    (":7\\t:7\\t..."); the workspace is exactly v2p_decode_workspace_bytes long; d_hap_begin, d_ids (ids_capacity entries) and the two
+    status words lie between guard regions of 0xA5, the workspace has one behind it, and all of them start as 0xA5 (status[0] = ~0).
+    Returns (status [2], hap_begin [2 n + 1], ids [ids_capacity], every guard untouched)."""
+    import decode_rule as R
+    from vcf2prot_amd import frontend
+    lib = frontend._hip()
+    n_rec, n_haps = len(row_begin), 2 * n_samples
+    assert 0 <= misalign < 16 and guard % 256 == 0
+    pad = (b":7\t" * 6)[:16]
+    host = np.full(guard + misalign + 16 + len(text) + 16 + guard, 0xA5, np.uint8)
+    t0 = guard + misalign + 16
+    host[t0 - 16:t0 + len(text) + 16] = np.frombuffer(pad + text + pad, np.uint8)
+    d_text = DevBuf.of(host, pad=256)
+    assert (d_text.ptr + t0) % 16 == misalign
+    d_rows = DevBuf.of(np.concatenate([np.asarray(row_begin, np.uint64), np.asarray(row_end, np.uint64)]))
+    tables = [np.asarray(csq_begin, np.uint32), R.sup_pairs(csq_begin, csq_supported), R.sup_bits(csq_supported)]
+    d_csq = DevBuf.of(np.concatenate(tables))
+    ws = int(lib.v2p_decode_workspace_bytes(n_rec, n_samples, ovf_words))
+    d_work = DevBuf(ws + guard, pad=256, fill=0xA5)
+    assert d_work.ptr % 256 == 0
+    # [guard | hap_begin | guard | ids | guard | status | guard]
+    hb_at = guard
+    ids_at = hb_at + 8 * (n_haps + 1) + guard
+    st_at = ids_at + (4 * ids_capacity + 7) // 8 * 8 + guard
+    out = np.full(st_at + 16 + guard, 0xA5, np.uint8)
+    out[st_at:st_at + 8] = 0xFF
+    d_out = DevBuf.of(out, pad=256)
+    rc = lib.v2p_decode_launch(None, d_text.ptr + t0, len(text), d_rows.ptr, d_rows.ptr + 8 * n_rec, n_rec, n_samples,
+                               d_csq.ptr, d_csq.ptr + 4 * (n_rec + 1), d_csq.ptr + 4 * (2 * n_rec + 1),
+                               d_work.ptr, ovf_words, d_out.ptr + hb_at, d_out.ptr + ids_at, ids_capacity, d_out.ptr + st_at, 15)
+    sync = hip().hipDeviceSynchronize()
+    if sync != 0:                                                     # a fault: nothing more goes to this GPU from this process
+        import pytest
+        pytest.exit(f"v2p_decode_launch left HIP error {sync} behind", returncode=3)
+    assert rc == 0, rc
+    got, work = d_out.download(), d_work.download()
+    for b in (d_text, d_rows, d_csq, d_work, d_out):
+        b.free()
+    status = got[st_at:st_at + 16].view(np.uint64).copy()
+    hap_begin = got[hb_at:hb_at + 8 * (n_haps + 1)].view(np.uint64).copy()
+    ids = got[ids_at:ids_at + 4 * ids_capacity].view(np.uint32).copy()
+    guards = all(bool((x == 0xA5).all()) for x in (got[:hb_at], got[hb_at + 8 * (n_haps + 1):ids_at], got[ids_at + 4 * ids_capacity:st_at],
+                                                   got[st_at + 16:], work[ws:]))
+    return status, hap_begin, ids, guards

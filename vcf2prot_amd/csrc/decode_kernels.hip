@@ -138,7 +138,8 @@ __device__ __forceinline__ uint32_t filter_word(uint32_t w, uint32_t base, const
 // The parser reads the column's last eight bytes from the text in memory (one unaligned load per entry; the record has just been
 // read) and they settle what the fast path settles (a tail of at most seven digits, '.', no ':' in reach); anything else -- long
 // numbers, comma lists, multi-word masks -- goes back through the text byte by byte, which therefore no longer depends on what the
-// ring still holds: the tail of a column is searched for its ':' over exactly 4 KiB.
+// ring still holds: the tail of a column is searched for its ':' over exactly 4 KiB (4096 bytes or more after the last ':' are refused, and
+// so is a column of that length without any ':' unless it is the row's first).
 template <uint32_t BS>
 __global__ __launch_bounds__(BS) void parse_rows_kernel(DecodeArgs a)
 {
@@ -220,7 +221,13 @@ __global__ __launch_bounds__(BS) void parse_rows_kernel(DecodeArgs a)
                     if (c == '\t') break;
                     --q;
                 }
-                if (!colon && q == lo && lo > q0) err = DEC_FIELD_TOO_LONG;
+                if (!colon && q == lo && lo > q0) {
+                    // no ':' or tab within TAIL_MAX bytes.  The row's first column has no tab before it: it begins at q0, and without a ':'
+                    // anywhere it is a column without a mask, whatever its length (nothing); with one further back its tail is too long
+                    bool far_colon = f != 0u;
+                    for (uint32_t k = lo; k > q0 && !far_colon; --k) far_colon = gtext[k - 1u] == ':';
+                    if (far_colon) err = DEC_FIELD_TOO_LONG;
+                }
             }
             if (colon) {
                 const uint32_t s = q;                                          // tail = gtext[s, p)

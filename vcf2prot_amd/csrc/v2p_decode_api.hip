@@ -94,7 +94,7 @@ Reason reason_of(uint32_t r)
         case DEC_MASK_PARSE: return {V2P_ERR_MASK_PARSE, "bit mask word is not a u32 (MaskDecoder.rs:41,47)"};
         case DEC_MASK_INDEX: return {V2P_ERR_MASK_INDEX, "bit mask selects a consequence the record does not have (vcf_ds.rs:321)"};
         case DEC_COLUMNS: return {V2P_ERR_COLUMNS, "record does not have one column per proband (vcf_ds.rs:148)"};
-        case DEC_FIELD_TOO_LONG: return {V2P_ERR_FIELD_TOO_LONG, "sample column longer than the 4 KiB window after its last ':'"};
+        case DEC_FIELD_TOO_LONG: return {V2P_ERR_FIELD_TOO_LONG, "sample column with 4096 bytes or more after its last ':' (or, not the record's first, without any ':')"};
         case DEC_CAPACITY: return {V2P_ERR_CAPACITY, "multi-word / id capacity exceeded"};
         default: return {V2P_ERR_INVALID_ARG, "decode error"};
     }
@@ -228,7 +228,7 @@ static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begi
     uint64_t row_bytes = 0;
     for (uint64_t r = 0; r < n_records; ++r) row_bytes += row_end[r] - row_begin[r];
     const uint64_t avg_row = row_bytes / n_records;
-    uint32_t parse_threads = avg_row <= 1536 ? 64u : (avg_row <= 3072 ? 128u : 256u);     // a tile = 16 bytes per thread
+    const uint32_t parse_threads = avg_row <= 1536 ? 64u : (avg_row <= 3072 ? 128u : 256u);     // a tile = 16 bytes per thread
     int rc = V2P_OK;
     bool done = false;                                  // set only after the emit pass: a retry that runs out of attempts is an error
     std::string last_reason = "decode: retries exhausted";
@@ -257,7 +257,6 @@ static int decode_resident(v2p_ctx* ctx, v2p_decode* d, const uint64_t* row_begi
             const Reason why = reason_of(reason);
             last_reason = std::string("decode: ") + why.text + " (after a retry)";
             if (reason == DEC_CAPACITY && status[1] > ovf_words && status[1] < (1ull << 31)) { ovf_words = status[1]; continue; }
-            if (reason == DEC_FIELD_TOO_LONG && parse_threads != 256u) { parse_threads = 256u; continue; }     // the narrow kernels look back 1-2 KiB only
             rc = ctx_fail(ctx, why.code, std::string("decode: ") + why.text + " at record " +
                           std::to_string((status[0] >> 8) / n_samples) + ", sample " + std::to_string((status[0] >> 8) % n_samples),
                           int64_t(status[0] >> 8));
