@@ -26,9 +26,13 @@
  *   (7) the tables of (4) on the device   v2p_decode_tables_build makes the file-wide consequence tables from the text a decode keeps resident;
  *                         v2p_csq_tables_from_arrays (host) wraps the downloaded columns into the v2p_csq_tables of (4).
  *
+ *   (8) the record index of (1) on the device   v2p_decode_index_build makes the index's columns from the text a decode keeps resident
+ *                         (v2p_decode_upload puts a flat text there); v2p_vcf_index_from_arrays (host) wraps the downloaded columns into the
+ *                         v2p_vcf_index of (1).
+ *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
  * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4), the v2p_decode_groups* calls of (5), the v2p_decode_tasks* calls of
- * (6) and the v2p_decode_tables* calls of (7); libv2p_cohort.so (plain C++) exports the rest.
+ * (6), the v2p_decode_tables* calls of (7) and the v2p_decode_upload / v2p_decode_index* calls of (8); libv2p_cohort.so (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -399,6 +403,47 @@ int  v2p_csq_tables_from_arrays(const uint8_t* text, uint64_t n_text, uint64_t n
                                 const uint16_t* mut_pos, const uint16_t* ref_pos, const uint32_t* ident, const uint32_t* extra_begin,
                                 const uint32_t* extra, const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len,
                                 v2p_csq_tables** out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (8) the record index of (1) built on the device, from the text a decode keeps resident.  The rule is v2p_vcf_index_build's; every
+ * column compares equal to it, and so does the verdict on a file it refuses.  Only the "#CHROM" line is copied to the host, where the
+ * host's own header rule runs on it.  Opt-in for the callers of this repository (pipeline.vcf_to_fasta(device_index=True),
+ * --device-index): a file the device index refuses is refused, as the host index refuses it; there is no fallback.
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* flat text made resident without lists: the state v2p_decode_inflate leaves (v2p_decode_run_inflated, v2p_decode_tables_build and
+ * v2p_decode_index_build take it) */
+int  v2p_decode_upload(struct v2p_ctx* ctx, const uint8_t* text, uint64_t n_text, v2p_decode** out);
+
+typedef struct v2p_index_info {
+    uint64_t n_lines, n_records, n_consequences, n_samples;
+    uint64_t header_begin, header_len;     /* the "#CHROM" line in the text */
+    uint32_t tile_bytes, line_threads;     /* what was launched */
+} v2p_index_info;
+
+/* Builds the index on the device of d, which must hold text (with or without lists; lists stay).  On a file the host index refuses
+ * returns V2P_ERR_VCF_FORMAT with v2p_last_error(ctx) = the host's message and v2p_last_error_index(ctx) = the 0-based index of the line
+ * the host's loop would have stopped at (the smallest failing line, the header line's included), or -1 for an empty file, a file
+ * without header line and a file without records.  A failed build leaves d without an index; a successful one keeps the columns on d
+ * until the next build or v2p_decode_destroy.  info is filled in on success (tile_bytes and line_threads either way). */
+int  v2p_decode_index_build(struct v2p_ctx* ctx, v2p_decode* d, v2p_index_info* info);
+/* The columns of the last successful build on d, to host arrays sized as the v2p_vcf_index_* accessors say (info gives the sizes;
+ * csq_begin has n_records + 1 entries).  V2P_ERR_STATE without an index. */
+int  v2p_decode_index_download(v2p_decode* d, uint64_t* sample_begin, uint64_t* sample_len, uint64_t* row_begin, uint64_t* row_end,
+                               uint32_t* csq_begin, uint8_t* csq_supported, uint64_t* csq_text_begin, uint32_t* csq_text_len);
+/* milliseconds of the last build / download on d (HIP events): the line pass (count, scan, emit), the record pass's count, its two
+ * scans, its emit, the download.  V2P_ERR_STATE without an index. */
+int  v2p_decode_index_timing(const v2p_decode* d, float* ms_lines, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download);
+
+/* An index from its columns (e.g. of v2p_decode_index_download), for every v2p_vcf_index_* / v2p_groups_build / v2p_csq_tables_build
+ * call; exported by libv2p_cohort.so.  The columns are copied.  Returns -1 (and *out with v2p_vcf_index_error set, to be destroyed)
+ * unless there is at least one sample and one record, every range lies in [0, n_text], row_begin[r] <= row_end[r] < row_begin[r + 1],
+ * csq_begin ascends from 0 to n_consequences with at least one consequence per record, the consequence ranges ascend and each ends
+ * before its record's row_begin, and every csq_supported is 0 or 1. */
+int  v2p_vcf_index_from_arrays(uint64_t n_text, uint64_t n_samples, const uint64_t* sample_begin, const uint64_t* sample_len,
+                               uint64_t n_records, const uint64_t* row_begin, const uint64_t* row_end, const uint32_t* csq_begin,
+                               uint64_t n_consequences, const uint8_t* csq_supported, const uint64_t* csq_text_begin,
+                               const uint32_t* csq_text_len, v2p_vcf_index** out);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

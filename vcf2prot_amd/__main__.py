@@ -1,4 +1,4 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [--host-groups] [--device-tasks] [--device-tables] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
@@ -24,6 +24,7 @@ def main() -> int:
     ap.add_argument("--write_bgzf", action="store_true", help="BGZF (bgzip's format) compressed on the GPU, plus .gzi; not with -c")
     ap.add_argument("--host-groups", action="store_true", help="group consequences per transcript on the host instead of on the GPU (same bytes; for A/B runs)")
     ap.add_argument("--device-tables", action="store_true", help="build the file-wide consequence tables on the GPU too, from the resident VCF text (same bytes; opt-in)")
+    ap.add_argument("--device-index", action="store_true", help="build the VCF record index on the GPU too, from the resident VCF text (same bytes; opt-in)")
     ap.add_argument("--device-tasks", action="store_true", help="generate instructions and Task vectors (steps 4a / 4b) on the GPU too (same bytes; opt-in)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
@@ -50,6 +51,8 @@ def main() -> int:
         cmd.append("--device-tasks")
     if a.device_tables:
         cmd.append("--device-tables")
+    if a.device_index:
+        cmd.append("--device-index")
     return subprocess.run(cmd).returncode
 
 

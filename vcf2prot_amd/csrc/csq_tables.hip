@@ -13,26 +13,14 @@
 // Every probe loop is bounded by the table's slot count: a full table sets the status word and the lane goes on.  No store goes past
 // an array's size.
 #include "csq_tables.h"
+#include "csq_sup_names.h"
 
 namespace v2p {
 namespace {
 
 constexpr uint32_t HASH_B = 0x01000193u;
 
-__constant__ char SUP_NAME[22][36] = {
-    "missense", "*missense", "frameshift", "*frameshift", "inframe_insertion", "*inframe_insertion", "inframe_deletion",
-    "*inframe_deletion", "stop_gained", "stop_lost", "*missense&inframe_altering", "*frameshift&stop_retained",
-    "*stop_gained&inframe_altering", "frameshift&stop_retained", "inframe_deletion&stop_retained",
-    "inframe_insertion&stop_retained", "stop_gained&inframe_altering", "start_lost", "*stop_gained", "stop_lost&frameshift",
-    "missense&inframe_altering", "start_lost&splice_region"};
 __constant__ uint8_t START_LOST_AA[5] = {'1', 'M', '>', '1', '*'};        // text_parser.rs:48-57
-
-__device__ inline bool lit_eq(const uint8_t* p, uint32_t n, const char* lit)
-{
-    uint32_t k = 0;
-    for (; k < n; ++k) if (!lit[k] || uint8_t(lit[k]) != p[k]) return false;
-    return lit[k] == 0;
-}
 
 __device__ inline bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n)
 {
@@ -117,8 +105,7 @@ __device__ inline void parse_csq(const uint8_t* s, uint32_t n, Parsed& p)
         return;
     }
     p.name_off = f2b; p.name_len = f2e - f2b;                        // split_ok
-    int type = -1;
-    for (int t = 0; t < 22; ++t) if (lit_eq(s, f0e, SUP_NAME[t])) { type = t; break; }
+    const int type = sup_type_index(s, f0e);
     if (type < 0) return;
     uint32_t gt = aa_n, n_gt = 0;
     for (uint32_t k = 0; k < aa_n; ++k) if (aa[k] == '>') { if (!n_gt) gt = k; ++n_gt; }

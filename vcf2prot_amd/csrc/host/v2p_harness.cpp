@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--device-tables] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            the per-transcript grouping comes from the GPU (v2p_decode_groups); --host-groups, or a list the kernel
 //                                            refuses, sends the whole file through the host grouping on the same tables -- same bytes;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
@@ -362,7 +362,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -409,7 +409,39 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     const double t_inflate = since(t0); t0 = clk::now();
     const uint8_t* text = reinterpret_cast<const uint8_t*>(vcf.data());
     v2p_vcf_index* idx = nullptr;
-    if (v2p_vcf_index_build(text, vcf.size(), &idx) != 0) {
+    // --device-index: built on the device from the resident text (include/v2p_frontend.h part 8) -- a flat text is uploaded first and the
+    // decode below runs on the same handle -- downloaded and wrapped.  A file the index refuses is refused with the host's words; no fallback
+    float xms[5] = {0, 0, 0, 0, 0};
+    double t_resident = 0;                                          // the context and the upload of a text that was not resident yet
+    if (device_index) {
+        const auto tr = clk::now();
+        if (!ctx_box) ctx_box.reset(new GpuContext());
+        v2p_ctx* c = ctx_box->raw();
+        if (!dec && v2p_decode_upload(c, text, vcf.size(), &dec) != V2P_OK) { std::fprintf(stderr, "%s\n", v2p_last_error(c)); return 101; }
+        t_resident = since(tr);
+        v2p_index_info xinf{};
+        const int rc = v2p_decode_index_build(c, dec, &xinf);
+        if (rc != V2P_OK) {
+            std::fprintf(stderr, rc == V2P_ERR_VCF_FORMAT ? "reading the file failed: %s\n" : "%s\n", v2p_last_error(c));
+            v2p_decode_destroy(dec);
+            return 101;
+        }
+        std::vector<uint64_t> x_sb(xinf.n_samples + 1), x_sl(xinf.n_samples + 1), x_rb(xinf.n_records + 1), x_re(xinf.n_records + 1), x_tb(xinf.n_consequences + 1);
+        std::vector<uint32_t> x_cb(xinf.n_records + 1), x_tl(xinf.n_consequences + 1);
+        std::vector<uint8_t> x_sup(xinf.n_consequences + 1);
+        if (v2p_decode_index_download(dec, x_sb.data(), x_sl.data(), x_rb.data(), x_re.data(), x_cb.data(), x_sup.data(), x_tb.data(), x_tl.data()) != V2P_OK) {
+            std::fprintf(stderr, "%s\n", v2p_last_error(c));
+            v2p_decode_destroy(dec);
+            return 101;
+        }
+        if (v2p_vcf_index_from_arrays(vcf.size(), xinf.n_samples, x_sb.data(), x_sl.data(), xinf.n_records, x_rb.data(), x_re.data(), x_cb.data(),
+                                      xinf.n_consequences, x_sup.data(), x_tb.data(), x_tl.data(), &idx) != 0) {
+            std::fprintf(stderr, "the device index's columns were refused: %s\n", v2p_vcf_index_error(idx));
+            v2p_decode_destroy(dec);
+            return 101;
+        }
+        v2p_decode_index_timing(dec, &xms[0], &xms[1], &xms[2], &xms[3], &xms[4]);
+    } else if (v2p_vcf_index_build(text, vcf.size(), &idx) != 0) {
         std::fprintf(stderr, "reading the file failed: %s\n", v2p_vcf_index_error(idx));
         if (dec) v2p_decode_destroy(dec);
         return 101;
@@ -724,6 +756,8 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         std::printf(", \"tables\": {\"path\": \"%s\", \"ms_upload\": %.3f, \"ms_parse\": %.3f, \"ms_names\": %.3f, \"ms_sort\": %.3f, \"ms_ident\": %.3f, "
                     "\"ms_extras\": %.3f, \"ms_download\": %.3f, \"name_slots\": %u, \"ident_slots\": %u}", tables_on_device ? "device" : "host",
                     tms[0], tms[1], tms[2], tms[3], tms[4], tms[5], tms[6], tinf.name_slots, tinf.ident_slots);
+        std::printf(", \"index\": {\"path\": \"%s\", \"ms_lines\": %.3f, \"ms_count\": %.3f, \"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f, "
+                    "\"s_context_and_upload\": %.4f}", device_index ? "device" : "host", xms[0], xms[1], xms[2], xms[3], xms[4], t_resident);
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     };
     if (tasks_on_device) {
@@ -1027,7 +1061,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false, device_tables = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -1036,13 +1070,14 @@ int main(int argc, char** argv)
             host_groups |= !std::strcmp(argv[i], "--host-groups");
             device_tasks |= !std::strcmp(argv[i], "--device-tasks");
             device_tables |= !std::strcmp(argv[i], "--device-tables");
+            device_index |= !std::strcmp(argv[i], "--device-index");
             write_all |= !std::strcmp(argv[i], "--write-all") || !std::strcmp(argv[i], "-a");
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

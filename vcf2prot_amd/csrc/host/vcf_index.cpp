@@ -81,7 +81,7 @@ int v2p_vcf_index_build(const uint8_t* text_u8, uint64_t n, v2p_vcf_index** out)
     v2p_vcf_index* x = new (std::nothrow) v2p_vcf_index();
     if (!x) return -1;
     *out = x;                                        // kept on failure so that the message can be read
-    if (!text_u8 || !n) return fail(x, "the provided file is empty");                     // readers.rs:109-112
+    if (!text_u8 || !n) return fail(x, v2p_frontend::MSG_EMPTY_FILE);                     // readers.rs:109-112
     const char* text = reinterpret_cast<const char*>(text_u8);
     bool have_header = false;
     x->csq_begin.push_back(0);
@@ -97,18 +97,7 @@ int v2p_vcf_index_build(const uint8_t* text_u8, uint64_t n, v2p_vcf_index** out)
         if (!line.empty() && line[0] == '#') {
             if (!have_header && line.substr(0, 6) == "#CHROM") {                             // readers.rs:116-127
                 have_header = true;
-                if (!line.empty() && line.back() == '\t') line.remove_suffix(1);             // readers.rs:128-131
-                std::vector<std::pair<uint64_t, uint64_t>> cols;
-                size_t p = 0;
-                while (p <= line.size()) {
-                    size_t t = line.find('\t', p);
-                    if (t == std::string_view::npos) t = line.size();
-                    cols.emplace_back(line0 + p, t - p);
-                    p = t + 1;
-                }
-                if (cols.size() < 9) return fail(x, "The provided file does not contain the minimum number of columns");   // readers.rs:138-143 (+ drain(0..9))
-                for (size_t i = 9; i < cols.size(); ++i) { x->sample_begin.push_back(cols[i].first); x->sample_len.push_back(cols[i].second); }
-                if (x->sample_begin.empty()) return fail(x, "The file does not contain any patients!!, after removing the mandatory columns");
+                if (const char* why = v2p_frontend::header_samples(line, line0, x->sample_begin, x->sample_len)) return fail(x, why);
             }
             continue;
         }
@@ -121,11 +110,11 @@ int v2p_vcf_index_build(const uint8_t* text_u8, uint64_t n, v2p_vcf_index** out)
             tabs[nt++] = uint64_t(t - line.data());
             p = tabs[nt - 1] + 1;
         }
-        if (nt < 7) return fail(x, "record line with fewer than 8 columns (readers.rs:187 would abort)");
+        if (nt < 7) return fail(x, v2p_frontend::MSG_FEW_COLUMNS);
         const uint64_t info_b = tabs[6] + 1, info_e = nt >= 8 ? tabs[7] : line.size();
         std::string_view info = line.substr(info_b, info_e - info_b);
         if (!record_supported(info)) continue;
-        if (nt < 9) return fail(x, "supported record without sample columns (vcf_ds.rs:148 would abort)");
+        if (nt < 9) return fail(x, v2p_frontend::MSG_NO_SAMPLE_COLUMNS);
         x->row_begin.push_back(line0 + tabs[8] + 1);
         x->row_end.push_back(line0 + line.size());
         // vcf_ds.rs:78: rec.split("BCSQ=")[1] -- from the first "BCSQ=" to the next one or the end of the column
@@ -144,11 +133,53 @@ int v2p_vcf_index_build(const uint8_t* text_u8, uint64_t n, v2p_vcf_index** out)
             x->csq_supported.push_back(sup_type_index(csq.substr(0, csq.find('|'))) >= 0 ? 1 : 0);   // text_parser::get_type + SUP_TYPE
             p = c + 1;
         }
-        if (x->csq_supported.size() >= 0xFFFFFFF0ull) return fail(x, "more than 2^32 consequences");
+        if (x->csq_supported.size() >= 0xFFFFFFF0ull) return fail(x, v2p_frontend::MSG_TOO_MANY_CSQ);
         x->csq_begin.push_back(uint32_t(x->csq_supported.size()));
     }
-    if (!have_header) return fail(x, "Could not find a header line");                        // readers.rs:122-125
-    if (x->row_begin.empty()) return fail(x, "Could not extract any records from the provided file!!");   // readers.rs:175-178
+    if (!have_header) return fail(x, v2p_frontend::MSG_NO_HEADER);                        // readers.rs:122-125
+    if (x->row_begin.empty()) return fail(x, v2p_frontend::MSG_NO_RECORDS);   // readers.rs:175-178
+    return 0;
+}
+
+int v2p_vcf_index_from_arrays(uint64_t n_text, uint64_t n_samples, const uint64_t* sample_begin, const uint64_t* sample_len,
+                              uint64_t n_records, const uint64_t* row_begin, const uint64_t* row_end, const uint32_t* csq_begin,
+                              uint64_t n_csq, const uint8_t* csq_supported, const uint64_t* csq_text_begin, const uint32_t* csq_text_len,
+                              v2p_vcf_index** out)
+{
+    if (!out) return -1;
+    *out = nullptr;
+    v2p_vcf_index* x = new (std::nothrow) v2p_vcf_index();
+    if (!x) return -1;
+    *out = x;                                        // kept on failure so that the message can be read
+    auto refuse = [&](const char* why) { x->error = std::string("v2p_vcf_index_from_arrays: ") + why; return -1; };
+    if (!n_samples || !n_records) return refuse("needs at least one sample and one record");
+    if (!sample_begin || !sample_len || !row_begin || !row_end || !csq_begin || (n_csq && (!csq_supported || !csq_text_begin || !csq_text_len)))
+        return refuse("null argument");
+    auto inside = [&](uint64_t b, uint64_t len) { return b <= n_text && len <= n_text - b; };
+    for (uint64_t s = 0; s < n_samples; ++s)
+        if (!inside(sample_begin[s], sample_len[s])) return refuse("a sample name outside the text");
+    if (csq_begin[0] != 0 || csq_begin[n_records] != n_csq) return refuse("csq_begin must run from 0 to n_consequences");
+    for (uint64_t r = 0; r < n_records; ++r) {
+        if (row_begin[r] > row_end[r] || row_end[r] > n_text) return refuse("a record range outside the text");
+        if (r + 1 < n_records && row_end[r] >= row_begin[r + 1]) return refuse("record ranges must ascend");
+        if (csq_begin[r + 1] <= csq_begin[r] || csq_begin[r + 1] > n_csq) return refuse("csq_begin must ascend, with at least one consequence per record");
+    }
+    for (uint64_t r = 0; r < n_records; ++r)
+        for (uint64_t i = csq_begin[r]; i < csq_begin[r + 1]; ++i) {
+            if (!inside(csq_text_begin[i], csq_text_len[i])) return refuse("a consequence range outside the text");
+            const uint64_t end = csq_text_begin[i] + csq_text_len[i];
+            if (i + 1 < n_csq && end > csq_text_begin[i + 1]) return refuse("consequence ranges must ascend");
+            if (end > row_begin[r]) return refuse("a consequence must end before its record's sample columns");
+            if (csq_supported[i] > 1) return refuse("csq_supported must be 0 or 1");
+        }
+    x->sample_begin.assign(sample_begin, sample_begin + n_samples);
+    x->sample_len.assign(sample_len, sample_len + n_samples);
+    x->row_begin.assign(row_begin, row_begin + n_records);
+    x->row_end.assign(row_end, row_end + n_records);
+    x->csq_begin.assign(csq_begin, csq_begin + n_records + 1);
+    x->csq_supported.assign(csq_supported, csq_supported + n_csq);
+    x->csq_text_begin.assign(csq_text_begin, csq_text_begin + n_csq);
+    x->csq_text_len.assign(csq_text_len, csq_text_len + n_csq);
     return 0;
 }
 

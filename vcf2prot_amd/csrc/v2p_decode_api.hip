@@ -17,7 +17,9 @@
 #include "group_csr.h"
 #include "group_stats.h"
 #include "group_tasks.h"
+#include "host/frontend_common.hpp"
 #include "inflate_format.hpp"
+#include "record_index.h"
 #include "v2p_ctx_internal.h"
 
 using namespace v2p;
@@ -82,6 +84,15 @@ struct CsqTablesDev {
     uint64_t n = 0, n_extra = 0, n_aa = 0;
     bool ok = false;
     float ms[7] = {0, 0, 0, 0, 0, 0, 0};    // upload, parse, names, host sort + rank upload, ident, extras, download
+};
+
+// v2p_decode_index_build: the record index made on the device, until the next build
+struct IndexDev {
+    DevMem row_begin, row_end, csq_begin, csq_supported, csq_text_begin, csq_text_len;
+    std::vector<uint64_t> sample_begin, sample_len;                    // the host's header rule on the "#CHROM" line
+    uint64_t n_records = 0, n_csq = 0;
+    bool ok = false;
+    float ms[5] = {0, 0, 0, 0, 0};    // line pass, record count, scans, record emit, download
 };
 
 // a status word's reason (decode_kernels.h) as the ABI's error code and the reference's words
@@ -165,6 +176,7 @@ struct v2p_decode {
     TaskTables task_tables;
     Tasks tasks;
     CsqTablesDev csq_tables;          // (made of the text alone: they outlive the lists)
+    IndexDev index;                   // (likewise)
     void drop_lists() { lists = Lists{}; groups = Groups{}; tasks = Tasks{}; }     // (the tables and the text stay)
 };
 
@@ -1183,6 +1195,202 @@ int v2p_decode_tables_timing(const v2p_decode* d, float* ms_upload, float* ms_pa
                              float* ms_download)
 {
     return d ? give_ms(d->csq_tables.ms, {ms_upload, ms_parse, ms_names, ms_sort, ms_ident, ms_extras, ms_download}) : V2P_ERR_INVALID_ARG;
+}
+
+int v2p_decode_upload(v2p_ctx* ctx, const uint8_t* text, uint64_t n_text, v2p_decode** out)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    if (!out || (n_text && !text)) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_upload: null argument", -1);
+    *out = nullptr;
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    std::unique_ptr<v2p_decode> d(new (std::nothrow) v2p_decode());
+    if (!d) return ctx_fail(ctx, V2P_ERR_HIP, "out of host memory", -1);
+    d->ctx = ctx; d->n_text = n_text;
+    TRY(d->text.alloc(n_text + 512), "hipMalloc(text)");
+    if (n_text) TRY(hipMemcpyAsync(d->text.get<uint8_t>() + 256, text, n_text, hipMemcpyHostToDevice, st), "H2D(text)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    *out = d.release();
+    return V2P_OK;
+}
+
+int v2p_decode_index_build(v2p_ctx* ctx, v2p_decode* d, v2p_index_info* info)
+{
+    namespace F = v2p_frontend;
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f("v2p_decode_index_build");
+    if (!d || d->ctx != ctx || !d->text)
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": needs a decode that holds text (v2p_decode_upload / v2p_decode_inflate / v2p_decode_run)", -1);
+    if (!info) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    *info = v2p_index_info{};
+    info->tile_bytes = RIDX_TILE_BYTES; info->line_threads = RIDX_LINE_THREADS;
+    d->index = IndexDev{};
+    const uint64_t n_text = d->n_text;
+    if (!n_text) return ctx_fail(ctx, V2P_ERR_VCF_FORMAT, F::MSG_EMPTY_FILE, -1);
+    const uint64_t n_tiles = (n_text + RIDX_TILE_BYTES - 1) / RIDX_TILE_BYTES;
+    if (n_tiles >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": more than 2^32 tiles of text", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    IndexDev X;                                         // moved onto d when everything succeeded
+    Events<10> ev;
+    TRY(ev.create(), "hipEventCreate");
+    const uint8_t* d_text = d->text.get<uint8_t>() + 256;
+
+    // everything the kernels read is uploaded, zeroed or fully written by an earlier launch
+    DevMem d_words, d_tile_count, d_tile_base, d_line_begin, d_is_record, d_csq_count, d_rank, d_base;
+    TRY(d_words.alloc(8 * sizeof(uint64_t)), "hipMalloc(index status)");       // status | header line | totals: line feeds, records, consequences
+    TRY(d_tile_count.alloc((n_tiles + 1) * sizeof(uint32_t)), "hipMalloc(tile_count)");
+    TRY(d_tile_base.alloc((n_tiles + 1) * sizeof(uint64_t)), "hipMalloc(tile_base)");
+    uint64_t* words = d_words.get<uint64_t>();
+    TRY(hipMemsetAsync(words, 0, 8 * sizeof(uint64_t), st), "hipMemset(index status)");
+    TRY(hipMemsetAsync(words, 0xFF, 2 * sizeof(uint64_t), st), "hipMemset(index status)");
+    unsigned long long* totals = reinterpret_cast<unsigned long long*>(words) + 2;
+    uint64_t host_words[8] = {~0ull, ~0ull, 0, 0, 0, 0, 0, 0};
+    auto read_words = [&]() -> hipError_t {
+        hipError_t e = hipMemcpyAsync(host_words, words, sizeof(host_words), hipMemcpyDeviceToHost, st);
+        return e == hipSuccess ? hipStreamSynchronize(st) : e;
+    };
+
+    // lines: count, scan, emit
+    LineArgs la{};
+    la.text = d_text; la.n_text = n_text; la.n_tiles = uint32_t(n_tiles);
+    la.tile_count = d_tile_count.get<uint32_t>(); la.tile_base = d_tile_base.get<unsigned long long>();
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    TRY(launch_index_lines(la, false, st), "index_lines_count_kernel");
+    TRY(launch_csq_scan(la.tile_count, la.n_tiles, d_tile_base.get<unsigned long long>(), nullptr, totals + 0, st), "csq_scan_kernel (tiles)");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    uint8_t last = 0;
+    TRY(hipMemcpyAsync(&last, d_text + n_text - 1, 1, hipMemcpyDeviceToHost, st), "D2H(last byte)");
+    TRY(read_words(), "D2H(index status)");
+    const uint64_t n_lf = host_words[2], n_lines = n_lf + (last != '\n');
+    if (n_lf > n_text || n_lines >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": more than 2^32 lines", -1);
+    TRY(d_line_begin.alloc((n_lines + 1) * sizeof(uint64_t)), "hipMalloc(line_begin)");
+    TRY(d_is_record.alloc((n_lines + 1) * sizeof(uint32_t)), "hipMalloc(is_record)");
+    TRY(d_csq_count.alloc((n_lines + 1) * sizeof(uint32_t)), "hipMalloc(csq_count)");
+    TRY(d_rank.alloc((n_lines + 1) * sizeof(uint64_t)), "hipMalloc(record_rank)");
+    TRY(d_base.alloc((n_lines + 1) * sizeof(uint64_t)), "hipMalloc(csq_base)");
+    la.line_begin = d_line_begin.get<unsigned long long>(); la.n_lines = n_lines;
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(launch_index_lines(la, true, st), "index_lines_emit_kernel");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+
+    // records: count, two scans
+    RecordArgs ra{};
+    ra.text = d_text; ra.n_text = n_text; ra.line_begin = la.line_begin; ra.n_lines = uint32_t(n_lines); ra.ends_with_lf = last == '\n';
+    ra.status = reinterpret_cast<unsigned long long*>(words); ra.header_line = ra.status + 1;
+    ra.is_record = d_is_record.get<uint32_t>(); ra.csq_count = d_csq_count.get<uint32_t>();
+    ra.record_rank = d_rank.get<unsigned long long>(); ra.csq_base = d_base.get<unsigned long long>();
+    TRY(launch_index_records(ra, false, st), "index_records_kernel (count)");
+    TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+    TRY(launch_csq_scan(ra.is_record, ra.n_lines, d_rank.get<unsigned long long>(), nullptr, totals + 1, st), "csq_scan_kernel (records)");
+    TRY(launch_csq_scan(ra.csq_count, ra.n_lines, d_base.get<unsigned long long>(), nullptr, totals + 2, st), "csq_scan_kernel (consequences)");
+    TRY(hipEventRecord(ev[5], st), "hipEventRecord");
+    TRY(read_words(), "D2H(index status)");
+    const uint64_t status = host_words[0], header_line = host_words[1], n_records = host_words[3], n_csq = host_words[4];
+    if (n_records > n_lines || (header_line != ~0ull && header_line >= n_lines) || (status != ~0ull && (status >> 8) >= n_lines))
+        return ctx_fail(ctx, V2P_ERR_HIP, f + ": the record pass left counts outside the lines", -1);
+
+    // the verdict: the failure on the smallest line, where the host's loop would have stopped
+    uint64_t fail_line = ~0ull;
+    const char* fail_msg = nullptr;
+    auto candidate = [&](uint64_t line, const char* msg) { if (line < fail_line) { fail_line = line; fail_msg = msg; } };
+    if (status != ~0ull) candidate(status >> 8, (status & 0xFF) == RIDX_ERR_COLUMNS ? F::MSG_FEW_COLUMNS : F::MSG_NO_SAMPLE_COLUMNS);
+    auto fetch = [&](void* dst, const void* src, size_t n) { return hipMemcpy(dst, src, n, hipMemcpyDeviceToHost); };
+    if (header_line != ~0ull) {
+        uint64_t lb[2] = {0, 0};
+        const bool is_last = header_line + 1 == n_lines;
+        TRY(fetch(lb, la.line_begin + header_line, (is_last ? 1 : 2) * sizeof(uint64_t)), "D2H(header line)");
+        const uint64_t b = lb[0];
+        uint64_t e = is_last ? n_text - (last == '\n') : lb[1] - 1;
+        if (b > e || e > n_text) return ctx_fail(ctx, V2P_ERR_HIP, f + ": the header line lies outside the text", -1);
+        std::string line(e - b, '\0');
+        if (e > b) TRY(fetch(&line[0], d_text + b, e - b), "D2H(header line)");
+        if (!line.empty() && line.back() == '\r') line.pop_back();    // str::lines
+        if (const char* why = F::header_samples(line, b, X.sample_begin, X.sample_len)) candidate(header_line, why);
+        info->header_begin = b; info->header_len = line.size();
+    }
+    if (n_csq >= RIDX_MAX_CSQ) {
+        // the host stops at the record that brings the count there: the smallest line i with csq_base[i + 1] >= the limit
+        uint64_t lo = 0, hi = n_lines - 1;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            uint64_t v = 0;
+            TRY(fetch(&v, ra.csq_base + mid + 1, sizeof(uint64_t)), "D2H(csq_base)");
+            if (v >= RIDX_MAX_CSQ) hi = mid; else lo = mid + 1;
+        }
+        candidate(lo, F::MSG_TOO_MANY_CSQ);
+    }
+    if (fail_msg) return ctx_fail(ctx, V2P_ERR_VCF_FORMAT, fail_msg, int64_t(fail_line));
+    if (header_line == ~0ull) return ctx_fail(ctx, V2P_ERR_VCF_FORMAT, F::MSG_NO_HEADER, -1);
+    if (!n_records) return ctx_fail(ctx, V2P_ERR_VCF_FORMAT, F::MSG_NO_RECORDS, -1);
+
+    // records: emit
+    X.n_records = n_records; X.n_csq = n_csq;
+    TRY(X.row_begin.alloc(n_records * sizeof(uint64_t)), "hipMalloc(row_begin)");
+    TRY(X.row_end.alloc(n_records * sizeof(uint64_t)), "hipMalloc(row_end)");
+    TRY(X.csq_begin.alloc((n_records + 1) * sizeof(uint32_t)), "hipMalloc(csq_begin)");
+    TRY(X.csq_supported.alloc(n_csq + 1), "hipMalloc(csq_supported)");
+    TRY(X.csq_text_begin.alloc((n_csq + 1) * sizeof(uint64_t)), "hipMalloc(csq_text_begin)");
+    TRY(X.csq_text_len.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(csq_text_len)");
+    ra.n_records = n_records; ra.n_csq = n_csq;
+    ra.row_begin = X.row_begin.get<unsigned long long>(); ra.row_end = X.row_end.get<unsigned long long>(); ra.csq_begin = X.csq_begin.get<uint32_t>();
+    ra.csq_text_begin = X.csq_text_begin.get<unsigned long long>(); ra.csq_text_len = X.csq_text_len.get<uint32_t>();
+    ra.csq_supported = X.csq_supported.get<uint8_t>();
+    TRY(hipEventRecord(ev[6], st), "hipEventRecord");
+    TRY(launch_index_records(ra, true, st), "index_records_kernel (emit)");
+    TRY(hipEventRecord(ev[7], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    float ms_a = 0, ms_b = 0;
+    (void)hipEventElapsedTime(&ms_a, ev[0], ev[1]); (void)hipEventElapsedTime(&ms_b, ev[2], ev[3]);
+    X.ms[0] = ms_a + ms_b;
+    (void)hipEventElapsedTime(&X.ms[1], ev[3], ev[4]);
+    (void)hipEventElapsedTime(&X.ms[2], ev[4], ev[5]);
+    (void)hipEventElapsedTime(&X.ms[3], ev[6], ev[7]);
+    info->n_lines = n_lines; info->n_records = n_records; info->n_consequences = n_csq; info->n_samples = X.sample_begin.size();
+    X.ok = true;
+    d->index = std::move(X);
+    return V2P_OK;
+}
+
+int v2p_decode_index_download(v2p_decode* d, uint64_t* sample_begin, uint64_t* sample_len, uint64_t* row_begin, uint64_t* row_end,
+                              uint32_t* csq_begin, uint8_t* csq_supported, uint64_t* csq_text_begin, uint32_t* csq_text_len)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* ctx = d->ctx;
+    Guard g(ctx);
+    IndexDev& X = d->index;
+    if (!X.ok) return ctx_fail(ctx, V2P_ERR_STATE, "v2p_decode_index_download: no successful v2p_decode_index_build on this decode", -1);
+    if (!sample_begin || !sample_len || !row_begin || !row_end || !csq_begin || (X.n_csq && (!csq_supported || !csq_text_begin || !csq_text_len)))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, "v2p_decode_index_download: null argument", -1);
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    Events<2> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    auto get = [&](void* dst, const DevMem& src, uint64_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(dst, src.get<void>(), bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    TRY(get(row_begin, X.row_begin, X.n_records * sizeof(uint64_t)), "D2H(row_begin)");
+    TRY(get(row_end, X.row_end, X.n_records * sizeof(uint64_t)), "D2H(row_end)");
+    TRY(get(csq_begin, X.csq_begin, (X.n_records + 1) * sizeof(uint32_t)), "D2H(csq_begin)");
+    TRY(get(csq_supported, X.csq_supported, X.n_csq), "D2H(csq_supported)");
+    TRY(get(csq_text_begin, X.csq_text_begin, X.n_csq * sizeof(uint64_t)), "D2H(csq_text_begin)");
+    TRY(get(csq_text_len, X.csq_text_len, X.n_csq * sizeof(uint32_t)), "D2H(csq_text_len)");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&X.ms[4], ev[0], ev[1]);
+    memcpy(sample_begin, X.sample_begin.data(), X.sample_begin.size() * sizeof(uint64_t));
+    memcpy(sample_len, X.sample_len.data(), X.sample_len.size() * sizeof(uint64_t));
+    return V2P_OK;
+}
+
+int v2p_decode_index_timing(const v2p_decode* d, float* ms_lines, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download)
+{
+    if (!d) return V2P_ERR_INVALID_ARG;
+    if (!d->index.ok) return V2P_ERR_STATE;
+    return give_ms(d->index.ms, {ms_lines, ms_count, ms_scan, ms_emit, ms_download});
 }
 
 void v2p_decode_destroy(v2p_decode* d)

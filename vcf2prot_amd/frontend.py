@@ -10,6 +10,11 @@ A .vcf.gz as bgzip writes it (BGZF) is inflated on the GPU first, and its text s
     idx    = VcfIndex(text)
     lists  = decode_bitmasks(ctx, idx, resident)     # v2p_decode_run_inflated: no second upload
 
+The index can be made on the GPU too, from the resident text (opt-in; same columns, same verdicts):
+
+    resident = upload_text(ctx, vcf_bytes)           # or the InflatedText of inflate_bgzf
+    idx    = VcfIndex.from_device(ctx, vcf_bytes, resident)
+
 The decode has no CPU path: without the HIP library / a GPU it raises.
 """
 from __future__ import annotations
@@ -64,6 +69,10 @@ DECODE_API = {
     "v2p_decode_tables_build": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
     "v2p_decode_tables_download": (c_int, [c_void_p] + [c_void_p] * 12),
     "v2p_decode_tables_timing": (c_int, [c_void_p] + [POINTER(c_float)] * 7),
+    "v2p_decode_upload": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "v2p_decode_index_build": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "v2p_decode_index_download": (c_int, [c_void_p] + [c_void_p] * 8),
+    "v2p_decode_index_timing": (c_int, [c_void_p] + [POINTER(c_float)] * 5),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -112,6 +121,8 @@ HOST_API = {
     "v2p_csq_tables_aa_begin": (POINTER(c_uint64), [c_void_p]),
     "v2p_csq_tables_aa_ref_len": (POINTER(c_uint32), [c_void_p]),
     "v2p_csq_tables_from_arrays": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64] + [c_void_p] * 12 + [POINTER(c_void_p)]),
+    "v2p_vcf_index_from_arrays": (c_int, [c_uint64, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
+                                          c_void_p, POINTER(c_void_p)]),
 }
 
 
@@ -141,6 +152,11 @@ class v2p_tables_caps(ctypes.Structure):
 class v2p_tables_info(ctypes.Structure):
     _fields_ = [("n_transcripts", c_uint64), ("n_extra", c_uint64), ("n_aa", c_uint64), ("n_lengths", c_uint32), ("name_slots", c_uint32),
                 ("ident_slots", c_uint32)]
+
+
+class v2p_index_info(ctypes.Structure):
+    _fields_ = [("n_lines", c_uint64), ("n_records", c_uint64), ("n_consequences", c_uint64), ("n_samples", c_uint64), ("header_begin", c_uint64),
+                ("header_len", c_uint64), ("tile_bytes", c_uint32), ("line_threads", c_uint32)]
 
 
 class v2p_tasks_info(ctypes.Structure):
@@ -223,7 +239,10 @@ class VcfIndex:
             msg = self._lib.v2p_vcf_index_error(h).decode() if h else "index build failed"
             self.close()
             raise N.V2PError(rc, msg)
-        L = self._lib
+        self._read()
+
+    def _read(self):
+        L, h = self._lib, self._h
         self.n_samples = int(L.v2p_vcf_index_n_samples(h))
         self.n_records = int(L.v2p_vcf_index_n_records(h))
         self.n_consequences = int(L.v2p_vcf_index_n_consequences(h))
@@ -233,6 +252,42 @@ class VcfIndex:
         self.csq_supported = _arr(L.v2p_vcf_index_csq_supported(h), self.n_consequences, np.uint8)
         self.csq_text_begin = _arr(L.v2p_vcf_index_csq_text_begin(h), self.n_consequences, np.uint64)
         self.csq_text_len = _arr(L.v2p_vcf_index_csq_text_len(h), self.n_consequences, np.uint32)
+
+    COLUMNS = ("sample_begin", "sample_len", "row_begin", "row_end", "csq_begin", "csq_supported", "csq_text_begin", "csq_text_len")
+    COLUMN_DTYPES = (np.uint64, np.uint64, np.uint64, np.uint64, np.uint32, np.uint8, np.uint64, np.uint32)      # the order of v2p_decode_index_download
+
+    path, info = "host", None                                           # from_device sets them: where the index was made, what was launched
+
+    @classmethod
+    def from_arrays(cls, text: bytes, **columns) -> "VcfIndex":
+        """v2p_vcf_index_from_arrays: an index of `text` from its COLUMNS (copied); malformed columns raise V2PError."""
+        x = cls.__new__(cls)
+        x.text = np.frombuffer(text, dtype=np.uint8)
+        x._bytes = text
+        L = x._lib = _host()
+        c = {k: np.ascontiguousarray(columns[k], dt) for k, dt in zip(cls.COLUMNS, cls.COLUMN_DTYPES)}
+        h = c_void_p()
+        rc = L.v2p_vcf_index_from_arrays(x.text.size, c["sample_begin"].size, _ptr(c["sample_begin"]), _ptr(c["sample_len"]), c["row_begin"].size,
+                                         _ptr(c["row_begin"]), _ptr(c["row_end"]), _ptr(c["csq_begin"]), c["csq_supported"].size,
+                                         _ptr(c["csq_supported"]), _ptr(c["csq_text_begin"]), _ptr(c["csq_text_len"]), ctypes.byref(h))
+        x._h = h
+        if rc != 0:
+            msg = L.v2p_vcf_index_error(h).decode() if h else "v2p_vcf_index_from_arrays failed"
+            x.close()
+            raise N.V2PError(rc, msg)
+        x._read()
+        return x
+
+    @classmethod
+    def from_device(cls, ctx, text: bytes, resident_text) -> "VcfIndex":
+        """The index built on the GPU from the text `resident_text` (upload_text or inflate_bgzf of `text`) keeps there:
+        v2p_decode_index_build, v2p_decode_index_download, v2p_vcf_index_from_arrays.  A file the host index refuses raises the same
+        V2PError(V2P_ERR_VCF_FORMAT) with the same message and, as .index, the failing line.  .path is "device", .info the sizes and
+        timing_ms."""
+        columns, info = device_index_columns(ctx, resident_text)
+        x = cls.from_arrays(text, **columns)
+        x.path, x.info = "device", info
+        return x
 
     def sample_names(self):
         out, b, n = [], c_uint64(), c_uint64()
@@ -304,6 +359,38 @@ def inflate_bgzf(ctx, gz):
                                 text.ctypes.data, ctypes.byref(h))
     _check(ctx, rc)
     return text[:int(ob[-1] - ob[0])].tobytes(), InflatedText(ctx, h, int(ob[-1] - ob[0]))
+
+
+def upload_text(ctx, text) -> InflatedText:
+    """v2p_decode_upload: flat VCF text made resident on the GPU of `ctx` without lists -- the state inflate_bgzf leaves, for
+    VcfIndex.from_device, decode_resident and CsqTables.from_device."""
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    h = c_void_p()
+    _check(ctx, _hip().v2p_decode_upload(ctx._h, _ptr(buf), buf.size, ctypes.byref(h)))
+    return InflatedText(ctx, h, buf.size)
+
+
+def device_index_build(ctx, resident) -> dict:
+    """v2p_decode_index_build alone: the info dict; the columns stay on the decode.  Raises the file's verdict as V2PError."""
+    info = v2p_index_info()
+    _check(ctx, _hip().v2p_decode_index_build(ctx._h, resident._h, ctypes.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in v2p_index_info._fields_}
+
+
+def device_index_timing(resident) -> dict:
+    t = [c_float() for _ in range(5)]
+    _hip().v2p_decode_index_timing(resident._h, *[ctypes.byref(x) for x in t])
+    return dict(zip(("lines", "count", "scan", "emit", "download"), (x.value for x in t)))
+
+
+def device_index_columns(ctx, resident):
+    """v2p_decode_index_build + v2p_decode_index_download: ({column: array} in VcfIndex.COLUMNS order, info dict with timing_ms)."""
+    info = device_index_build(ctx, resident)
+    s, r, n = info["n_samples"], info["n_records"], info["n_consequences"]
+    cols = [np.zeros(k, dt) for k, dt in zip((s, s, r, r, r + 1, n, n, n), VcfIndex.COLUMN_DTYPES)]
+    _check(ctx, _hip().v2p_decode_index_download(resident._h, *[_ptr(c) for c in cols]))
+    info["timing_ms"] = device_index_timing(resident)
+    return dict(zip(VcfIndex.COLUMNS, cols)), info
 
 
 class ResidentLists(_DecodeHandle):

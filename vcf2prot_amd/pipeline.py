@@ -14,7 +14,7 @@ import numpy as np
 from . import _native as N
 from . import step4a
 from .frontend import (CsqTables, Groups, TranscriptInputs, VcfIndex, decode_resident, device_groups, device_groups_resident, device_tasks_count,
-                       device_tasks_emit, device_tasks_timing, inflate_bgzf, input_format)
+                       device_tasks_emit, device_tasks_timing, inflate_bgzf, input_format, upload_text)
 from .step4b import inspect_transcript_tasks, transcript_g_rep
 
 
@@ -186,7 +186,8 @@ def _csq_tables(ctx, idx, resident, on_device, report):
 
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
                  device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False, host_groups: bool = False,
-                 groups_caps=None, report: dict = None, device_tasks: bool = False, device_tables: bool = False) -> Dict[str, bytes]:
+                 groups_caps=None, report: dict = None, device_tasks: bool = False, device_tables: bool = False,
+                 device_index: bool = False) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
@@ -207,7 +208,12 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     loop below runs the whole file.
     device_tables (opt-in): the file-wide consequence tables are built on the GPU from the text the decode keeps there
     (CsqTables.from_device, include/v2p_frontend.h part 7) -- same tables, same bytes.  Any failure of the device build falls back to the
-    host build for the whole file; report receives {"tables": {"path": "device" | "host", "ms": ..., ...}}."""
+    host build for the whole file; report receives {"tables": {"path": "device" | "host", "ms": ..., ...}}.
+    device_index (opt-in): the record index is built on the GPU from the resident text (VcfIndex.from_device, include/v2p_frontend.h part 8):
+    flat or host-inflated text is uploaded first and the decode runs on that same handle -- same columns, same bytes.  A file the index
+    refuses raises the V2PError the host index raises; there is no fallback.  report receives {"index": {"path": "device" | "host",
+    "ms": ..., ...}}."""
+    import time
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
     fmt, inflated = input_format(vcf), None
@@ -216,12 +222,17 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     elif fmt == "gzip":
         import gzip
         vcf = gzip.decompress(bytes(vcf))
+    t_index = time.perf_counter()
+    if device_index and inflated is None:
+        inflated = upload_text(ctx, vcf)
     try:
-        idx = VcfIndex(vcf)
+        idx = VcfIndex.from_device(ctx, vcf, inflated) if device_index else VcfIndex(vcf)
     except N.V2PError:
         if inflated is not None:
             inflated.close()
         raise
+    if report is not None:
+        report["index"] = dict(idx.info or {}, path=idx.path, ms=(time.perf_counter() - t_index) * 1e3)
     resident = decode_resident(ctx, idx, inflated)
     try:
         n_haplotypes = resident.n_haplotypes
