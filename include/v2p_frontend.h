@@ -30,9 +30,13 @@
  *                         (v2p_decode_upload puts a flat text there); v2p_vcf_index_from_arrays (host) wraps the downloaded columns into the
  *                         v2p_vcf_index of (1).
  *
+ *   (9) -i / --write_int_map   v2p_decode_intmap_count / _emit serialise every proband's IntMap as JSON on the device from the CSR of (5);
+ *                         v2p_groups_intmap_json (host) reads the same bytes off a v2p_groups.
+ *
  * Where the reference aborts (panic!) these calls return a negative status; the binding maps it back to panic!.
  * libvcf2prot_hip.so exports (2), the v2p_decode_stats* calls of (4), the v2p_decode_groups* calls of (5), the v2p_decode_tasks* calls of
- * (6), the v2p_decode_tables* calls of (7) and the v2p_decode_upload / v2p_decode_index* calls of (8); libv2p_cohort.so (plain C++) exports the rest.
+ * (6), the v2p_decode_tables* calls of (7), the v2p_decode_upload / v2p_decode_index* calls of (8) and the v2p_decode_intmap* calls of (9);
+ * libv2p_cohort.so (plain C++) exports the rest.
  */
 #ifndef V2P_FRONTEND_H
 #define V2P_FRONTEND_H
@@ -444,6 +448,56 @@ int  v2p_vcf_index_from_arrays(uint64_t n_text, uint64_t n_samples, const uint64
                                uint64_t n_records, const uint64_t* row_begin, const uint64_t* row_end, const uint32_t* csq_begin,
                                uint64_t n_consequences, const uint8_t* csq_supported, const uint64_t* csq_text_begin,
                                const uint32_t* csq_text_len, v2p_vcf_index** out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (9) -i / --write_int_map: every proband's IntMap (Map.rs:9-15) as serde_json::to_writer writes it -- compact, no trailing newline --
+ * serialised on the device from the grouped CSR of (5), the rows of (4) and the amino-acid columns.  With h1 = 2s, h2 = 2s + 1:
+ *
+ *   P(s)  = {"proband_name":"E(sample_s)","mutations1":[L(h1)],"mutations2":[L(h2)]}
+ *   L(h)  = G(k) for the groups k of list h in CSR order, joined by ","
+ *   G(k)  = {"name":"E(tx[group_transcript[k]])","alts":[M(id) for the members of k in CSR order, joined by ","]}
+ *   M(id) = {"transcript_name":"E(tx[rank[id]])","mut_type":"V(type[id])","mut_info":{"ref_aa_position":D(ref_pos[id]),
+ *           "mut_aa_position":D(mut_pos[id]),"ref_aa":S(ref_aa[id]),"mut_aa":S(mut_aa[id])}}
+ *   S(a)  = "NotSeq" if a == "*"; {"EndSequence":"E(a)"} else if a contains '*'; {"Sequence":"E(a)"} otherwise
+ *   D(n)  = decimal; V(t) = the MutationType variant of SUP_TYPE[t] (mutation_ds.rs:32-53)
+ *   E(x)  = serde_json's escaping: \" \\ \b \f \n \r \t, every other byte below 0x20 as \u00xx (lowercase hex), the rest unchanged
+ *
+ * The reference's own -i cannot complete (writers.rs:43 create_dir's a directory main.rs:29-37 has made); the format is that of its
+ * #[derive(Serialize)] types.  The callers of this repository create <outdir>/int_maps if it is absent, write <stem>.json per proband
+ * after the grouping has succeeded and before the -s tables.  Their default is the host restatement below (on the probe's cohort it is the
+ * faster end to end); the device path is opt-in (--device-int-map, pipeline.vcf_to_fasta(device_int_map=True)) and is
+ * also what -i takes beside --device-tasks, where the CSR exists on the device only.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct v2p_intmap_info {
+    uint64_t n_fragments;       /* mut_ok consequences: each one's M(id) is built once per count */
+    uint64_t fragment_bytes;    /* ... and their bytes */
+    uint64_t out_bytes;         /* bytes of all probands' files */
+} v2p_intmap_info;
+
+/* The count launches and their scans on the CSR of the last successful v2p_decode_groups on d.  Host pointers.  aa / aa_begin /
+ * aa_ref_len as for v2p_decode_tasks_count: they share its residency on d and are uploaded by whichever of the two calls comes first.
+ * tx_json[tx_json_begin[r], tx_json_begin[r + 1]): the name of transcript rank r ALREADY ESCAPED (E above); sample_json /
+ * sample_json_begin likewise by sample; both are uploaded per call, the kernels never escape a name.  They do escape the amino-acid
+ * bytes.  proband_bytes[n_samples]: the size of every proband's file -- a caller cuts its ranges from these before anything is emitted.
+ * V2P_ERR_STATE unless d holds the CSR of a successful v2p_decode_groups; V2P_ERR_UNSUPPORTED for a group or a proband of 4 GiB or more
+ * or 2^32 groups or more.  info may be null. */
+int  v2p_decode_intmap_count(struct v2p_ctx* ctx, v2p_decode* d,
+                             const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len, uint64_t n_consequences,
+                             const uint8_t* tx_json, const uint64_t* tx_json_begin, uint64_t n_transcripts,
+                             const uint8_t* sample_json, const uint64_t* sample_json_begin, uint64_t n_samples,
+                             uint64_t* proband_bytes, v2p_intmap_info* info);
+/* The emit launch: the files of samples [s0, s1) of the last successful v2p_decode_intmap_count on d, back to back, into host_out.
+ * n_out must be the sum of their proband_bytes (else V2P_ERR_INVALID_ARG, nothing is launched); s0 == s1 writes nothing. */
+int  v2p_decode_intmap_emit(struct v2p_ctx* ctx, v2p_decode* d, uint64_t s0, uint64_t s1, uint8_t* host_out, uint64_t n_out);
+/* milliseconds of the last v2p_decode_intmap_count / _emit on d (HIP events): the upload of the names (and of the amino-acid columns
+ * when the decode did not hold them), the count launches, the scans, the last emit launch, its download */
+int  v2p_decode_intmap_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download);
+
+/* The host restatement (libv2p_cohort.so): P(sample) off the CSR of a v2p_groups over 2 * n_samples lists.  name[0, name_len): the
+ * sample's name, NOT escaped.  *n = the bytes of the file; they are written to out when cap holds them, else V2P_ERR_CAPACITY and
+ * nothing is written (out may then be null).  Reads g only: a caller may run it on many samples at once. */
+int  v2p_groups_intmap_json(const v2p_groups* g, uint64_t sample, const uint8_t* name, uint64_t name_len, uint8_t* out, uint64_t cap,
+                            uint64_t* n);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

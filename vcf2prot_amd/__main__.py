@@ -1,5 +1,5 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--no-test]`: the reference's command line
-(parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats) on top of
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--no-test]`: the reference's command line
+(parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
 CPU code and is refused.
@@ -21,6 +21,9 @@ def main() -> int:
     ap.add_argument("-a", "--write_all_proteins", action="store_true")
     ap.add_argument("-c", "--write_compressed", action="store_true")
     ap.add_argument("-s", "--stats", action="store_true", help="write the three mutation statistics tables, counted on the GPU, before the FASTA files")
+    ap.add_argument("-i", "--write_int_map", action="store_true",
+                    help="write every proband's intermediate map as JSON under <outdir>/int_maps, before the FASTA files")
+    ap.add_argument("--device-int-map", action="store_true", help="with -i: serialise the JSON on the GPU from the grouped CSR there (same bytes; opt-in)")
     ap.add_argument("--write_bgzf", action="store_true", help="BGZF (bgzip's format) compressed on the GPU, plus .gzi; not with -c")
     ap.add_argument("--host-groups", action="store_true", help="group consequences per transcript on the host instead of on the GPU (same bytes; for A/B runs)")
     ap.add_argument("--device-tables", action="store_true", help="build the file-wide consequence tables on the GPU too, from the resident VCF text (same bytes; opt-in)")
@@ -45,6 +48,10 @@ def main() -> int:
         cmd.append("--bgzf")
     if a.stats:
         cmd.append("-s")
+    if a.write_int_map:
+        cmd.append("-i")
+    if a.device_int_map:
+        cmd.append("--device-int-map")
     if a.host_groups:
         cmd.append("--host-groups")
     if a.device_tasks:

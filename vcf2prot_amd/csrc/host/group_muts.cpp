@@ -20,6 +20,7 @@
 #include "../../../include/v2p_frontend.h"
 #include "../../../include/v2p_step4a.h"
 #include "frontend_common.hpp"
+#include "intmap_format.hpp"
 
 struct ParsedText { std::string ref_aa, mut_aa; };
 
@@ -28,6 +29,7 @@ struct v2p_groups {
     std::vector<ParsedText> aa;                                       // per consequence: the two amino-acid strings of a valid Mutation
     int64_t error_hap = -1;
     std::vector<uint64_t> tx_begin; std::vector<uint32_t> tx_len;      // unique transcript ids (text ranges), sorted
+    std::vector<std::string> tx_json;                                 // ... and their text, escaped for v2p_groups_intmap_json
     std::vector<v2p_mutation> muts;
     std::vector<uint64_t> hap_group_begin;
     std::vector<uint32_t> group_transcript;
@@ -254,6 +256,9 @@ void fill_from_tables(v2p_groups* g, const Table& T)
     const uint64_t n_csq = T.rank.size();
     g->tx_begin = T.tx_begin;
     g->tx_len = T.tx_len;
+    g->tx_json.resize(T.names.size());
+    for (size_t r = 0; r < T.names.size(); ++r)
+        v2p_intmap::escape_into(g->tx_json[r], reinterpret_cast<const uint8_t*>(T.names[r].data()), T.names[r].size());
     g->muts.resize(n_csq);
     g->aa.resize(n_csq);
     for (uint64_t i = 0; i < n_csq; ++i) {
@@ -577,6 +582,54 @@ int v2p_groups_stats(const v2p_groups* g, uint64_t n_samples, uint64_t* per_prob
                 ++per_type[22 * (h / 2) + g->muts[g->member_ids[m]].type];
         }
     }
+    return 0;
+}
+
+// -i / --write_int_map: serde_json::to_writer(&IntMap) of one proband off the CSR (Map.rs:9-15; the text is intmap_format.hpp's)
+int v2p_groups_intmap_json(const v2p_groups* g, uint64_t sample, const uint8_t* name, uint64_t name_len, uint8_t* out, uint64_t cap, uint64_t* n)
+{
+    namespace J = v2p_intmap;
+    if (!g || !n || (name_len && !name) || g->error_hap >= 0 || g->hap_group_begin.size() < 2 * sample + 3) return -1;
+    static const char* const TYPE[J::N_TYPES] = {
+#define X(s) s,
+        V2P_INTMAP_TYPES(X)
+#undef X
+    };
+    std::string o;
+    auto aa = [&](const std::string& s) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+        const uint32_t kind = J::aa_kind(p, s.size());
+        if (kind == 2) { o += V2P_IM_S_NOT; return; }
+        o += kind == 1 ? V2P_IM_S_END : V2P_IM_S_SEQ;
+        J::escape_into(o, p, s.size());
+        o += V2P_IM_S_TAIL;
+    };
+    o += V2P_IM_P_HEAD;
+    J::escape_into(o, name, name_len);
+    for (uint64_t h = 2 * sample; h < 2 * sample + 2; ++h) {
+        o += h & 1 ? V2P_IM_P_MID2 : V2P_IM_P_MID1;
+        for (uint64_t k = g->hap_group_begin[h]; k < g->hap_group_begin[h + 1]; ++k) {
+            if (k > g->hap_group_begin[h]) o += ',';
+            o += V2P_IM_G_HEAD; o += g->tx_json[g->group_transcript[k]]; o += V2P_IM_G_MID;
+            for (uint64_t m = g->group_member_begin[k]; m < g->group_member_begin[k + 1]; ++m) {
+                const uint32_t id = g->member_ids[m];
+                const v2p_mutation& mu = g->muts[id];
+                if (m > g->group_member_begin[k]) o += ',';
+                o += V2P_IM_M_HEAD; o += g->tx_json[mu.transcript];
+                o += V2P_IM_M_TYPE; o += TYPE[mu.type];
+                o += V2P_IM_M_REF_POS; o += std::to_string(mu.ref_aa_position);
+                o += V2P_IM_M_MUT_POS; o += std::to_string(mu.mut_aa_position);
+                o += V2P_IM_M_REF_AA; aa(g->aa[id].ref_aa);
+                o += V2P_IM_M_MUT_AA; aa(g->aa[id].mut_aa);
+                o += V2P_IM_M_TAIL;
+            }
+            o += V2P_IM_G_TAIL;
+        }
+    }
+    o += V2P_IM_P_TAIL;
+    *n = o.size();
+    if (o.size() > cap || (!out && !o.empty())) return V2P_ERR_CAPACITY;
+    memcpy(out, o.data(), o.size());
     return 0;
 }
 

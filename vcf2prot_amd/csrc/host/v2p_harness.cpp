@@ -6,7 +6,7 @@
 //
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
-//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
+//   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--slice-kb K]   VCF -> one FASTA(.gz) per proband, no Rust anywhere;
 //                                            the per-transcript grouping comes from the GPU (v2p_decode_groups); --host-groups, or a list the kernel
 //                                            refuses, sends the whole file through the host grouping on the same tables -- same bytes;
 //                                            in.vcf may be BGZF (.vcf.gz, inflated on the GPU) or any other gzip (inflated on the host);
@@ -18,8 +18,11 @@
 //                                            slices of M MiB of result through v2p_pipeline_submit_stream, the results IN HOST MEMORY --
 //                                            the digests printed are then digests of the host bytes
 //   v2p_harness shard <world> <bytes...>     the ranges ppgg::shard_by_bytes cuts (no GPU)
+#include <sys/stat.h>
+
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +42,7 @@
 #include "../../../include/v2p_cohort.h"
 #include "../../../include/v2p_step4a.h"
 #include "../inflate_format.hpp"
+#include "intmap_format.hpp"
 #include "ppgg_gpu.hpp"
 
 using namespace ppgg;
@@ -362,7 +366,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index, bool int_map, bool device_int_map)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -571,11 +575,107 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         }
     }
     v2p_decode_groups_timing(dec, &gms[0], &gms[1], &gms[2], &gms[3], &gms[4]);
+    t_group = t_tables + since(t0); t0 = clk::now();     // the file-wide tables and the per-haplotype phase, as v2p_groups_build had them
+    // -i / --write_int_map (main.rs:29-37): every proband's IntMap as JSON under <outdir>/int_maps, after the grouping has succeeded and
+    // before the -s tables and the FASTA files.  By default the host restatement reads it off the v2p_groups, on up to 16 threads.  With
+    // --device-int-map (opt-in: on the probe's cohort the link and the host's buffers cost more than the kernels save) and
+    // with --device-tasks (the CSR then exists on the device only) it is serialised on the device (include/v2p_frontend.h part 9): count,
+    // cut sample ranges of about slice_bytes from the per-proband sizes, then emit, download and write, range after range.
+    double t_int_map = 0;
+    const bool int_map_on_device = int_map && device_groups && (device_int_map || tasks_on_device);
+    float jms[5] = {0, 0, 0, 0, 0};
+    uint64_t int_map_bytes = 0, int_map_ranges = 0;
+    if (int_map) {
+        const auto ti = clk::now();
+        auto chk_early = [&](int rc) { if (rc != V2P_OK) { std::fprintf(stderr, "panicked: %s\n", v2p_last_error(ctx.raw())); std::exit(101); } };
+        std::vector<std::string> samples(S);
+        for (uint64_t s = 0; s < S; ++s) {
+            uint64_t b = 0, n = 0;
+            v2p_vcf_index_sample(idx, s, &b, &n);
+            samples[s] = vcf.substr(b, n);
+            if (v2p_intmap::name_refused(samples[s])) {
+                std::fprintf(stderr, "panicked: sample name '%s' cannot name a file under int_maps (empty, '.', '..' or with a '/')\n", samples[s].c_str());
+                return 101;
+            }
+        }
+        const std::string dir = std::string(outdir) + "/int_maps";
+        if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) { std::fprintf(stderr, "panicked: Creating the output directory failed because of: %s\n", std::strerror(errno)); return 101; }
+        auto write_file = [&](uint64_t s, const uint8_t* p, uint64_t n) {
+            const std::string path = dir + "/" + v2p_intmap::file_name(samples[s]);
+            FILE* f = std::fopen(path.c_str(), "wb");
+            const bool ok = f && std::fwrite(p, 1, n, f) == n;
+            if (f && std::fclose(f) != 0) return false;
+            return ok;
+        };
+        if (int_map_on_device) {
+            std::string tx_json, sample_json;
+            std::vector<uint64_t> tx_json_begin(T + 1, 0), sample_json_begin(S + 1, 0), proband_bytes(S + 1, 0);
+            for (uint64_t r = 0; r < T; ++r) {
+                uint64_t b = 0, n = 0;
+                v2p_csq_tables_transcript(tb, r, &b, &n);
+                v2p_intmap::escape_into(tx_json, text + b, n);
+                tx_json_begin[r + 1] = tx_json.size();
+            }
+            for (uint64_t s = 0; s < S; ++s) {
+                v2p_intmap::escape_into(sample_json, reinterpret_cast<const uint8_t*>(samples[s].data()), samples[s].size());
+                sample_json_begin[s + 1] = sample_json.size();
+            }
+            v2p_intmap_info jinfo{};
+            chk_early(v2p_decode_intmap_count(ctx.raw(), dec, v2p_csq_tables_aa(tb), v2p_csq_tables_aa_begin(tb), v2p_csq_tables_aa_ref_len(tb),
+                                              v2p_csq_tables_n_consequences(tb), reinterpret_cast<const uint8_t*>(tx_json.data()), tx_json_begin.data(), T,
+                                              reinterpret_cast<const uint8_t*>(sample_json.data()), sample_json_begin.data(), S, proband_bytes.data(), &jinfo));
+            v2p_decode_intmap_timing(dec, &jms[0], &jms[1], &jms[2], nullptr, nullptr);
+            std::vector<uint8_t> buf;
+            uint64_t s0 = 0, acc = 0;
+            for (uint64_t s = 0; s < S; ++s) {
+                acc += proband_bytes[s];
+                if (acc < slice_bytes && s + 1 != S) continue;
+                buf.resize(acc + 1);
+                chk_early(v2p_decode_intmap_emit(ctx.raw(), dec, s0, s + 1, buf.data(), acc));
+                float ems[2] = {0, 0};
+                v2p_decode_intmap_timing(dec, nullptr, nullptr, nullptr, &ems[0], &ems[1]);
+                jms[3] += ems[0]; jms[4] += ems[1];
+                uint64_t at = 0;
+                for (uint64_t p = s0; p <= s; ++p) {
+                    if (!write_file(p, buf.data() + at, proband_bytes[p])) { std::fprintf(stderr, "panicked: could not write the int map of %s\n", samples[p].c_str()); return 101; }
+                    at += proband_bytes[p];
+                }
+                int_map_bytes += acc; ++int_map_ranges;
+                s0 = s + 1; acc = 0;
+            }
+        } else {
+            const unsigned nt = unsigned(std::min<uint64_t>(std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency())), std::max<uint64_t>(1, S)));
+            std::vector<std::vector<uint8_t>> files(S);
+            std::atomic<uint64_t> next{0};
+            std::atomic<bool> failed{false};
+            auto work = [&] {
+                for (uint64_t s = next++; s < S; s = next++) {
+                    uint64_t n = 0;
+                    const uint8_t* nm = reinterpret_cast<const uint8_t*>(samples[s].data());
+                    v2p_groups_intmap_json(g, s, nm, samples[s].size(), nullptr, 0, &n);
+                    files[s].resize(n + 1);
+                    if (v2p_groups_intmap_json(g, s, nm, samples[s].size(), files[s].data(), n, &n) != 0) failed = true;
+                    files[s].resize(n);
+                }
+            };
+            std::vector<std::thread> pool;
+            for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
+            work();
+            for (auto& t : pool) t.join();
+            if (failed) { std::fprintf(stderr, "panicked: the int maps could not be serialised\n"); return 101; }
+            for (uint64_t s = 0; s < S; ++s) {                         // in sample order: of two samples with one stem the later wins
+                if (!write_file(s, files[s].data(), files[s].size())) { std::fprintf(stderr, "panicked: could not write the int map of %s\n", samples[s].c_str()); return 101; }
+                int_map_bytes += files[s].size();
+            }
+            int_map_ranges = 1;
+        }
+        t_int_map = since(ti);
+        t0 = clk::now();
+    }
     if (!tasks_on_device) {
         v2p_decode_destroy(dec);
         v2p_csq_tables_destroy(tb);
     }
-    t_group = t_tables + since(t0); t0 = clk::now();     // the file-wide tables and the per-haplotype phase, as v2p_groups_build had them
     if (stats) {
         const auto ts = clk::now();
         // lists the kernel refused: the grouping above holds every list, so the tables are read off it
@@ -736,8 +836,9 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     auto report = [&](const std::string& tasks_json) {
         char stats_seconds[48] = "";
         if (stats) std::snprintf(stats_seconds, sizeof(stats_seconds), ", \"stats\": %.4f", t_stats);
-        char tables_seconds[48];
-        std::snprintf(tables_seconds, sizeof(tables_seconds), ", \"tables\": %.4f", t_tables);
+        char tables_seconds[96];
+        const int tn = std::snprintf(tables_seconds, sizeof(tables_seconds), ", \"tables\": %.4f", t_tables);
+        if (int_map) std::snprintf(tables_seconds + tn, sizeof(tables_seconds) - size_t(tn), ", \"int_map\": %.4f", t_int_map);
         std::printf("vcf: %llu records, %llu probands, %llu bytes of FASTA written to %s\n", (unsigned long long)R, (unsigned long long)S,
                     (unsigned long long)written, outdir);
         std::printf("{\"records\": %llu, \"probands\": %llu, \"fasta_bytes\": %llu, \"slices\": %llu, \"slices_through_the_host_builder\": %llu, \"seconds\": {\"read_files\": %.4f, \"index\": %.4f, "
@@ -750,6 +851,9 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         if (stats)
             std::printf(", \"stats_ms\": {\"upload\": %.3f, \"kernel\": %.3f, \"refused_lists\": %llu, \"sorted_members\": %llu, \"lds_bytes\": %u}",
                         sms[0], sms[1], (unsigned long long)sinfo.n_refused, (unsigned long long)sinfo.n_sorted_members, sinfo.lds_bytes);
+        if (int_map)
+            std::printf(", \"int_map_ms\": {\"path\": \"%s\", \"upload\": %.3f, \"count\": %.3f, \"scan\": %.3f, \"emit\": %.3f, \"download\": %.3f, \"bytes\": %llu, \"ranges\": %llu}",
+                        int_map_on_device ? "device" : "host", jms[0], jms[1], jms[2], jms[3], jms[4], (unsigned long long)int_map_bytes, (unsigned long long)int_map_ranges);
         std::printf(", \"groups\": {\"path\": \"%s\", \"n_refused\": %llu, \"key_capacity\": %u, \"lds_bytes\": %u, \"ms_upload\": %.3f, \"ms_count\": %.3f, "
                     "\"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f}", device_groups ? "device" : "host", (unsigned long long)ginfo.n_refused,
                     ginfo.key_capacity, ginfo.lds_bytes, gms[0], gms[1], gms[2], gms[3], gms[4]);
@@ -1061,7 +1165,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, int_map = false, device_int_map = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -1075,9 +1179,11 @@ int main(int argc, char** argv)
             compressed |= !std::strcmp(argv[i], "--write-compressed") || !std::strcmp(argv[i], "-c");
             bgzf |= !std::strcmp(argv[i], "--bgzf");
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
+            int_map |= !std::strcmp(argv[i], "-i") || !std::strcmp(argv[i], "--write_int_map");
+            device_int_map |= !std::strcmp(argv[i], "--device-int-map");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index); }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index, int_map, device_int_map); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

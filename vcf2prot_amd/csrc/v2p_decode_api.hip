@@ -18,7 +18,9 @@
 #include "group_stats.h"
 #include "group_tasks.h"
 #include "host/frontend_common.hpp"
+#include "host/intmap_format.hpp"
 #include "inflate_format.hpp"
+#include "intmap_json.h"
 #include "record_index.h"
 #include "v2p_ctx_internal.h"
 
@@ -58,11 +60,17 @@ struct Groups {
     std::vector<uint64_t> refused;
 };
 
-// the amino-acid and per-transcript tables of v2p_decode_tasks_count on the device, kept while the next call brings the same ones
-struct TaskTables {
-    DevMem aa, aa_bytes, tx, slot_rank;
+// the amino-acid columns on the device, for v2p_decode_tasks_count and v2p_decode_intmap_count alike: uploaded by whichever comes first,
+// kept while the next call brings the same ones
+struct AaTables {
+    DevMem aa, aa_bytes;
     std::vector<TaskAa> host_aa;
     std::vector<uint8_t> host_aa_bytes;
+};
+
+// the per-transcript tables of v2p_decode_tasks_count on the device, kept while the next call brings the same ones
+struct TaskTables {
+    DevMem tx, slot_rank;
     std::vector<TaskTx> host_tx;
     std::vector<uint32_t> host_slot_rank;
 };
@@ -75,6 +83,17 @@ struct Tasks {
     std::vector<uint64_t> host_first_item;     // [n_haps + 1] every list's first item
     bool ok = false;
     float ms[4] = {0, 0, 0, 0};       // upload of the tables, count, scans, the last emit
+};
+
+// v2p_decode_intmap_count: the fragments, the sizes and their prefix sums on the device until the next call or the end of their CSR
+struct Intmap {
+    DevMem tx_json, tx_json_begin, sample_json, sample_json_begin;
+    DevMem frag_len, frag_begin, frag, group_len, group_begin, proband_len, proband_begin, status;
+    IntmapArgs args{};                // what the count launched with: the emit launches with the same
+    std::vector<uint64_t> host_proband_begin;      // [n_samples + 1]
+    std::vector<uint64_t> host_hap_group_begin;    // [2 * n_samples + 1]
+    bool ok = false;
+    float ms[5] = {0, 0, 0, 0, 0};    // upload, count launches, scans, the last emit, its download
 };
 
 // v2p_decode_tables_build: the consequence tables made on the device, until the next build
@@ -173,11 +192,13 @@ struct v2p_decode {
     Tables tables;
     Stats stats;
     Groups groups;
+    AaTables aa_tables;
     TaskTables task_tables;
     Tasks tasks;
+    Intmap intmap;
     CsqTablesDev csq_tables;          // (made of the text alone: they outlive the lists)
     IndexDev index;                   // (likewise)
-    void drop_lists() { lists = Lists{}; groups = Groups{}; tasks = Tasks{}; }     // (the tables and the text stay)
+    void drop_lists() { lists = Lists{}; groups = Groups{}; tasks = Tasks{}; intmap = Intmap{}; }     // (the tables and the text stay)
 };
 
 #define TRY(expr, what) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
@@ -323,6 +344,7 @@ static int prepare_tables(v2p_ctx* ctx, v2p_decode* d, const std::string& f, con
         return V2P_OK;
     tb = Tables{};
     d->tasks = Tasks{};                                 // (its launches read the rows that go)
+    d->intmap = Intmap{};
     TRY(tb.rec.alloc(rec.size() * sizeof(StatsRec)), "hipMalloc(stats rows)");
     TRY(tb.extra_begin.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(extra_begin)");
     TRY(tb.extra.alloc((n_extra + 1) * sizeof(uint32_t)), "hipMalloc(extra)");
@@ -633,6 +655,7 @@ int v2p_decode_groups(v2p_ctx* ctx, v2p_decode* d, const uint32_t* rank, const u
     const uint64_t n_haps = c.n_haps, max_len = c.max_len;
     Groups& gr = d->groups;
     d->tasks = Tasks{};                                 // (counted on the CSR that goes)
+    d->intmap = Intmap{};
     // sizes: the bitmap covers every transcript; keys for the longest list and an eighth more (extras are rare), at least 2 048, a power of two; the
     // filter gets about 32 bits per id of the longest list.  Whatever does not fit 160 KiB of LDS shrinks, and lists over it are refused.
     const uint64_t lds_max = 160u * 1024u;
@@ -741,6 +764,47 @@ int v2p_decode_groups_timing(const v2p_decode* d, float* ms_upload, float* ms_co
 }
 
 // ---- (6) steps 4a / 4b on the device ----------------------------------------------------------------------------------------
+// the amino-acid strings, one row per consequence: inside the bytes, below 2^30 each, their MutatedString kind in the two top bits
+// (mutation_ds.rs:50-76); rows[n_csq] closes them
+static int aa_rows(v2p_ctx* ctx, const std::string& f, const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len, uint64_t n_csq,
+                   std::vector<TaskAa>& rows)
+{
+    rows.assign(n_csq + 1, TaskAa{0, 0u, 0u});
+    auto kind = [](const uint8_t* s, uint32_t n) -> uint32_t { return n == 1 && s[0] == '*' ? 2u : (n && memchr(s, '*', n) ? 1u : 0u); };
+    if (aa_begin[0] != 0) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin does not start at 0", 0);
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        if (aa_begin[i + 1] < aa_begin[i] || aa_begin[i + 1] > aa_begin[n_csq] || aa_begin[i + 1] - aa_begin[i] >= (1u << 30) || aa_ref_len[i] > aa_begin[i + 1] - aa_begin[i])
+            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin must ascend by less than 2^30 inside the bytes and hold aa_ref_len", int64_t(i));
+        const uint32_t rl = aa_ref_len[i], ml = uint32_t(aa_begin[i + 1] - aa_begin[i]) - rl;
+        rows[i] = TaskAa{aa_begin[i], rl | kind(aa + aa_begin[i], rl) << 30, ml | kind(aa + aa_begin[i] + rl, ml) << 30};
+    }
+    rows[n_csq] = TaskAa{aa_begin[n_csq], 0u, 0u};
+    return V2P_OK;
+}
+
+// ... and the rows and their bytes on the device: uploaded unless d already holds exactly these (*uploaded says which).  Whatever was
+// counted with the columns that go is dropped with them.
+static int aa_resident(v2p_ctx* ctx, v2p_decode* d, std::vector<TaskAa>& rows, const uint8_t* aa, hipStream_t st, bool* uploaded)
+{
+    AaTables& at = d->aa_tables;
+    const uint64_t n_aa = rows.back().begin;
+    if (at.aa && at.host_aa.size() == rows.size() && at.host_aa_bytes.size() == n_aa &&
+        !memcmp(at.host_aa.data(), rows.data(), rows.size() * sizeof(TaskAa)) && (!n_aa || !memcmp(at.host_aa_bytes.data(), aa, n_aa)))
+        return V2P_OK;
+    at = AaTables{};
+    d->tasks = Tasks{};
+    d->intmap = Intmap{};
+    TRY(at.aa.alloc(rows.size() * sizeof(TaskAa)), "hipMalloc(aa rows)");
+    TRY(at.aa_bytes.alloc(n_aa + 1), "hipMalloc(aa bytes)");
+    at.host_aa.swap(rows);
+    at.host_aa_bytes.assign(aa, aa + n_aa);
+    // (the copies are made from the decode's own vectors: they outlive the stream's work)
+    TRY(hipMemcpyAsync(at.aa.get<void>(), at.host_aa.data(), at.host_aa.size() * sizeof(TaskAa), hipMemcpyHostToDevice, st), "H2D(aa rows)");
+    if (n_aa) TRY(hipMemcpyAsync(at.aa_bytes.get<void>(), at.host_aa_bytes.data(), n_aa, hipMemcpyHostToDevice, st), "H2D(aa bytes)");
+    *uploaded = true;
+    return V2P_OK;
+}
+
 // the reference's words for an aborting item (the harness prints the same for its host loop)
 static std::string tasks_abort_text(uint32_t why, const std::string& name)
 {
@@ -773,18 +837,9 @@ int v2p_decode_tasks_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, const
     if (n_csq + 1 != d->tables.host_rec.size()) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": n_consequences is not that of the tables the CSR was made from", -1);
     if (n_transcripts > STATS_MAX_RANKS || n_slots >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts or 2^32 slots", -1);
     *info = v2p_tasks_info{};
-    // the strings, one row per consequence: inside the bytes, below 2^30 each, their MutatedString kind in the two top bits (mutation_ds.rs:50-76)
-    std::vector<TaskAa> rows(n_csq + 1);
-    auto kind = [](const uint8_t* s, uint32_t n) -> uint32_t { return n == 1 && s[0] == '*' ? 2u : (n && memchr(s, '*', n) ? 1u : 0u); };
-    if (aa_begin[0] != 0) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin does not start at 0", 0);
-    for (uint64_t i = 0; i < n_csq; ++i) {
-        if (aa_begin[i + 1] < aa_begin[i] || aa_begin[i + 1] > aa_begin[n_csq] || aa_begin[i + 1] - aa_begin[i] >= (1u << 30) || aa_ref_len[i] > aa_begin[i + 1] - aa_begin[i])
-            return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": aa_begin must ascend by less than 2^30 inside the bytes and hold aa_ref_len", int64_t(i));
-        const uint32_t rl = aa_ref_len[i], ml = uint32_t(aa_begin[i + 1] - aa_begin[i]) - rl;
-        rows[i] = TaskAa{aa_begin[i], rl | kind(aa + aa_begin[i], rl) << 30, ml | kind(aa + aa_begin[i] + rl, ml) << 30};
-    }
-    rows[n_csq] = TaskAa{aa_begin[n_csq], 0u, 0u};
-    const uint64_t n_aa = aa_begin[n_csq];
+    std::vector<TaskAa> rows;
+    const int arc = aa_rows(ctx, f, aa, aa_begin, aa_ref_len, n_csq, rows);
+    if (arc != V2P_OK) return arc;
     std::vector<TaskTx> txs(n_entries + 1, TaskTx{-1, {0, 0}, 0u, 0u});
     for (uint64_t t = 0; t < n_entries; ++t) {
         txs[t] = TaskTx{tx_proteome_off[t], {tx_header_off_1[t], tx_header_off_2[t]}, tx_ref_len[t], tx_header_len[t]};
@@ -809,23 +864,19 @@ int v2p_decode_tasks_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, const
     TRY(hipEventRecord(ev[0], st), "hipEventRecord");
     TaskTables& tt = d->task_tables;
     bool uploaded = false;
-    if (!(tt.aa && tt.host_aa.size() == rows.size() && tt.host_aa_bytes.size() == n_aa && tt.host_tx.size() == txs.size() &&
+    const int urc = aa_resident(ctx, d, rows, aa, st, &uploaded);
+    if (urc != V2P_OK) return urc;
+    const AaTables& at = d->aa_tables;
+    if (!(tt.tx && tt.host_tx.size() == txs.size() &&
           tt.host_slot_rank.size() == n_slots && (tt.slot_rank.get<void>() != nullptr) == write_all &&
-          !memcmp(tt.host_aa.data(), rows.data(), rows.size() * sizeof(TaskAa)) && (!n_aa || !memcmp(tt.host_aa_bytes.data(), aa, n_aa)) &&
           !memcmp(tt.host_tx.data(), txs.data(), txs.size() * sizeof(TaskTx)) &&
           (!n_slots || !memcmp(tt.host_slot_rank.data(), slot_rank, n_slots * sizeof(uint32_t))))) {
         tt = TaskTables{};
-        TRY(tt.aa.alloc(rows.size() * sizeof(TaskAa)), "hipMalloc(aa rows)");
-        TRY(tt.aa_bytes.alloc(n_aa + 1), "hipMalloc(aa bytes)");
         TRY(tt.tx.alloc(txs.size() * sizeof(TaskTx)), "hipMalloc(transcript rows)");
         if (write_all) TRY(tt.slot_rank.alloc((n_slots + 1) * sizeof(uint32_t)), "hipMalloc(slot ranks)");
-        tt.host_aa.swap(rows);
-        tt.host_aa_bytes.assign(aa, aa + n_aa);
         tt.host_tx.swap(txs);
         tt.host_slot_rank.assign(slot_rank, slot_rank + n_slots);
         // (the copies are made from the decode's own vectors: they outlive the stream's work)
-        TRY(hipMemcpyAsync(tt.aa.get<void>(), tt.host_aa.data(), tt.host_aa.size() * sizeof(TaskAa), hipMemcpyHostToDevice, st), "H2D(aa rows)");
-        if (n_aa) TRY(hipMemcpyAsync(tt.aa_bytes.get<void>(), tt.host_aa_bytes.data(), n_aa, hipMemcpyHostToDevice, st), "H2D(aa bytes)");
         TRY(hipMemcpyAsync(tt.tx.get<void>(), tt.host_tx.data(), tt.host_tx.size() * sizeof(TaskTx), hipMemcpyHostToDevice, st), "H2D(transcript rows)");
         if (n_slots) TRY(hipMemcpyAsync(tt.slot_rank.get<void>(), tt.host_slot_rank.data(), n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D(slot ranks)");
         uploaded = true;
@@ -844,7 +895,7 @@ int v2p_decode_tasks_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, const
     a.hap_group_begin = gr.hap_group_begin.get<unsigned long long>(); a.group_transcript = gr.group_transcript.get<uint32_t>();
     a.group_member_begin = gr.group_member_begin.get<unsigned long long>(); a.member_ids = gr.member_ids.get<uint32_t>();
     a.n_haps = uint32_t(n_haps); a.n_groups = gr.n_groups; a.n_members = gr.n_members;
-    a.rec = d->tables.rec.get<StatsRec>(); a.aa = tt.aa.get<TaskAa>(); a.n_csq = uint32_t(n_csq); a.aa_bytes = tt.aa_bytes.get<uint8_t>();
+    a.rec = d->tables.rec.get<StatsRec>(); a.aa = at.aa.get<TaskAa>(); a.n_csq = uint32_t(n_csq); a.aa_bytes = at.aa_bytes.get<uint8_t>();
     a.tx = tt.tx.get<TaskTx>(); a.n_tx = uint32_t(n_entries);
     a.slot_rank = write_all ? tt.slot_rank.get<uint32_t>() : nullptr; a.n_slots = uint32_t(n_slots);
     a.flags = flags; a.n_items = n_items;
@@ -964,6 +1015,173 @@ int v2p_decode_tasks_emit(v2p_ctx* ctx, v2p_decode* d, uint64_t h0, uint64_t h1,
 int v2p_decode_tasks_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit)
 {
     return d ? give_ms(d->tasks.ms, {ms_upload, ms_count, ms_scan, ms_emit}) : V2P_ERR_INVALID_ARG;
+}
+
+// ---- (9) -i / --write_int_map on the device ----------------------------------------------------------------------------------
+int v2p_decode_intmap_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, const uint64_t* aa_begin, const uint32_t* aa_ref_len, uint64_t n_csq,
+                            const uint8_t* tx_json, const uint64_t* tx_json_begin, uint64_t n_transcripts,
+                            const uint8_t* sample_json, const uint64_t* sample_json_begin, uint64_t n_samples,
+                            uint64_t* proband_bytes, v2p_intmap_info* info)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f = "v2p_decode_intmap_count";
+    if (!d || d->ctx != ctx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null decode, or one of another context", -1);
+    Groups& gr = d->groups;
+    if (!gr.ok || !d->tables.rec) return ctx_fail(ctx, V2P_ERR_STATE, f + ": needs the CSR of a successful v2p_decode_groups on this decode", -1);
+    if (!aa_begin || (n_csq && !aa_ref_len) || (n_csq && aa_begin[n_csq] && !aa) || !tx_json_begin || !sample_json_begin || !proband_bytes ||
+        (tx_json_begin[n_transcripts] && !tx_json) || (sample_json_begin[n_samples] && !sample_json))
+        return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    if (n_csq + 1 != d->tables.host_rec.size()) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": n_consequences is not that of the tables the CSR was made from", -1);
+    if (n_samples != d->n_samples) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": n_samples is not that of the decode", -1);
+    if (n_transcripts > STATS_MAX_RANKS) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": more than 2^24 transcripts", -1);
+    if (gr.n_groups >= 0xffffffffull) return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": 2^32 groups or more", -1);
+    if (tx_json_begin[0] != 0 || sample_json_begin[0] != 0) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": name offsets do not start at 0", 0);
+    for (uint64_t r = 0; r < n_transcripts; ++r)
+        if (tx_json_begin[r + 1] < tx_json_begin[r]) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": tx_json_begin descends", int64_t(r));
+    for (uint64_t s = 0; s < n_samples; ++s)
+        if (sample_json_begin[s + 1] < sample_json_begin[s]) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": sample_json_begin descends", int64_t(s));
+    uint64_t n_frag = 0;
+    for (uint64_t i = 0; i < n_csq; ++i) {
+        const StatsRec& r = d->tables.host_rec[i];
+        if (!(r.flags & 1u)) continue;
+        if (r.rank >= n_transcripts) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": a consequence's transcript has no name", int64_t(i));
+        ++n_frag;
+    }
+    std::vector<TaskAa> rows;
+    const int arc = aa_rows(ctx, f, aa, aa_begin, aa_ref_len, n_csq, rows);
+    if (arc != V2P_OK) return arc;
+
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    const uint64_t n_haps = 2 * n_samples, n_tx_bytes = tx_json_begin[n_transcripts], n_sample_bytes = sample_json_begin[n_samples];
+    d->intmap = Intmap{};
+    Events<6> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    bool uploaded = false;
+    const int urc = aa_resident(ctx, d, rows, aa, st, &uploaded);
+    if (urc != V2P_OK) return urc;
+    (void)uploaded;
+    Intmap& im = d->intmap;
+    TRY(im.tx_json.alloc(n_tx_bytes + 1), "hipMalloc(transcript names)");
+    TRY(im.tx_json_begin.alloc((n_transcripts + 1) * sizeof(uint64_t)), "hipMalloc(transcript name offsets)");
+    TRY(im.sample_json.alloc(n_sample_bytes + 1), "hipMalloc(sample names)");
+    TRY(im.sample_json_begin.alloc((n_samples + 1) * sizeof(uint64_t)), "hipMalloc(sample name offsets)");
+    // (pageable copies return once the source has been read: the caller's arrays need not outlive the call)
+    if (n_tx_bytes) TRY(hipMemcpyAsync(im.tx_json.get<void>(), tx_json, n_tx_bytes, hipMemcpyHostToDevice, st), "H2D(transcript names)");
+    TRY(hipMemcpyAsync(im.tx_json_begin.get<void>(), tx_json_begin, (n_transcripts + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(transcript name offsets)");
+    if (n_sample_bytes) TRY(hipMemcpyAsync(im.sample_json.get<void>(), sample_json, n_sample_bytes, hipMemcpyHostToDevice, st), "H2D(sample names)");
+    TRY(hipMemcpyAsync(im.sample_json_begin.get<void>(), sample_json_begin, (n_samples + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st), "H2D(sample name offsets)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+
+    TRY(im.frag_len.alloc((n_csq + 1) * sizeof(uint32_t)), "hipMalloc(fragment lengths)");
+    TRY(im.frag_begin.alloc((n_csq + 1) * sizeof(uint64_t)), "hipMalloc(fragment offsets)");
+    TRY(im.group_len.alloc((gr.n_groups + 1) * sizeof(uint32_t)), "hipMalloc(group lengths)");
+    TRY(im.group_begin.alloc((gr.n_groups + 1) * sizeof(uint64_t)), "hipMalloc(group offsets)");
+    TRY(im.proband_len.alloc((n_samples + 1) * sizeof(uint32_t)), "hipMalloc(proband lengths)");
+    TRY(im.proband_begin.alloc((n_samples + 1) * sizeof(uint64_t)), "hipMalloc(proband offsets)");
+    TRY(im.status.alloc(4 * sizeof(uint64_t)), "hipMalloc(intmap status)");
+    TRY(hipMemsetAsync(im.status.get<void>(), 0, 4 * sizeof(uint64_t), st), "hipMemset(intmap status)");
+    IntmapArgs& a = im.args;
+    a.hap_group_begin = gr.hap_group_begin.get<unsigned long long>(); a.group_transcript = gr.group_transcript.get<uint32_t>();
+    a.group_member_begin = gr.group_member_begin.get<unsigned long long>(); a.member_ids = gr.member_ids.get<uint32_t>();
+    a.n_samples = uint32_t(n_samples); a.n_groups = gr.n_groups; a.n_members = gr.n_members;
+    a.rec = d->tables.rec.get<StatsRec>(); a.aa = d->aa_tables.aa.get<TaskAa>(); a.aa_bytes = d->aa_tables.aa_bytes.get<uint8_t>(); a.n_csq = uint32_t(n_csq);
+    a.tx_json = im.tx_json.get<uint8_t>(); a.tx_json_begin = im.tx_json_begin.get<unsigned long long>(); a.n_tx = uint32_t(n_transcripts);
+    a.sample_json = im.sample_json.get<uint8_t>(); a.sample_json_begin = im.sample_json_begin.get<unsigned long long>();
+    a.frag_len = im.frag_len.get<uint32_t>(); a.frag_begin = im.frag_begin.get<unsigned long long>();
+    a.group_len = im.group_len.get<uint32_t>(); a.group_begin = im.group_begin.get<unsigned long long>();
+    a.proband_len = im.proband_len.get<uint32_t>(); a.proband_begin = im.proband_begin.get<unsigned long long>();
+    a.status = im.status.get<unsigned long long>();
+    unsigned long long* d_totals = a.status + 1;        // the three scans' totals
+    float ms_count = 0, ms_scan = 0, ms = 0;
+    // fragments: lengths, offsets, bytes
+    TRY(launch_intmap_fragments(a, false, st), "intmap_fragment_kernel (count)");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(launch_csq_scan(a.frag_len, uint32_t(n_csq), a.frag_begin, nullptr, d_totals + 0, st), "csq_scan_kernel (fragments)");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    uint64_t frag_bytes = 0;
+    TRY(hipMemcpyAsync(&frag_bytes, d_totals + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(fragment bytes)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&im.ms[0], ev[0], ev[1]);      // (the names every time; the amino-acid columns when `uploaded`)
+    (void)hipEventElapsedTime(&ms, ev[1], ev[2]); ms_count += ms;
+    (void)hipEventElapsedTime(&ms, ev[2], ev[3]); ms_scan += ms;
+    TRY(im.frag.alloc(frag_bytes + 1), "hipMalloc(fragments)");
+    a.frag = im.frag.get<uint8_t>(); a.frag_bytes = frag_bytes;
+    // groups, then probands: lengths and offsets
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    TRY(launch_intmap_fragments(a, true, st), "intmap_fragment_kernel (emit)");
+    TRY(launch_intmap_group_count(a, st), "intmap_group_count_kernel");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(launch_csq_scan(a.group_len, uint32_t(gr.n_groups), a.group_begin, nullptr, d_totals + 1, st), "csq_scan_kernel (groups)");
+    TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+    TRY(launch_intmap_proband_count(a, st), "intmap_proband_count_kernel");
+    TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+    TRY(launch_csq_scan(a.proband_len, uint32_t(n_samples), a.proband_begin, nullptr, d_totals + 2, st), "csq_scan_kernel (probands)");
+    TRY(hipEventRecord(ev[5], st), "hipEventRecord");
+    uint64_t status = 0;
+    im.host_proband_begin.assign(n_samples + 1, 0);
+    im.host_hap_group_begin.assign(n_haps + 1, 0);
+    TRY(hipMemcpyAsync(&status, a.status, sizeof(status), hipMemcpyDeviceToHost, st), "D2H(intmap status)");
+    TRY(hipMemcpyAsync(im.host_proband_begin.data(), a.proband_begin, (n_samples + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(proband offsets)");
+    TRY(hipMemcpyAsync(im.host_hap_group_begin.data(), gr.hap_group_begin.get<void>(), (n_haps + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(hap_group_begin)");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&ms, ev[1], ev[2]); ms_count += ms;
+    (void)hipEventElapsedTime(&ms, ev[2], ev[3]); ms_scan += ms;
+    (void)hipEventElapsedTime(&ms, ev[3], ev[4]); ms_count += ms;
+    (void)hipEventElapsedTime(&ms, ev[4], ev[5]); ms_scan += ms;
+    im.ms[1] = ms_count; im.ms[2] = ms_scan;
+    if (status == 1) return ctx_fail(ctx, V2P_ERR_UNSUPPORTED, f + ": a group or a proband of 4 GiB or more", -1);
+    if (status != 0) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": the grouped CSR does not fit these tables", -1);
+    const std::vector<uint64_t>& hgb = im.host_hap_group_begin;
+    for (uint64_t h = 0; h < n_haps; ++h)
+        if (hgb[h + 1] < hgb[h] || hgb[h + 1] > gr.n_groups) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": the grouped CSR does not fit these tables", int64_t(h));
+    for (uint64_t s = 0; s < n_samples; ++s) proband_bytes[s] = im.host_proband_begin[s + 1] - im.host_proband_begin[s];
+    if (info) { info->n_fragments = n_frag; info->fragment_bytes = frag_bytes; info->out_bytes = im.host_proband_begin[n_samples]; }
+    im.ok = true;
+    return V2P_OK;
+}
+
+int v2p_decode_intmap_emit(v2p_ctx* ctx, v2p_decode* d, uint64_t s0, uint64_t s1, uint8_t* host_out, uint64_t n_out)
+{
+    if (!ctx) return V2P_ERR_INVALID_ARG;
+    Guard g(ctx);
+    const std::string f = "v2p_decode_intmap_emit";
+    if (!d || d->ctx != ctx) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null decode, or one of another context", -1);
+    Intmap& im = d->intmap;
+    if (!im.ok || !d->groups.ok) return ctx_fail(ctx, V2P_ERR_STATE, f + ": needs a successful v2p_decode_intmap_count on this decode", -1);
+    if (s0 > s1 || s1 > d->n_samples) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": sample range outside the file", -1);
+    const std::vector<uint64_t>& pb = im.host_proband_begin;
+    if (n_out != pb[s1] - pb[s0]) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": n_out is not the sum of the range's proband_bytes", -1);
+    if (n_out && !host_out) return ctx_fail(ctx, V2P_ERR_INVALID_ARG, f + ": null argument", -1);
+    im.ms[3] = im.ms[4] = 0;
+    if (!n_out) return V2P_OK;
+    (void)hipSetDevice(ctx_device(ctx));
+    hipStream_t st = ctx_stream(ctx);
+    DevMem d_out;                                       // freed on every exit path
+    Events<3> ev;
+    TRY(ev.create(), "hipEventCreate");
+    TRY(d_out.alloc(n_out), "hipMalloc(intmap bytes)");
+    IntmapArgs a = im.args;
+    a.s0 = uint32_t(s0); a.s1 = uint32_t(s1);
+    a.g0 = im.host_hap_group_begin[2 * s0]; a.g1 = im.host_hap_group_begin[2 * s1];
+    a.out_base = pb[s0]; a.out = d_out.get<uint8_t>(); a.out_bytes = n_out;
+    TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    TRY(launch_intmap_emit(a, st), "intmap_emit kernels");
+    TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    TRY(hipMemcpyAsync(host_out, d_out.get<void>(), n_out, hipMemcpyDeviceToHost, st), "D2H(intmap bytes)");
+    TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&im.ms[3], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&im.ms[4], ev[1], ev[2]);
+    return V2P_OK;
+}
+
+int v2p_decode_intmap_timing(const v2p_decode* d, float* ms_upload, float* ms_count, float* ms_scan, float* ms_emit, float* ms_download)
+{
+    return d ? give_ms(d->intmap.ms, {ms_upload, ms_count, ms_scan, ms_emit, ms_download}) : V2P_ERR_INVALID_ARG;
 }
 
 int v2p_decode_tables_build(v2p_ctx* ctx, v2p_decode* d, const uint8_t* text, const uint64_t* csq_text_begin, const uint32_t* csq_text_len,

@@ -73,6 +73,10 @@ DECODE_API = {
     "v2p_decode_index_build": (c_int, [c_void_p, c_void_p, c_void_p]),
     "v2p_decode_index_download": (c_int, [c_void_p] + [c_void_p] * 8),
     "v2p_decode_index_timing": (c_int, [c_void_p] + [POINTER(c_float)] * 5),
+    "v2p_decode_intmap_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64,
+                                        c_void_p, c_void_p]),
+    "v2p_decode_intmap_emit": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint64]),
+    "v2p_decode_intmap_timing": (c_int, [c_void_p] + [POINTER(c_float)] * 5),
 }
 # ... and in libv2p_cohort.so (plain C++)
 HOST_API = {
@@ -123,6 +127,7 @@ HOST_API = {
     "v2p_csq_tables_from_arrays": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64] + [c_void_p] * 12 + [POINTER(c_void_p)]),
     "v2p_vcf_index_from_arrays": (c_int, [c_uint64, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                           c_void_p, POINTER(c_void_p)]),
+    "v2p_groups_intmap_json": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64)]),
 }
 
 
@@ -161,6 +166,10 @@ class v2p_index_info(ctypes.Structure):
 
 class v2p_tasks_info(ctypes.Structure):
     _fields_ = [("n_items", c_uint64), ("n_tx", c_uint64), ("n_tasks", c_uint64), ("n_alt", c_uint64), ("out_bytes", c_uint64)]
+
+
+class v2p_intmap_info(ctypes.Structure):
+    _fields_ = [("n_fragments", c_uint64), ("fragment_bytes", c_uint64), ("out_bytes", c_uint64)]
 
 
 _bound = {}
@@ -525,6 +534,18 @@ class Groups:
             raise N.V2PError(rc, "v2p_groups_stats failed")
         return pp, pt, px[:self.n_transcripts]
 
+    def intmap_json(self, sample: int, name) -> bytes:
+        """v2p_groups_intmap_json: the proband's IntMap as serde_json::to_writer writes it (-i / --write_int_map), off the CSR on the
+        host.  `name` (str or bytes) is escaped by the library."""
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        n = c_uint64()
+        self._lib.v2p_groups_intmap_json(self._h, sample, name, len(name), None, 0, ctypes.byref(n))
+        out = np.zeros(n.value, np.uint8)
+        rc = self._lib.v2p_groups_intmap_json(self._h, sample, name, len(name), out.ctypes.data, out.size, ctypes.byref(n))
+        if rc != 0:
+            raise N.V2PError(rc, "v2p_groups_intmap_json failed", sample)
+        return out.tobytes()
+
     def of(self, hap: int):
         """[(transcript name, [consequence ids])] of one haplotype, in the reference's order."""
         out = []
@@ -772,6 +793,94 @@ def device_tasks_timing(resident: ResidentLists) -> dict:
     t = [c_float() for _ in range(4)]
     _hip().v2p_decode_tasks_timing(resident._h, *[ctypes.byref(x) for x in t])
     return dict(zip(("upload", "count", "scan", "emit"), (x.value for x in t)))
+
+
+# ---- -i / --write_int_map (include/v2p_frontend.h part 9) ----------------------------------------------------------------------
+_JSON_ESCAPES = {0x22: b'\\"', 0x5C: b"\\\\", 0x08: b"\\b", 0x0C: b"\\f", 0x0A: b"\\n", 0x0D: b"\\r", 0x09: b"\\t"}
+_JSON_TABLE = [_JSON_ESCAPES.get(c, b"\\u%04x" % c if c < 0x20 else bytes([c])) for c in range(256)]
+
+
+def json_escape(x) -> bytes:
+    """serde_json's string escaping of bytes (or of a str's UTF-8): \\" \\\\ \\b \\f \\n \\r \\t, other bytes below 0x20 as \\u00xx, the rest unchanged"""
+    x = x.encode() if isinstance(x, str) else bytes(x)
+    return b"".join(_JSON_TABLE[c] for c in x)
+
+
+def int_map_name_refused(name: str) -> bool:
+    """a sample name -i refuses before anything is written: it would not name a file inside int_maps/"""
+    return name in ("", ".", "..") or "/" in name
+
+
+def int_map_file_name(name: str) -> str:
+    """PathBuf::push(name) + set_extension("json"): the sample name up to its last '.', unless that dot is its first byte"""
+    dot = name.rfind(".")
+    return (name if dot <= 0 else name[:dot]) + ".json"
+
+
+def _json_blob(names):
+    esc = [json_escape(n) for n in names]
+    begin = np.concatenate([[0], np.cumsum([len(e) for e in esc])]).astype(np.uint64)
+    return np.frombuffer(b"".join(esc) or b"\0", np.uint8).copy(), begin
+
+
+def _transcript_names_bytes(tables):
+    names = getattr(tables, "tx_names", None)
+    if names is not None:
+        return list(names)
+    text = tables._idx.text
+    return [text[int(b):int(b) + int(n)].tobytes() for b, n in zip(tables.transcript_begin, tables.transcript_len)]
+
+
+def device_intmap_count(ctx, resident: ResidentLists, tables, samples):
+    """v2p_decode_intmap_count on the CSR the last v2p_decode_groups left on `resident`: (proband_bytes [n_samples], info dict).  `tables`
+    is a CsqTables or anything with its arrays (tx_names, a list of bytes by rank, overrides the names in its text); `samples` the sample
+    names (str or bytes) in VCF order."""
+    lib = _hip()
+    tx, tx_begin = _json_blob(_transcript_names_bytes(tables))
+    sm, sm_begin = _json_blob(samples)
+    out = np.zeros(len(samples) + 1, np.uint64)
+    info = v2p_intmap_info()
+    rc = lib.v2p_decode_intmap_count(ctx._h, resident._h, _ptr(tables.aa), tables.aa_begin.ctypes.data, _ptr(tables.aa_ref_len), tables.n_consequences,
+                                     tx.ctypes.data, tx_begin.ctypes.data, tx_begin.size - 1, sm.ctypes.data, sm_begin.ctypes.data, len(samples),
+                                     out.ctypes.data, ctypes.byref(info))
+    _check(ctx, rc)
+    return out[:len(samples)], {k: int(getattr(info, k)) for k, _ in v2p_intmap_info._fields_}
+
+
+def device_intmap_emit(ctx, resident: ResidentLists, s0: int, s1: int, n_out: int) -> bytes:
+    """v2p_decode_intmap_emit: the files of samples [s0, s1) of the last device_intmap_count, back to back"""
+    out = np.zeros(max(n_out, 1), np.uint8)
+    _check(ctx, _hip().v2p_decode_intmap_emit(ctx._h, resident._h, s0, s1, out.ctypes.data, n_out))
+    return out[:n_out].tobytes()
+
+
+def device_intmap_timing(resident: ResidentLists) -> dict:
+    t = [c_float() for _ in range(5)]
+    _hip().v2p_decode_intmap_timing(resident._h, *[ctypes.byref(x) for x in t])
+    return dict(zip(("upload", "count", "scan", "emit", "download"), (x.value for x in t)))
+
+
+def device_intmap_json(ctx, resident: ResidentLists, tables, samples, s0=None, s1=None):
+    """-i / --write_int_map on the GPU: count, then emit samples [s0, s1) (default: all) in one range.  ([file bytes per sample of the
+    range], proband_bytes of the whole file, info dict with timing_ms)"""
+    sizes, info = device_intmap_count(ctx, resident, tables, samples)
+    s0 = 0 if s0 is None else s0
+    s1 = len(samples) if s1 is None else s1
+    cut = np.concatenate([[0], np.cumsum(sizes[s0:s1])]).astype(np.int64)
+    data = device_intmap_emit(ctx, resident, s0, s1, int(cut[-1]))
+    info["timing_ms"] = device_intmap_timing(resident)
+    return [data[int(cut[k]):int(cut[k + 1])] for k in range(s1 - s0)], sizes, info
+
+
+def write_int_maps(outdir, samples, files) -> None:
+    """<outdir>/int_maps/<stem>.json per sample, in sample order (two samples with one stem: the later one wins, as in the reference's
+    sequential loop); the directory is created if absent and reused if present.  The names must have passed int_map_name_refused."""
+    import os
+    d = os.path.join(outdir, "int_maps")
+    os.makedirs(d, exist_ok=True)
+    for name, data in zip(samples, files):
+        with open(os.path.join(d, int_map_file_name(name)), "wb") as f:
+            f.write(data)
 
 
 class CohortStats:

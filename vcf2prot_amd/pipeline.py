@@ -96,7 +96,36 @@ def resident_reference(names, ref):
     return proteome, np.frombuffer("".join(hdr).encode(), dtype=np.uint8), off, hdr_off
 
 
-def _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report):
+def _int_maps(ctx, idx, resident, tables, groups, outdir, slice_bytes, report, on_device):
+    """-i / --write_int_map: <outdir>/int_maps/<stem>.json per proband (frontend.write_int_maps), after the grouping has succeeded and
+    before anything else is made.  By default the host restatement reads it off the Groups.  on_device (opt-in), or groups None (device
+    tasks: the CSR exists on `resident` only): it is serialised there (include/v2p_frontend.h part 9) -- counted once, then emitted and
+    written in sample ranges of about slice_bytes.  A grouping that fell back to the host always takes the host restatement.  Same bytes."""
+    from .frontend import (device_intmap_count, device_intmap_emit, device_intmap_timing, int_map_name_refused, write_int_maps)
+    samples = idx.sample_names()
+    for name in samples:
+        if int_map_name_refused(name):
+            raise N.V2PError(-1, f"sample name {name!r} cannot name a file under int_maps (empty, '.', '..' or with a '/')")
+    if groups is not None and (groups.path != "device" or not on_device):
+        write_int_maps(outdir, samples, [groups.intmap_json(s, name) for s, name in enumerate(samples)])
+        if report is not None:
+            report["int_map"] = {"path": "host"}
+        return
+    sizes, info = device_intmap_count(ctx, resident, tables, samples)
+    s0 = acc = n_ranges = 0
+    for s in range(len(samples)):
+        acc += int(sizes[s])
+        if acc < slice_bytes and s + 1 != len(samples):
+            continue
+        data = device_intmap_emit(ctx, resident, s0, s + 1, acc)
+        cut = np.concatenate([[0], np.cumsum(sizes[s0:s + 1])]).astype(np.int64)
+        write_int_maps(outdir, samples[s0:s + 1], [data[int(cut[k]):int(cut[k + 1])] for k in range(s + 1 - s0)])
+        s0, acc, n_ranges = s + 1, 0, n_ranges + 1
+    if report is not None:
+        report["int_map"] = dict(info, path="device", n_ranges=n_ranges, timing_ms=device_intmap_timing(resident))
+
+
+def _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report, write_int_map=None):
     """vcf_to_fasta with steps 4a / 4b on the device (include/v2p_frontend.h part 6): the grouped CSR never leaves the device.  The
     per-haplotype arena sizes of the count cut the probands into slices of about slice_bytes; every slice is emitted as a resident stream,
     built and executed by the one call, and read back -- one slice after the other.  A slice the one call refuses (V2P_ERR_UNSUPPORTED) is
@@ -110,6 +139,8 @@ def _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes
         raise err
     if report is not None:
         report["groups"] = dict(ginfo, path="device")
+    if write_int_map:
+        _int_maps(ctx, idx, resident, tables, None, write_int_map, slice_bytes, report, True)
     file_names = tables.transcript_names()
     names = sorted(set(file_names) | set(ref), key=lambda x: x.encode()) if write_all else file_names
     proteome, headers, off, hdr_off = resident_reference(names, ref)
@@ -187,7 +218,7 @@ def _csq_tables(ctx, idx, resident, on_device, report):
 def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFAULT_FLAGS, write_all: bool = False,
                  device_build: bool = True, slice_bytes: int = 256 << 20, bgzf: bool = False, host_groups: bool = False,
                  groups_caps=None, report: dict = None, device_tasks: bool = False, device_tables: bool = False,
-                 device_index: bool = False) -> Dict[str, bytes]:
+                 device_index: bool = False, write_int_map=False, device_int_map: bool = False) -> Dict[str, bytes]:
     """{proband: text of <proband>.fasta}: the altered transcripts (personalized_genome.rs:72-117) or, with write_all
     (-a / --write_all_proteins, :118-204), every transcript of the reference per haplotype, unaltered ones as they are.
     device_build (default): the per-transcript GIRs of whole probands are gathered into SLICES of about `slice_bytes` of FASTA text and
@@ -212,7 +243,11 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
     device_index (opt-in): the record index is built on the GPU from the resident text (VcfIndex.from_device, include/v2p_frontend.h part 8):
     flat or host-inflated text is uploaded first and the decode runs on that same handle -- same columns, same bytes.  A file the index
     refuses raises the V2PError the host index raises; there is no fallback.  report receives {"index": {"path": "device" | "host",
-    "ms": ..., ...}}."""
+    "ms": ..., ...}}.
+    write_int_map (-i / --write_int_map): an output directory, or False.  Every proband's IntMap is written as JSON to
+    <write_int_map>/int_maps/<stem>.json (the directory is created if absent), as soon as the grouping has succeeded: by the host restatement,
+    or -- device_int_map (opt-in), and always with device_tasks -- serialised on the GPU from the grouped CSR there (_int_maps).  report
+    receives {"int_map": {"path": ...}}."""
     import time
     from .bgzf import EOF_BLOCK
     ref = read_fasta(reference_fasta)
@@ -239,13 +274,15 @@ def vcf_to_fasta(ctx, vcf: bytes, reference_fasta: str, flags: int = step4a.DEFA
         tables = _csq_tables(ctx, idx, resident, device_tables, report)
         try:
             if device_tasks and device_build and not host_groups:
-                out = _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report)
+                out = _device_tasks(ctx, idx, resident, tables, ref, flags, write_all, slice_bytes, bgzf, groups_caps, report, write_int_map)
                 if out is not None:
                     return out
             if host_groups:
                 groups = Groups.from_tables(tables, resident.download())
             else:
                 groups = device_groups(ctx, idx, resident, tables, groups_caps)
+            if write_int_map:
+                _int_maps(ctx, idx, resident, tables, groups, write_int_map, slice_bytes, report, device_int_map)
         finally:
             tables.close()
     finally:
