@@ -349,7 +349,8 @@ int v2p_batch_counts(const v2p_batch* b, uint64_t* n_haps, uint64_t* n_desc, uin
 /* in what form the batch's image sits on the device right now (diagnostics, tests): bit 0 = padded wave image (v2p_batch_build_and_execute;
  * made dense by the next v2p_batch_execute / download), bit 1 = a piece image was built (a dense rows image that is executed again:
  * vcf2prot_amd/csrc/dense_pieces.h), bit 2 = staging buffers for the phases' descriptors exist, bit 3 = a TILE image (pieces in the tiles' slots:
- * v2p_batch_download_image has no descriptors or chunks to hand out, v2p_batch_counts reports pieces and tiles in their place) */
+ * v2p_batch_download_image has no descriptors or chunks to hand out, v2p_batch_counts reports pieces and tiles in their place), bit 4 = the batch holds RESIDENT descriptor
+ * rows of its image (a wave image that has been executed again) and the next v2p_batch_execute runs from them */
 int v2p_batch_image_form(const v2p_batch* b);
 /* result range of haplotype h inside the arena */
 int v2p_batch_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len);

@@ -127,10 +127,35 @@ constexpr uint32_t TOUCH_CHUNKS_PER_WAVE = 4;      // records, then first descri
 // slots per chunk -- the stitch wave of chunk c then loads its descriptors from stage[64 c + lane], an address it knows before its
 // chunk record has arrived (one round trip less in its chain), from lines this XCD has just written; the image's own array -- dense,
 // or the tiles' slots of a padded image (sir_pack.hpp) -- is only ever read here, as a stream.
+// rows != nullptr (RESIDENT rows: an image that is executed AGAIN, launch_stitch): row (chunk index) of `rows` already holds what the
+// mode above would copy there -- the image does not change between two executes -- so the wave only LOADS: the rows, the chunk records
+// and the payload lines the rows' descriptors name.  Nothing is written and the image's own array is not read at all.
 __device__ __forceinline__ void touch_chunks(const uint64_t* __restrict__ desc, const Chunk* __restrict__ chunks, uint32_t c0, uint32_t n_chunks, uint64_t n_desc,
-                                             const uint8_t* __restrict__ payload, uint64_t payload_len, uint32_t lane, uint64_t* __restrict__ stage = nullptr)
+                                             const uint8_t* __restrict__ payload, uint64_t payload_len, uint32_t lane, uint64_t* __restrict__ stage = nullptr,
+                                             const uint64_t* __restrict__ rows = nullptr)
 {
     if (c0 >= n_chunks) return;
+    auto payload_lines = [&](uint64_t dd) {
+        const uint64_t src = dd & SRC_MASK, len = (dd >> 40) & LEN_MASK;
+        if ((dd >> 62) == SPACE_PAYLOAD && len != 0u && src < payload_len && len <= payload_len - src) {
+            const uint32_t b0 = payload[src], b1 = payload[src + len - 1u];
+            asm volatile("" :: "v"(b0), "v"(b1));
+        }
+    };
+    if (rows) {
+        uint64_t r[TOUCH_CHUNKS_PER_WAVE], t[TOUCH_CHUNKS_PER_WAVE];
+#pragma unroll
+        for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) {
+            const uint32_t c = c0 + 8u * k < n_chunks ? c0 + 8u * k : c0;
+            r[k] = rows[uint64_t(c) * STAGE_SLOTS + lane];
+            t[k] = reinterpret_cast<const uint64_t*>(chunks + c)[lane & 1u];        // (the record's line; a wave chunk has no descriptors past its row)
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) payload_lines(r[k]);
+#pragma unroll
+        for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) asm volatile("" :: "v"(r[k]), "v"(t[k]));
+        return;
+    }
     Chunk ch[TOUCH_CHUNKS_PER_WAVE];
 #pragma unroll
     for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) ch[k] = chunks[c0 + 8u * k < n_chunks ? c0 + 8u * k : c0];
@@ -147,13 +172,6 @@ __device__ __forceinline__ void touch_chunks(const uint64_t* __restrict__ desc, 
         for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k)
             if (c0 + 8u * k < n_chunks) stage[uint64_t(c0 + 8u * k) * STAGE_SLOTS + lane] = d[k];
     }
-    auto payload_lines = [&](uint64_t dd) {
-        const uint64_t src = dd & SRC_MASK, len = (dd >> 40) & LEN_MASK;
-        if ((dd >> 62) == SPACE_PAYLOAD && len != 0u && src < payload_len && len <= payload_len - src) {
-            const uint32_t b0 = payload[src], b1 = payload[src + len - 1u];
-            asm volatile("" :: "v"(b0), "v"(b1));
-        }
-    };
 #pragma unroll
     for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) payload_lines(d[k]);
     for (uint32_t k = 0; k < TOUCH_CHUNKS_PER_WAVE; ++k) {           // chunks of more than 64 descriptors (per-block, dense images)

@@ -53,12 +53,20 @@ struct StitchArgs {
     uint32_t        stage_chunks = 0;        // rows per buffer: at least stitch_stage_chunks() of the same arguments
     const uint64_t* stage_cur = nullptr;     // set by launch_stitch(): this phase's buffer / the next phase's
     uint64_t*       stage_next = nullptr;
+    // RESIDENT rows (an image that is executed AGAIN; the ride form of a pure wave rows image, whole-table launches only): ONE buffer of
+    // ((n_chunks + 7) & ~7) x 64 slots, row = chunk index in the WHOLE table, filled once by launch_stage_rows() -- a phase's stage_cur is
+    // its first row there whatever the phase size, and the read-ahead writes nothing (stitch_device.hpp: touch_chunks, rows)
+    const uint64_t* resident = nullptr;      // (nullptr: none -- staged per phase into `stage`, or read in place)
+    const uint64_t* rows_next = nullptr;     // set by launch_stitch(): the next phase's first resident row
     uint32_t        phase_chunks = 0;        // set by launch_stitch(): != 0 -- ONE wave launch for all phases of that many chunks, the read-ahead
                                              // workgroups of phase g + 1 placed in the grid before the stitch workgroups of phase g
 };
 
 // rows per staging buffer launch_stitch() would use for these arguments (0: this image is not launched in the form that stages)
 uint32_t stitch_stage_chunks(const StitchArgs& args, int nontemporal);
+// resident rows of the WHOLE chunk table of `args`: one launch of what the read-ahead does when it stages, every slot of every row written
+// (the rows of the rounding up to a multiple of 8 hold fills); rows: [((n_chunks + 7) & ~7) * 64]
+hipError_t launch_stage_rows(const StitchArgs& args, uint64_t* rows, hipStream_t stream);
 
 struct OrderedArgs {
     const uint8_t*  code;

@@ -1248,10 +1248,28 @@ static const uint8_t* device_dots(hipError_t* err)
 // (PHASE_BYTES_DEFAULT / PHASE_BYTES_RICH / PHASE_MIN_CHUNKS and image_is_rich(): sir_pack.hpp, next to the chunk order's rule)
 
 __global__ __launch_bounds__(256) void touch_image_kernel(const uint64_t* __restrict__ desc, const Chunk* __restrict__ chunks, uint32_t n_chunks, uint64_t n_desc,
-                                                          const uint8_t* __restrict__ payload, uint64_t payload_len, uint64_t* __restrict__ stage)
+                                                          const uint8_t* __restrict__ payload, uint64_t payload_len, uint64_t* __restrict__ stage,
+                                                          const uint64_t* __restrict__ rows = nullptr)
 {
     // workgroup b runs on XCD b % 8: its four waves read chunks of residue b % 8
-    touch_chunks(desc, chunks, touch_wave_first(blockIdx.x & 7u, (blockIdx.x >> 3) * 4u + (threadIdx.x >> 6)), n_chunks, n_desc, payload, payload_len, threadIdx.x & 63u, stage);
+    uint32_t q = (blockIdx.x >> 3) * 4u + (threadIdx.x >> 6);
+    if (rows) { const uint32_t tq = touch_waves_per_xcd(n_chunks); if (q >= tq) return; q = tq - 1u - q; }      // (resident rows: last chunk first, see stitchw_kernel)
+    touch_chunks(desc, chunks, touch_wave_first(blockIdx.x & 7u, q), n_chunks, n_desc, payload, payload_len, threadIdx.x & 63u, stage, rows);
+}
+
+// the rows [first, first + n) of a resident rows buffer filled with fills (the rounding up of the chunk count to a multiple of 8)
+__global__ __launch_bounds__(64) void fill_rows_kernel(uint64_t* __restrict__ rows, uint64_t first, uint32_t n)
+{
+    if (blockIdx.x < n) rows[(first + blockIdx.x) * STAGE_SLOTS + threadIdx.x] = uint64_t(SPACE_FILL) << 62;
+}
+
+hipError_t launch_stage_rows(const StitchArgs& a, uint64_t* rows, hipStream_t stream)
+{
+    if (a.n_chunks == 0 || !rows) return hipSuccess;
+    hipLaunchKernelGGL(touch_image_kernel, dim3(8u * ((touch_waves_per_xcd(a.n_chunks) + 3u) / 4u)), dim3(256), 0, stream, a.desc, a.chunks, a.n_chunks, a.n_desc, a.src1, a.src1_len, rows, nullptr);
+    const uint32_t pad = (8u - (a.n_chunks & 7u)) & 7u;
+    if (pad) hipLaunchKernelGGL(fill_rows_kernel, dim3(pad), dim3(64), 0, stream, rows, uint64_t(a.n_chunks), pad);
+    return hipGetLastError();
 }
 
 static hipError_t launch_stitch_range(const StitchArgs& args, hipStream_t stream, int nontemporal, uint32_t max_blocks);
@@ -1327,7 +1345,7 @@ hipError_t launch_stitch(const StitchArgs& args, hipStream_t stream, int nontemp
     // a pure wave image: the read-ahead of phase k + 1 rides on the trailing workgroups of phase k's launch (they are dispatched while
     // its last chunks drain) instead of a kernel of its own between the two; only phase 0 has a touch kernel (opt_touch 2: A/B)
     bool ride = false;
-    const uint64_t per = phase_plan(a, nontemporal, max_blocks, args.stage != nullptr && a.rows, &ride);
+    const uint64_t per = phase_plan(a, nontemporal, max_blocks, (args.stage != nullptr || args.resident != nullptr) && a.rows, &ride);
     if (per == 0) return launch_stitch_range(a, stream, nontemporal, max_blocks);
     const bool no_touch = (a.opt_touch & 1u) != 0;
     // (V2P_PHASE_ONE_LAUNCH, A/B: ONE launch for all phases, the read-ahead workgroups of phase g + 1 placed in the grid before the
@@ -1373,7 +1391,12 @@ hipError_t launch_stitch(const StitchArgs& args, hipStream_t stream, int nontemp
         return err != hipSuccess ? err : hipGetLastError();
     }
     // STAGED descriptors: the ride form of a rows image with the caller's two buffers (stitch_kernels.h)
-    const bool staged = ride && a.rows && wsel == 0 && args.stage != nullptr && per <= args.stage_chunks;
+    // RESIDENT rows (an image executed again): one buffer for the whole table, row = global chunk index -- no parity, no cap on the phase,
+    // and the read-ahead (phase 0's kernel, the trailing workgroups) only reads
+    // (KEEP IN STEP with v2p_api.hip's rows_wanted(), which tells v2p_batch_image_form whether this branch will be taken: ride, a rows image,
+    // wsel == 0, phases, not one launch, not dual; launch_stitch_wave then takes the STG instance only for a whole phase in one launch)
+    const bool resident = ride && a.rows && wsel == 0 && args.resident != nullptr;
+    const bool staged = !resident && ride && a.rows && wsel == 0 && args.stage != nullptr && per <= args.stage_chunks;
     uint32_t phase = 0;
     for (uint64_t c0 = 0; c0 < args.n_chunks; c0 += per, ++phase) {
         const uint32_t nc = uint32_t(args.n_chunks - c0 < per ? args.n_chunks - c0 : per);
@@ -1384,13 +1407,16 @@ hipError_t launch_stitch(const StitchArgs& args, hipStream_t stream, int nontemp
             a.next_chunks = args.chunks + c0 + per;
             a.n_next = uint32_t(args.n_chunks - (c0 + per) < per ? args.n_chunks - (c0 + per) : per);
         }
-        a.stage_cur = nullptr; a.stage_next = nullptr;
-        if (staged) {
+        a.stage_cur = nullptr; a.stage_next = nullptr; a.rows_next = nullptr;
+        if (resident) {
+            a.stage_cur = args.resident + c0 * STAGE_SLOTS;
+            if (a.next_chunks) a.rows_next = args.resident + (c0 + per) * STAGE_SLOTS;
+        } else if (staged) {
             a.stage_cur = args.stage + uint64_t(phase & 1u) * args.stage_chunks * STAGE_SLOTS;
             a.stage_next = args.stage + uint64_t((phase + 1u) & 1u) * args.stage_chunks * STAGE_SLOTS;
         }
         if (!no_touch && (!ride || c0 == 0)) hipLaunchKernelGGL(touch_image_kernel, dim3(8u * ((touch_waves_per_xcd(nc) + 3u) / 4u)), dim3(256), 0, stream, a.desc, a.chunks, nc, a.n_desc, a.src1, a.src1_len,
-                                                                 staged ? const_cast<uint64_t*>(a.stage_cur) : nullptr);
+                                                                 staged ? const_cast<uint64_t*>(a.stage_cur) : nullptr, resident ? a.stage_cur : nullptr);
         err = launch_stitch_range(a, stream, nontemporal, 0);
         if (err != hipSuccess) return err;
 #ifdef V2P_BENCH_VARIANTS

@@ -116,6 +116,8 @@ __device__ __forceinline__ u32x4 wmerge(u32x4 v, u32x4 ld, u32x4 m)      // byte
 // STG (rows images launched in phases, the ride form): the chunk's descriptors are read from row c of a STAGING buffer that the read-ahead
 // of this phase filled (touch_chunks: 64 slots per chunk, in launch order) -- an address the wave knows before its chunk record has
 // arrived, so record and descriptors are requested together -- and the trailing workgroups fill the other buffer for the next phase.
+// An image that is executed AGAIN has RESIDENT rows (launch_stitch): row c of one buffer for the whole chunk table, filled once; p_stage is
+// then the phase's first row, and the trailing workgroups only read the next phase's rows (p_rows_next), records and payload lines.
 template <int WPG, bool NT, bool SC1 = false, bool RIMG = false, bool STG = false>
 __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const uint64_t* __restrict__ p_desc, const Chunk* __restrict__ p_chunks,
                                                             const uint8_t* __restrict__ p_src0, const uint8_t* __restrict__ p_src1,
@@ -123,7 +125,8 @@ __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const u
                                                             const uint8_t* __restrict__ p_dots,
                                                             uint32_t n_chunks, uint64_t n_desc, uint64_t src0_len, uint64_t src1_len, uint64_t out_len,
                                                             const Chunk* __restrict__ p_next, uint32_t n_next, uint32_t phase_chunks,
-                                                            const uint64_t* __restrict__ p_stage = nullptr, uint64_t* __restrict__ p_stage_next = nullptr)
+                                                            const uint64_t* __restrict__ p_stage = nullptr, uint64_t* __restrict__ p_stage_next = nullptr,
+                                                            const uint64_t* __restrict__ p_rows_next = nullptr)
 {
     static_assert(!STG || (RIMG && WPG == 1), "staged descriptors: rows images, one wave per workgroup");
     constexpr uint32_t ROWS = CHUNK_BYTES_WAVE / 1024u;              // 1 KiB rows of a chunk: all gathered before the first store
@@ -162,9 +165,14 @@ __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const u
         // records, descriptors and payload lines into the caches (launch_stitch: phases) -- the read-ahead costs no launch of its own
         // (they start at a workgroup index that is a multiple of 8: workgroup b is on XCD b % 8 and reads chunks of that residue)
         const uint32_t first_wg = (((n_chunks + uint32_t(WPG) - 1u) / uint32_t(WPG)) + 7u) & ~7u;
-        if (blockIdx.x >= first_wg)
-            touch_chunks(p_desc, p_next, touch_wave_first(blockIdx.x & 7u, ((blockIdx.x - first_wg) >> 3) * uint32_t(WPG) + wid), n_next, n_desc, p_src1, src1_len, lane,
-                         STG ? p_stage_next : nullptr);
+        if (blockIdx.x >= first_wg) {
+            // (resident rows are read ahead LAST CHUNK FIRST: what the next launch needs first is read last -- in launch order they were no
+            // faster than rows staged per phase, C3 whole 7.6 against 7.2 ms: profiles/resident_rows_ab.json)
+            uint32_t q = ((blockIdx.x - first_wg) >> 3) * uint32_t(WPG) + wid;
+            if (STG && p_rows_next) { const uint32_t tq = touch_waves_per_xcd(n_next); q = q < tq ? tq - 1u - q : q; }
+            touch_chunks(p_desc, p_next, touch_wave_first(blockIdx.x & 7u, q), n_next, n_desc, p_src1, src1_len, lane,
+                         STG ? p_stage_next : nullptr, STG ? p_rows_next : nullptr);
+        }
         return;
     }
     WaveLds& L = s_all[wid];
@@ -450,7 +458,7 @@ hipError_t launch_stitch_wave(const StitchArgs& a, hipStream_t stream, bool nt, 
 #define V2P_LWR(NTT, SCC) hipLaunchKernelGGL((stitchw_kernel<1, NTT, SCC, true>), dim3(tw ? (((nc + 7u) & ~7u) + 8u * tw) : nc), dim3(64), 0, stream, \
         a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, nullptr, nullptr)
 #define V2P_LWS(NTT, SCC) hipLaunchKernelGGL((stitchw_kernel<1, NTT, SCC, true, true>), dim3(tw ? (((nc + 7u) & ~7u) + 8u * tw) : nc), dim3(64), 0, stream, \
-        a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, a.stage_cur, a.stage_next)
+        a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, a.stage_cur, a.stage_next, a.rows_next)
         if (a.rows && a.stage_cur && c0 == 0u && nc == a.n_chunks) {      // (staged descriptors: the whole phase is one launch, row c of the buffer = chunk c)
             if (nt && a.store_sc1) V2P_LWS(true, true); else if (nt) V2P_LWS(true, false); else V2P_LWS(false, false);
         } else if (a.rows) { if (nt && a.store_sc1) V2P_LWR(true, true); else if (nt) V2P_LWR(true, false); else V2P_LWR(false, false); }

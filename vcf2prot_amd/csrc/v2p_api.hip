@@ -188,7 +188,12 @@ struct v2p_batch {
     uint64_t n_pieces = 0;
     int pieces_state = 0;          // 0: not tried; 1: built (d_pieces / d_chunks2 describe the batch's image); -1: the image is not converted (kept on the dense kernel)
     PinnedBuf h_sum;               // the one call: the 64 bytes the host reads per slice (counts, flags, status)
-    DevBuf d_stage;                // STAGED descriptors (stitch_kernels.h): two buffers of a phase's chunks x 64 slots, filled by the read-ahead
+    DevBuf d_stage;                // STAGED descriptors (stitch_kernels.h): two buffers of a phase's chunks x 64 slots, filled by the read-ahead of every
+                                   // phase -- an image's first execute, sliced launches, and re-executes of a batch that has no resident rows (below)
+    DevBuf d_rows;                 // RESIDENT rows (stitch_kernels.h): 64 slots for every chunk of the whole table, filled ONCE at the first re-execute
+    int rows_state = 0;            // 1: ... and describing the batch's image; -1: no room for them (not asked for again at every step); 0: not tried -- set
+                                   // wherever the image can change (reset, every builder).  d_rows is only ensured when the rows are built: under
+                                   // V2P_DEBUG_POISON DevBuf refills a buffer at every such call
     // a PADDED wave image (sir_pack.hpp; what the one call leaves behind): d_desc holds ROWS_TILE_SLOTS slots per tile, the chunk records
     // address its slots; desc_slots = its size (the kernels' bound), n_desc the descriptors it holds; pad_tdbase = the scan of the tiles'
     // counts (in d_tiles), with which a download hands out the dense form
@@ -1044,7 +1049,7 @@ void v2p_batch_destroy(v2p_batch* b)
     }
     b->d_desc.release(); b->d_chunks.release(); b->d_payload.release(); b->d_out.release();
     b->d_hap.release(); b->d_digest.release(); b->d_status.release(); b->d_build.release();
-    b->d_tiles.release(); b->d_cover.release(); b->d_pad.release(); b->d_order.release(); b->d_patch.release(); b->d_stage.release(); b->d_pieces.release(); b->d_chunks2.release(); b->h_sum.release();
+    b->d_tiles.release(); b->d_cover.release(); b->d_pad.release(); b->d_order.release(); b->d_patch.release(); b->d_stage.release(); b->d_rows.release(); b->rows_state = 0; b->d_pieces.release(); b->d_chunks2.release(); b->h_sum.release();
     b->d_zws.release(); b->d_z.release(); b->d_zbegin.release();
     for (hipEvent_t e : b->ev_os) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : b->ev_aux) if (e) (void)hipEventDestroy(e);
@@ -1620,7 +1625,7 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
     b->n_desc = n_desc; b->n_chunks = n_chunks; b->n_payload = v.n_alt; b->payload_dev = v.alt; b->out_bytes = out_bytes; b->n_haps = n_h;
     b->launch_hint = (mode == ROWS_DENSE ? 2 : 4) | 8 | 16 | 32 | (1 << 6) | (1 << 8);
     b->uses_proteome = true;
-    b->finalized = true;
+    b->rows_state = 0; b->finalized = true;
     b->n_slices = 0;
     return V2P_OK;
 }
@@ -1878,7 +1883,7 @@ int v2p_batch_build_on_device(v2p_batch* b, const v2p_txstream* s, uint32_t wind
     const int tpt = meta[3] <= 256u ? 1 : (meta[3] <= 512u ? 2 : 4);
     b->launch_hint = ((meta[0] & 2u) ? 2 : 0) | ((meta[0] & 4u) ? 4 : 0) | ((meta[0] & 1u) ? 0 : 16) | (meta[2] ? 0 : 32) | ((meta[1] ? 2 : 1) << 6) | (tpt << 8);
     b->uses_proteome = true;
-    b->finalized = true;
+    b->rows_state = 0; b->finalized = true;
     return V2P_OK;
 #endif   // V2P_BENCH_VARIANTS: the grid builders
 }
@@ -1990,7 +1995,7 @@ static int build_patch_image(v2p_batch* b, const DevStreamView& v, float* build_
     b->n_chunks = n_chunks; b->n_payload = v.n_alt; b->payload_dev = v.alt; b->out_bytes = out_bytes; b->n_haps = n_h;
     b->launch_hint = 0; b->is_patch = true;
     b->uses_proteome = true;
-    b->finalized = true;
+    b->rows_state = 0; b->finalized = true;
     b->n_slices = 0;
     return V2P_OK;
 }
@@ -2258,6 +2263,7 @@ static int batch_reset_locked(v2p_batch* b, bool wait)
     b->payload_dev = nullptr; b->n_slices = 0; b->launch_hint = 0; b->is_patch = false; b->patch_segs = b->patch_patches = 0;
     b->is_tiles = false; b->tile_slots = 0; b->tiles_n = 0; b->tiles_count = nullptr; b->tiles_res_base = nullptr;
     b->pad_image = false; b->desc_slots = 0; b->pad_tdbase = nullptr; b->pieces_state = 0; b->executed = false;
+    b->rows_state = 0;                              // (the resident rows are the image's that is gone)
     b->z_ready = false; b->z_begin.clear();
     b->os_kernel = 0; b->os_build_ms = 0.f; b->os_wall_ms = 0.0; b->os_ahead = false;      // (v2p_batch_oneshot_info: no call to report on)
     stream_detach(b); b->orphaned = false;
@@ -2334,6 +2340,28 @@ static hipError_t ensure_event(hipEvent_t& e) { return e ? hipSuccess : hipEvent
 // Staging buffers for an image launch_stitch() will run in the form that stages (a pure wave rows image in phases): sized by the
 // launcher's own rule.  libv2p_bench.so's variant 23 (A/B): no staging -- the stitch waves read descriptors where the image has them;
 // 25: dense rows images are staged as well.
+//
+// RE-EXECUTION (v2p_batch_execute on a batch that has been executed): a dense image that would be staged per phase runs from RESIDENT rows
+// instead (attach_rows) -- the image and its chunk order do not change between two executes, so row c of a staging buffer would hold the
+// same 512 bytes every step.  The whole chunk table is staged once into d_rows, row = global chunk index; from then on a step's read-ahead
+// writes nothing and never reads the image's own descriptor array, and it reads a phase's rows LAST CHUNK FIRST, so that the rows the next
+// launch needs first are the ones read last (read ahead in launch order the rows were no faster than staging, 7.5-7.6 ms, and fell off
+// from 40 MB phases on like descriptors read in place).  C3 whole: 7.45 -> 7.18 ms per execute in one process, bench.py 7.41 -> 7.18;
+// WRITE_SIZE per step falls by the 1.93 GB of staging writes to the result's bytes, FETCH_SIZE does not fall -- the rows still come
+// through the L2s twice (profiles/resident_rows_ab.json).  Sliced launches (stitch_range) and the first execute keep this
+// function.  A rich image that reads a LARGE reference (C4 whole) is read in place at its first execute and gets resident rows as well.
+// libv2p_bench.so's variant 30 (A/B): never resident; 31: resident rows for every dense wave image that is launched in phases.
+
+// a dense image whose descriptors are worth staging: rich, and at least eight phases of the phase size in force -- per phase only while
+// the reference is small (small_ref); resident rows pay for a large reference too (C4 whole, 56 MB: 6.30 -> 6.09 ms at its 28 MB phases --
+// the one point this rule extrapolates from: nothing was measured between 8 MB and 56 MB of reference, or above)
+static bool stage_rich(const StitchArgs& a, bool small_ref)
+{
+    const uint64_t idesc = a.img_desc ? a.img_desc : a.n_desc, ibytes = a.img_bytes ? a.img_bytes : a.out_len;
+    const uint64_t phase = a.opt_phase_bytes != 0 && a.opt_phase_bytes != ~0ull ? a.opt_phase_bytes : PHASE_BYTES_RICH;
+    return image_is_rich(idesc, ibytes) && (!small_ref || a.src0_len <= PHASE_STAGED_SMALL_REF) && 8u * idesc + 16u * uint64_t(a.n_chunks) >= 8u * phase;
+}
+
 static hipError_t attach_stage(v2p_batch* b, StitchArgs& a, int hint)
 {
     // A padded image is staged; so is a dense one that is rich and reads a small reference (the north star's cohort): at the 28 MB phases
@@ -2341,10 +2369,10 @@ static hipError_t attach_stage(v2p_batch* b, StitchArgs& a, int hint)
     // phases -- a third fewer launches, tails and read-ahead hand-overs: C3 whole 7.42 -> 7.23 ms per execute; read in place the image
     // falls off a cliff there (7.3 ... 7.8 ms at 40-48 MB by run).  C4 whole (56 MB of reference) and C2 (thin: half-filled staging rows)
     // gain nothing from either and are read in place (tools/stage_probe.py, profiles/r05_staged_steady_state.json).
-    const uint64_t idesc = a.img_desc ? a.img_desc : a.n_desc, ibytes = a.img_bytes ? a.img_bytes : a.out_len;
     // (... and large: what staging buys is FEWER phases; an image of three phases gains nothing from being one of two and pays the copy --
-    // the routing sweep's 1.5 GB images ran 1-3 % slower staged, profiles/r05_routing_sweep.json)
-    const bool small_rich = image_is_rich(idesc, ibytes) && a.src0_len <= PHASE_STAGED_SMALL_REF && 8u * idesc + 16u * uint64_t(a.n_chunks) >= 8u * PHASE_BYTES_RICH;
+    // the routing sweep's 1.5 GB images ran 1-3 % slower staged, profiles/r05_routing_sweep.json.  Eight phases of the size in force:
+    // v2p_set_launch_opts' phase_bytes where one is set -- tests reach the form with images of a megabyte)
+    const bool small_rich = stage_rich(a, true);
     if (ctx_variant(b->ctx) == 23u || !(b->pad_image || ctx_variant(b->ctx) == 25u || small_rich)) return hipSuccess;
     const uint32_t rows = stitch_stage_chunks(a, hint);
     if (rows == 0) return hipSuccess;
@@ -2352,6 +2380,38 @@ static hipError_t attach_stage(v2p_batch* b, StitchArgs& a, int hint)
     if (e != hipSuccess) { (void)hipGetLastError(); return hipSuccess; }       // (no room: launched without)
     a.stage = reinterpret_cast<uint64_t*>(b->d_stage.ptr()); a.stage_chunks = rows;
     return hipSuccess;
+}
+
+// would a whole-table execute of this (finalized, executed) batch run from resident rows?  Rich dense images of at least eight phases
+// (libv2p_bench.so's variant 31: every dense rows image), launched in the form that stages (stitch_stage_chunks: phases, the ride form --
+// not one launch, not dual, not "no phases").  KEEP IN STEP with launch_stitch (stitch_kernels.hip: `resident`) and launch_stitch_wave's
+// choice of the STG instance: this is the host's mirror of their conditions, and v2p_batch_image_form reports it -- it does not observe the launch.
+static bool rows_wanted(const v2p_batch* b, const StitchArgs& a, int hint)
+{
+    const uint32_t var = ctx_variant(b->ctx);
+    if (var == 23u || var == 30u || b->pad_image || b->is_tiles || b->is_patch) return false;
+    return (stage_rich(a, false) || var == 31u) && stitch_stage_chunks(a, hint) != 0;
+}
+
+// Resident rows for a re-execute (see attach_stage): built here when the batch has none for its image; true: `a` carries them.  No room
+// for the buffer: false, and the caller goes on as before (staged per phase, or read in place).
+static bool attach_rows(v2p_batch* b, StitchArgs& a, int hint, hipError_t* err)
+{
+    *err = hipSuccess;
+    if (!rows_wanted(b, a, hint) || b->rows_state < 0) return false;
+    if (b->rows_state == 0) {
+        // (row c = chunk c of the whole table, rounded up to 8 rows; DevBuf: 256 readable bytes in front, PAD_BYTES behind the last slot --
+        // an immediate record's 16-byte blocks around its own slot stay inside the allocation)
+        const uint64_t n_rows = (b->n_chunks + 7u) & ~7ull;
+        // (sized once per image and never growing: no slack)
+        if (b->d_rows.ensure_exact(n_rows * uint64_t(CHUNK_TASKS_WAVE) * 8u) != hipSuccess) { (void)hipGetLastError(); b->rows_state = -1; return false; }
+        *err = launch_stage_rows(a, reinterpret_cast<uint64_t*>(b->d_rows.ptr()), b->ctx->stream);
+        if (*err == hipSuccess) *err = hipStreamSynchronize(b->ctx->stream);      // (once per image, like to_pieces: the rows are whole before anything reads them on any stream)
+        if (*err != hipSuccess) return false;
+        b->rows_state = 1;
+    }
+    a.resident = reinterpret_cast<const uint64_t*>(b->d_rows.ptr());
+    return true;
 }
 
 // One slice's share of launch_stitch's routing (phases, store policy) follows the slice, not the table it is a range of
@@ -2620,7 +2680,7 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
     b->n_desc = desc0; b->n_chunks = chunk0; b->n_slices = S;
     b->img.hap_out_begin = st->hap_out_begin;
     b->uses_proteome = true;
-    b->finalized = true;
+    b->rows_state = 0; b->finalized = true;
     return V2P_OK;
 }
 
@@ -2743,7 +2803,7 @@ static int build_tiles(v2p_batch* b, const v2p_stream* st, bool execute, bool* f
     b->pieces_src0_len = c->proteome_len + c->headers_len; b->pieces_src1_len = v.n_alt;
     b->launch_hint = 0; b->pad_image = false; b->desc_slots = 0;
     b->img.hap_out_begin = st->hap_out_begin;
-    b->uses_proteome = true; b->finalized = true;
+    b->uses_proteome = true; b->rows_state = 0; b->finalized = true;
     b->n_slices = 1; b->slice_chunk0[0] = 0; b->slice_chunk0[1] = n_tiles; b->os_ahead = false;
     if (execute && !executed_in_slices) HIP_TRY(c, tiles_execute(b, A), "launch(stitch: tile image)");
     HIP_TRY(c, hipEventRecord(b->ev_os[1], A), "hipEventRecord");
@@ -2932,6 +2992,7 @@ int v2p_batch_set_packed(v2p_batch* b,
         if (rc) return rc;
     }
     b->img = ImageBuilder();
+    b->rows_state = 0;
     b->img.desc.assign(desc, desc + n_desc);
     b->img.chunks.resize(n_chunks);
     if (n_chunks) memcpy(b->img.chunks.data(), chunks, n_chunks * sizeof(Chunk));
@@ -2974,7 +3035,7 @@ int v2p_batch_finalize(v2p_batch* b)
     std::vector<uint64_t>().swap(b->img.desc);
     std::vector<Chunk>().swap(b->img.chunks);
     std::vector<uint8_t>().swap(b->img.payload);
-    b->finalized = true;
+    b->rows_state = 0; b->finalized = true;
     return V2P_OK;
 }
 
@@ -3022,6 +3083,19 @@ static int to_pieces(v2p_batch* b)
     return V2P_OK;
 }
 
+// the launcher's arguments for the batch's whole chunk table under the context's launch options (v2p_batch_execute; v2p_batch_image_form asks the same rules)
+static StitchArgs whole_table_args(const v2p_batch* b)
+{
+    const v2p_ctx* c = b->ctx;
+    StitchArgs a{reinterpret_cast<const uint64_t*>(b->d_desc.ptr()), b->pad_image ? b->desc_slots : b->n_desc, reinterpret_cast<const Chunk*>(b->d_chunks.ptr()),
+                 uint32_t(b->n_chunks), c->proteome.ptr(), c->proteome_len + c->headers_len, b->payload_dev, b->n_payload,
+                 b->d_out.ptr(), b->out_bytes, reinterpret_cast<unsigned long long*>(b->d_status.ptr())};
+    a.opt_phase_bytes = c->launch_opts.phase_bytes; a.opt_phase_min_chunks = c->launch_opts.phase_min_chunks; a.opt_store_sc1 = c->launch_opts.store_sc1;
+    a.opt_touch = touch_of(ctx_variant(c));
+    a.img_desc = b->pad_image ? b->n_desc : 0;          // (the routing looks at the descriptors the image holds, not at the array's slots)
+    return a;
+}
+
 int v2p_batch_execute(v2p_batch* b)
 {
     if (!b) return V2P_ERR_INVALID_ARG;
@@ -3058,15 +3132,16 @@ int v2p_batch_execute(v2p_batch* b)
             return V2P_OK;
         }
     }
-    StitchArgs a{reinterpret_cast<const uint64_t*>(b->d_desc.ptr()), b->pad_image ? b->desc_slots : b->n_desc, reinterpret_cast<const Chunk*>(b->d_chunks.ptr()),
-                 uint32_t(b->n_chunks), c->proteome.ptr(), c->proteome_len + c->headers_len, b->payload_dev, b->n_payload,
-                 b->d_out.ptr(), b->out_bytes, reinterpret_cast<unsigned long long*>(b->d_status.ptr())};
-    a.opt_phase_bytes = c->launch_opts.phase_bytes; a.opt_phase_min_chunks = c->launch_opts.phase_min_chunks; a.opt_store_sc1 = c->launch_opts.store_sc1;
-    a.opt_touch = touch_of(ctx_variant(c));
-    a.img_desc = b->pad_image ? b->n_desc : 0;          // (the routing looks at the descriptors the image holds, not at the array's slots)
+    StitchArgs a = whole_table_args(b);
     dual_of(c, a);
     const int hint = int(!(c->flags & V2P_FLAG_TEMPORAL)) | b->launch_hint;
-    (void)attach_stage(b, a, hint);
+    bool resident = false;
+    if (b->executed) {                                  // (a re-execute: the same image again, its rows staged once)
+        hipError_t re = hipSuccess;
+        resident = attach_rows(b, a, hint, &re);
+        HIP_TRY(c, re, "launch(resident rows)");
+    }
+    if (!resident) (void)attach_stage(b, a, hint);
     HIP_TRY(c, launch_stitch(a, c->stream, hint, 0), "launch(stitch)");
     b->executed = true;
     return V2P_OK;
@@ -3102,7 +3177,14 @@ int v2p_batch_image_form(const v2p_batch* b)
 {
     if (!b) return V2P_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(b->ctx->mu);
-    return (b->pad_image ? 1 : 0) | (b->pieces_state == 1 ? 2 : 0) | (b->d_stage.ptr() ? 4 : 0) | (b->is_tiles ? 8 : 0);
+    // (16: the next v2p_batch_execute runs from the resident rows the batch holds -- under the launch options in force now)
+    bool resident = false;
+    if (b->finalized && b->executed && b->rows_state == 1 && b->d_rows.ptr()) {
+        StitchArgs a = whole_table_args(b);
+        a.opt_dual = ctx_variant(b->ctx) == 19u ? 1u : 0u;
+        resident = rows_wanted(b, a, int(!(b->ctx->flags & V2P_FLAG_TEMPORAL)) | b->launch_hint);
+    }
+    return (b->pad_image ? 1 : 0) | (b->pieces_state == 1 ? 2 : 0) | (b->d_stage.ptr() ? 4 : 0) | (b->is_tiles ? 8 : 0) | (resident ? 16 : 0);
 }
 
 int v2p_batch_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len)
@@ -3712,7 +3794,7 @@ int v2p_set_launch_opts(v2p_ctx* c, const v2p_launch_opts* opts)
 }
 
 #ifdef V2P_BENCH_VARIANTS
-// libv2p_bench.so only (csrc/bench/v2p_bench.h): the A/B switches 16 .. 29 of the builders and launchers
+// libv2p_bench.so only (csrc/bench/v2p_bench.h): the A/B switches 16 .. 31 of the builders and launchers
 int v2p_bench_set_variant(v2p_ctx* c, uint32_t variant)
 {
     if (!c) return V2P_ERR_INVALID_ARG;

@@ -109,7 +109,7 @@ class Context:
     def set_launch_opts(self, phase_bytes: int = 0, phase_min_chunks: int = 0, store_sc1: int = -1, variant: int = 0):
         """Phase size / phase threshold / store policy of every batch this context executes from now on (A/B runs, tests); no arguments:
         the library's defaults (v2p_set_launch_opts).  variant (development contexts only: v2p_bench_set_variant, csrc/bench/v2p_bench.h):
-        16 / 17 / 18 one launch for all phases / the read-ahead as kernels of its own / no read-ahead, 20 .. 29 the builders' switches."""
+        16 / 17 / 18 one launch for all phases / the read-ahead as kernels of its own / no read-ahead, 20 .. 29 the builders' switches, 30 / 31 resident descriptor rows for an image that is executed again."""
         o = N.LaunchOpts(1, 0, phase_bytes, phase_min_chunks, store_sc1, 0, 0)
         self._check(self._lib.v2p_set_launch_opts(self._h, ctypes.byref(o)))
         if variant or self.development:
@@ -412,7 +412,7 @@ class Batch:
         f = self._lib.v2p_batch_image_form(self._h)
         if f < 0:
             self.ctx._check(f)
-        return {"padded": bool(f & 1), "pieces": bool(f & 2), "staging_buffers": bool(f & 4), "tiles": bool(f & 8)}
+        return {"padded": bool(f & 1), "pieces": bool(f & 2), "staging_buffers": bool(f & 4), "tiles": bool(f & 8), "resident_rows": bool(f & 16)}
 
     def oneshot_info(self) -> dict:
         info = N.OneShotInfo()
