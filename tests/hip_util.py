@@ -120,3 +120,46 @@ def decode_launch(text: bytes, row_begin, row_end, n_samples: int, csq_begin, cs
     guards = all(bool((x == 0xA5).all()) for x in (got[:hb_at], got[hb_at + 8 * (n_haps + 1):ids_at], got[ids_at + 4 * ids_capacity:st_at],
                                                    got[st_at + 16:], work[ws:]))
     return status, hap_begin, ids, guards
+
+
+def stitch_launch(desc, chunks, src0, src1, out_len, opts=None, guard=4096):
+    """v2p_stitch_launch_opts (include/vcf2prot_hip.h) of the product library on device buffers of the HIP runtime, as its contract words
+    them: both sources with exactly PAD_BYTES (32) of 0xEE either side (leaked padding is never a letter), the descriptor array with exactly
+    16 bytes before and 32 behind it that look like descriptors (a copy from far outside the proteome), the arena 16-byte aligned, `out_len`
+    bytes of 0x5A between two guard regions of 0xA5, the status word all ones between guards.  The routing bits come from
+    v2p_stitch_launch_bits; `opts`: nontemporal, store_sc1, phase_bytes, phase_min_chunks.
+    Returns (arena [out_len], status word, every guard untouched)."""
+    from vcf2prot_amd import _native as N
+    lib = N.hip_lib()
+    desc = np.ascontiguousarray(desc, np.uint64)
+    chunks = np.ascontiguousarray(chunks, np.uint64).reshape(-1, 2)
+    poison = np.uint64((1 << 36) | (1000 << 40))
+    d_host = np.concatenate([np.full(2, poison, np.uint64), desc, np.full(4, poison, np.uint64)])
+    d_desc, d_chunks = DevBuf.of(d_host), DevBuf.of(chunks)
+    srcs = []
+    for s in (src0, src1):
+        h = np.full(32 + len(s) + 32, 0xEE, np.uint8)
+        h[32:32 + len(s)] = s
+        srcs.append(DevBuf.of(h))
+    tail = (-out_len) % 16                                            # (the rear guard begins at the arena's last byte, whatever out_len & 15)
+    a_host = np.full(guard + out_len + guard + tail, 0xA5, np.uint8)
+    a_host[guard:guard + out_len] = 0x5A
+    d_out = DevBuf.of(a_host, pad=256)
+    assert (d_out.ptr + guard) % 16 == 0
+    s_host = np.full(guard + 8 + guard, 0xA5, np.uint8)
+    s_host[guard:guard + 8] = 0xFF
+    d_status = DevBuf.of(s_host, pad=256)
+    bits = int(lib.v2p_stitch_launch_bits(chunks.ctypes.data, chunks.shape[0]))
+    o = N.LaunchOpts(routing=bits, **(opts or {}))
+    rc = N.stitch_launch(lib, None, d_desc.ptr + 16, desc.size, d_chunks.ptr, chunks.shape[0], srcs[0].ptr + 32, len(src0), srcs[1].ptr + 32, len(src1),
+                         d_out.ptr + guard, out_len, d_status.ptr + guard, o)
+    sync = hip().hipDeviceSynchronize()
+    if sync != 0:                                                     # a fault: nothing more goes to this GPU from this process
+        import pytest
+        pytest.exit(f"v2p_stitch_launch_opts left HIP error {sync} behind", returncode=3)
+    got, st = d_out.download(), d_status.download()
+    for b in (d_desc, d_chunks, d_out, d_status, *srcs):
+        b.free()
+    assert rc == 0, rc
+    guards = bool((got[:guard] == 0xA5).all() and (got[guard + out_len:] == 0xA5).all() and (st[:guard] == 0xA5).all() and (st[guard + 8:] == 0xA5).all())
+    return got[guard:guard + out_len].copy(), int(st[guard:guard + 8].view(np.uint64)[0]), guards

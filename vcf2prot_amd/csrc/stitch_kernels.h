@@ -7,6 +7,9 @@
 namespace v2p {
 
 // device status word: min over offending rows of (row << 8 | reason); ~0ull = clean
+// (the four stitch kernels alike: a chunk with a descriptor that is reported -- STATUS_SRC_OOB at that descriptor -- is not executed,
+// nothing of it is written, and it is not reported a second time as a chunk; a chunk that breaks a limit of its kernel or leaves the
+// arena is STATUS_RES_OOB at its first descriptor.  Pinned by tests/test_gpu_stitch_rule.py)
 enum : uint32_t {
     STATUS_BAD_CODE = 1,        // exe_code not in {0,1}
     STATUS_RES_OOB = 2,         // result range outside the result tape / arena

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint64_t* __restrict_
         // ---- A: TPT consecutive descriptors per lane ----
         uint64_t adj[TPT];
         uint32_t len[TPT];
-        uint32_t lsum = 0, lnz = 0;
+        uint32_t lsum = 0, lnz = 0, lbad = 0;                   // (lbad: the lane reported a descriptor -- the chunk is not executed)
 #pragma unroll
         for (int k = 0; k < TPT; ++k) {
             adj[k] = dots16;
@@ -177,12 +177,13 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint64_t* __restrict_
                 const uint32_t space = uint32_t(d >> 62);
                 const uint64_t src = d & ((1ull << 40) - 1);
                 if (space == SPACE_IMM) {
-                    if (len[k] > IMM_MAX_BYTES) report(a.status, tb + i, STATUS_SRC_OOB);
+                    if (len[k] > IMM_MAX_BYTES) { report(a.status, tb + i, STATUS_SRC_OOB); lbad = 1u; }
                     else adj[k] = ADJ_IMM | src;
                 } else {
                     const uint64_t limit = space == SPACE_PROTEOME ? a.src0_len : (space == SPACE_PAYLOAD ? a.src1_len : ~0ull);
                     if (src + len[k] > limit) {                  // never read out of bounds: task.rs would panic
                         report(a.status, tb + i, STATUS_SRC_OOB);
+                        lbad = 1u;
                     } else if (space != SPACE_FILL) {
                         adj[k] = reinterpret_cast<uint64_t>(space == SPACE_PROTEOME ? a.src0 : a.src1) + src;
                     }
@@ -195,7 +196,8 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint64_t* __restrict_
         for (int q = 0; q < 8; ++q) s_map32[8u * tid + q] = 0u;
         if (DBG == 20) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st1 = __builtin_amdgcn_s_memtime(); }
         const uint32_t incl = wave_incl_scan(lsum);
-        const uint32_t nzincl = wave_incl_scan(lnz);
+        const uint32_t lnzb = lnz | (lbad << 16);             // (one scan for both: at most 1024 non-empty tasks, at most 1024 reported ones)
+        const uint32_t nzincl = wave_incl_scan(lnzb);
         if (lane == 63u) { s_w[0][wid] = incl; s_w[1][wid] = nzincl; }
         lds_barrier();
 
@@ -203,11 +205,12 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint64_t* __restrict_
         const uint32_t l0 = s_w[0][0], l1 = s_w[0][1], l2 = s_w[0][2], l3 = s_w[0][3];
         const uint32_t z0 = s_w[1][0], z1 = s_w[1][1], z2 = s_w[1][2], z3 = s_w[1][3];
         const uint32_t total = l0 + l1 + l2 + l3;
-        const uint32_t nz = z0 + z1 + z2 + z3;
+        const uint32_t nz = (z0 + z1 + z2 + z3) & 0xFFFFu;
+        const bool chunk_bad = ((z0 + z1 + z2 + z3) >> 16) != 0u;       // a descriptor of the chunk was reported: nothing of the chunk is written
         uint32_t excl = incl - lsum + (wid > 0 ? l0 : 0u) + (wid > 1 ? l1 : 0u) + (wid > 2 ? l2 : 0u);
-        uint32_t rank = nzincl - lnz + (wid > 0 ? z0 : 0u) + (wid > 1 ? z1 : 0u) + (wid > 2 ? z2 : 0u);
+        uint32_t rank = (nzincl - lnzb + (wid > 0 ? z0 : 0u) + (wid > 1 ? z1 : 0u) + (wid > 2 ? z2 : 0u)) & 0xFFFFu;
         const uint32_t nblk = total ? (head + total + 15u) >> 4 : 0u;
-        const bool chunk_ok = hdr_ok && dst + total <= a.out_len && nblk <= 4096u && total <= DOTS_BYTES - 96u;
+        const bool chunk_ok = hdr_ok && !chunk_bad && dst + total <= a.out_len && nblk <= 4096u && total <= DOTS_BYTES - 96u;
 #pragma unroll
         for (int k = 0; k < TPT; ++k) {
             if (len[k] != 0u) {
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint64_t* __restrict_
 
         if (DBG == 20) st2 = __builtin_amdgcn_s_memtime();
         if (!chunk_ok) {                                      // never write out of bounds
-            if (tid == 0) report(a.status, tb, STATUS_RES_OOB);
+            if (tid == 0 && !chunk_bad) report(a.status, tb, STATUS_RES_OOB);      // (the status names the offending descriptor, not the chunk, where there is one)
         } else {
             // ---- K2: wave `wid` takes the 64-block rows wid, wid+4, ... (a workgroup pass = 4 KiB of result) ----
             uint8_t* const out0 = a.out + (dst - head);
@@ -429,6 +432,7 @@ __global__ __launch_bounds__(256) void stitch_dense_kernel(const uint64_t* __res
     __shared__ __attribute__((aligned(16))) uint32_t s_img[DENSE_STAGE / 4u + 8u];
     __shared__ uint64_t s_piece[DENSE_PIECES];              // space:2 | source offset:40 | (bytes - 1) << 42 | image offset << 46
     __shared__ uint32_t s_w[2][4];
+    __shared__ uint32_t s_bad[4];                           // per wave: one of its descriptors was reported
     __shared__ u32x4 s_low[17];                             // s_low[j]: the low j bytes of a 16-byte block
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
@@ -472,6 +476,7 @@ __global__ __launch_bounds__(256) void stitch_dense_kernel(const uint64_t* __res
     uint32_t len[TPT];
     uint64_t sw[TPT];                                       // space << 40 | source offset (the literal of an immediate task)
     uint32_t patch[TPT];                                    // fused substitution: bytes before the literal | literal << 12 | 1 << 20 [| position of a second literal << 21 | 1 << 28]
+    bool lane_bad = false;
     auto load_tasks = [&](bool first_time) -> uint32_t {
         uint64_t d[TPT];
         uint32_t lsum = 0, bad = 0u;
@@ -524,6 +529,7 @@ __global__ __launch_bounds__(256) void stitch_dense_kernel(const uint64_t* __res
 #pragma unroll
         for (int k = 0; k < TPT; ++k) g[k] = (len[k] && DBG != 1) ? piece(sw[k]) : u32x4{uint32_t(sw[k]), 0u, 0u, 0u};
         if (bad && first_time) report(a.status, tb + tid * TPT + uint32_t(__builtin_ctz(bad)), STATUS_SRC_OOB);   // task.rs would panic
+        if (first_time) lane_bad = bad != 0u;
         return lsum;
     };
     const uint32_t lsum = load_tasks(true);
@@ -534,11 +540,13 @@ __global__ __launch_bounds__(256) void stitch_dense_kernel(const uint64_t* __res
         if (tid < 2u) *reinterpret_cast<u32x4*>(&s_img[DENSE_STAGE / 4u + tid * 4u]) = z;
     }
     const uint32_t incl = wave_incl_scan(lsum);
-    if (lane == 63u) s_w[0][wid] = incl;
+    const bool wave_bad = __ballot(lane_bad) != 0ull;
+    if (lane == 63u) { s_w[0][wid] = incl; s_bad[wid] = wave_bad ? 1u : 0u; }
     lds_barrier();
     const uint32_t l0 = s_w[0][0], l1 = s_w[0][1], l2 = s_w[0][2], l3 = s_w[0][3];
     const uint32_t total = l0 + l1 + l2 + l3;
     const uint32_t excl = incl - lsum + (wid > 0 ? l0 : 0u) + (wid > 1 ? l1 : 0u) + (wid > 2 ? l2 : 0u);
+    if ((s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) != 0u) return;      // a reported descriptor: the chunk is not executed (uniform)
     if (!(hdr_ok && dst + total <= a.out_len)) {            // never write out of bounds
         if (tid == 0) report(a.status, tb, STATUS_RES_OOB);
         return;
@@ -646,8 +654,10 @@ __global__ __launch_bounds__(256) void stitch_dense_kernel(const uint64_t* __res
             }
         }
     };
+    // a chunk flagged dense is one window in EVERY instance: beside plain chunks of more than 512 descriptors the whole table comes to
+    // the multi-window instance, and a flagged chunk over the limit is refused there as well (include/vcf2prot_hip.h), not executed
+    if ((ONE || fused) && span > DENSE_STAGE) { if (tid == 0) report(a.status, tb, STATUS_RES_OOB); return; }   // not a chunk of a dense image: refused, nothing written
     if (ONE) {
-        if (span > DENSE_STAGE) { if (tid == 0) report(a.status, tb, STATUS_RES_OOB); return; }   // not a chunk of a dense image: refused, nothing written
         window(0u);
         return;
     }
@@ -1005,7 +1015,7 @@ __global__ __launch_bounds__(256) void stitch4_kernel(const uint64_t* __restrict
         if (DBG == 20) q4 = __builtin_amdgcn_s_memtime();
 
         if (!chunk_ok) {                                      // never write out of bounds
-            if (tid == 0u) report(p_status, tb, STATUS_RES_OOB);
+            if (tid == 0u && !chunk_bad) report(p_status, tb, STATUS_RES_OOB);     // (the status names the offending descriptor, not the chunk, where there is one)
         } else if (DBG != 4) {
             // ---- bulk: per pass wave `wid` takes the 64-block rows wid, wid+4, ..., wid+28 of the pass's 32: R gathers, then R stores ----
             uint8_t* const out0 = p_out + (dst - head);                     // 16-byte aligned
