@@ -183,6 +183,8 @@ BENCH_API = {
     # what no routing rule of the product picks (V2P_BENCH_VARIANTS build of the engine)
     "v2p_batch_download_patch_image": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_bench_set_variant": (c_int, [c_void_p, c_uint32]),
+    # the front end's prefix sums on caller-owned memory (tests/test_gpu_scan.py)
+    "v2p_scan_launch": (c_int, [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p]),
 }
 _bench = None
 

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include "../stitch_kernels.h"
 #include "../stitch_device.hpp"
+#include "../device_scan.h"
+#include "../group_tasks.h"
 #include "v2p_bench.h"
 
 namespace v2p {
@@ -359,6 +361,16 @@ int v2p_copy_mix_launch(void* hip_stream, const uint8_t* d_src, uint64_t window,
 int v2p_fill_launch(void* hip_stream, uint8_t* d_out, uint64_t bytes, uint32_t word, int nontemporal)
 {
     return v2p::launch_fill(d_out, bytes, word, nontemporal, reinterpret_cast<hipStream_t>(hip_stream)) == hipSuccess ? 0 : -2;
+}
+
+int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch)
+{
+    using namespace v2p;
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (kind == 2) return launch_tasks_tile_scan(static_cast<const TaskCount*>(d_in), n, static_cast<TaskCount*>(d_out), static_cast<TaskCount*>(d_scratch), st) == hipSuccess ? 0 : -2;
+    if ((kind != 0 && kind != 1) || n > 0xFFFFFFFFull) return -1;
+    return launch_device_scan(static_cast<const uint32_t*>(d_in), uint32_t(n), kind == 0 ? static_cast<unsigned long long*>(d_out) : nullptr,
+                              kind == 1 ? static_cast<uint32_t*>(d_out) : nullptr, static_cast<unsigned long long*>(d_scratch), st) == hipSuccess ? 0 : -2;
 }
 
 }  // extern "C"

@@ -98,6 +98,9 @@ int v2p_copy_mix_launch(void* hip_stream, const uint8_t* d_src, uint64_t window,
                         const uint8_t* d_desc, uint32_t bytes_per_lane, uint32_t every, uint32_t stride, uint32_t flags);
 int v2p_gather_bench_launch(void* hip_stream, const uint8_t* d_src, uint64_t window, uint32_t misalign, uint32_t iters,
                             uint32_t blocks, uint32_t* d_sink);
+/* the front end's prefix sums through the product's launchers on caller-owned device memory (tests/test_gpu_scan.py): kind 0 / 1 = launch_device_scan,
+ * uint32_t in[n], uint64_t / uint32_t out[n + 1], scratch = the 64-bit total; 2 = launch_tasks_tile_scan, TaskCount in[n], out[n + 1], scratch[ceil(n / TASKS_SCAN_TILE) + 1] */
+int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

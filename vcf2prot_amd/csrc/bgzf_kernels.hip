@@ -14,6 +14,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "bgzf_format.hpp"
 #include "bgzf_kernels.h"
+#include "block_scan.hpp"
 
 namespace {
 
@@ -36,41 +37,17 @@ __host__ __device__ inline uint64_t slots_offset(uint64_t n_ranges) { return 256
 
 __device__ inline SlotMeta* meta_of(uint8_t* slots, uint64_t blk) { return reinterpret_cast<SlotMeta*>(slots + blk * bgzf::SLOT + META); }
 
-// block-wide exclusive scan of one value per thread (blockDim.x == NT, a multiple of 64); returns the exclusive prefix, *total the sum
-template <uint32_t NT, class T>
-__device__ inline T block_exclusive_scan(T v, T* lds, T* total)
-{
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        T run = 0;
-        for (uint32_t w = 0; w < NT / 64; ++w) { const T t = lds[w]; lds[w] = run; run += t; }
-        lds[NT / 64] = run;
-    }
-    __syncthreads();
-    const T ex = lds[wave] + x - v;
-    *total = lds[NT / 64];
-    __syncthreads();
-    return ex;
-}
-
 __global__ __launch_bounds__(SCAN_THREADS) void bgzf_plan_kernel(const uint64_t* __restrict__ range_begin, uint64_t n_ranges,
                                                                   uint64_t* __restrict__ n_blocks, uint64_t* __restrict__ blk_begin)
 {
-    __shared__ uint64_t lds[SCAN_THREADS / 64 + 1];
+    __shared__ uint64_t lds[SCAN_THREADS / 64];
     uint64_t carry = 0;
     for (uint64_t base = 0; base < n_ranges; base += SCAN_THREADS) {
         const uint64_t r = base + threadIdx.x;
         uint64_t nb = 0;
         if (r < n_ranges && range_begin[r + 1] > range_begin[r]) nb = (range_begin[r + 1] - range_begin[r] + bgzf::BLOCK - 1) / bgzf::BLOCK;
         uint64_t tot;
-        const uint64_t ex = block_exclusive_scan<SCAN_THREADS>(nb, lds, &tot);
+        const uint64_t ex = v2p::block_excl_scan<SCAN_THREADS>(nb, lds, &tot);
         if (r < n_ranges) blk_begin[r] = carry + ex;
         carry += tot;
     }
@@ -113,7 +90,7 @@ struct CompressLds {
     bgzf::Plan plan;
     uint32_t crc[LANES / 64];
     uint32_t table[256];
-    uint64_t scan[LANES / 64 + 1];
+    uint64_t scan[LANES / 64];
     int n_sym;
     uint32_t stored;
 };
@@ -194,7 +171,7 @@ __global__ __launch_bounds__(LANES) void bgzf_compress_kernel(const uint8_t* __r
         for (uint32_t d = 32; d; d >>= 1) raw ^= __shfl_xor(raw, d, 64);
         if (lane == 0) L.crc[wave] = raw;
         uint64_t data_bits;
-        const uint64_t off = block_exclusive_scan<LANES>(bits, L.scan, &data_bits);
+        const uint64_t off = v2p::block_excl_scan<LANES>(bits, L.scan, &data_bits);
         if (t == 0) {
             L.plan.data_bits = data_bits;
             L.stored = use_stored(L.plan, n) ? 1u : 0u;
@@ -249,26 +226,24 @@ __global__ __launch_bounds__(LANES) void bgzf_compress_kernel(const uint8_t* __r
 __global__ __launch_bounds__(SCAN_THREADS) void bgzf_sizes_kernel(const uint64_t* __restrict__ n_blocks_p, const uint64_t* __restrict__ blk_begin,
                                                                    uint64_t n_ranges, uint8_t* __restrict__ slots, uint64_t* __restrict__ out_begin)
 {
-    __shared__ uint64_t lds[SCAN_THREADS / 64 + 1];
-    __shared__ uint64_t total_s;
+    __shared__ uint64_t lds[SCAN_THREADS / 64];
     const uint64_t n_blocks = *n_blocks_p;
     uint64_t carry = 0;
     for (uint64_t base = 0; base < n_blocks; base += SCAN_THREADS) {
         const uint64_t b = base + threadIdx.x;
         const uint64_t sz = b < n_blocks ? meta_of(slots, b)->size : 0;
         uint64_t tot;
-        const uint64_t ex = block_exclusive_scan<SCAN_THREADS>(sz, lds, &tot);
+        const uint64_t ex = v2p::block_excl_scan<SCAN_THREADS>(sz, lds, &tot);
         if (b < n_blocks) meta_of(slots, b)->moff = carry + ex;
         carry += tot;
     }
-    if (threadIdx.x == 0) total_s = carry;
     __threadfence_block();
     __syncthreads();
     for (uint64_t r = threadIdx.x; r < n_ranges; r += SCAN_THREADS) {
         const uint64_t b = blk_begin[r];
-        out_begin[r] = b < n_blocks ? meta_of(slots, b)->moff : total_s;
+        out_begin[r] = b < n_blocks ? meta_of(slots, b)->moff : carry;
     }
-    if (threadIdx.x == 0) out_begin[n_ranges] = total_s;
+    if (threadIdx.x == 0) out_begin[n_ranges] = carry;
 }
 
 __global__ __launch_bounds__(256) void bgzf_compact_kernel(const uint64_t* __restrict__ n_blocks_p, const uint8_t* __restrict__ slots,

@@ -8,8 +8,6 @@
 namespace v2p {
 
 constexpr uint32_t CSQ_THREADS = 64;            // lanes of one workgroup: every lane walks a text of its own length
-constexpr uint32_t CSQ_SCAN_THREADS = 1024;     // the scans run in one workgroup that walks the array tile by tile
-constexpr uint32_t CSQ_SCAN_PER_THREAD = 8;
 constexpr uint32_t CSQ_NO_NAME = ~0u;           // name_len of a consequence that does not split
 constexpr uint32_t CSQ_MAX_EXTRA = 65535;       // extras of one consequence (prepare_tables refuses more)
 
@@ -55,7 +53,5 @@ hipError_t launch_csq_rank(const CsqArgs& a, hipStream_t st);
 hipError_t launch_csq_ident_insert(const CsqArgs& a, hipStream_t st);   // insert, then own_label
 hipError_t launch_csq_ident(const CsqArgs& a, hipStream_t st);          // ident from label_rank
 hipError_t launch_csq_extras(const CsqArgs& a, bool emit, hipStream_t st);
-// out[n + 1] = exclusive prefix sums of in[n] (out[n] the total, also as 64 bits in *total); Out = uint32_t or unsigned long long
-hipError_t launch_csq_scan(const uint32_t* in, uint32_t n, unsigned long long* out64, uint32_t* out32, unsigned long long* total, hipStream_t st);
 
 }  // namespace v2p

@@ -317,43 +317,6 @@ __global__ __launch_bounds__(CSQ_THREADS) void csq_extras_kernel(CsqArgs a)
     }
 }
 
-// one workgroup walks the array tile by tile with a running carry
-__global__ __launch_bounds__(CSQ_SCAN_THREADS) void csq_scan_kernel(const uint32_t* in, uint32_t n, unsigned long long* out64, uint32_t* out32,
-                                                                      unsigned long long* total)
-{
-    __shared__ unsigned long long part[CSQ_SCAN_THREADS];
-    const uint32_t t = threadIdx.x;
-    constexpr uint64_t TILE = uint64_t(CSQ_SCAN_THREADS) * CSQ_SCAN_PER_THREAD;
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < n; base += TILE) {
-        const uint64_t i0 = base + uint64_t(t) * CSQ_SCAN_PER_THREAD;
-        uint32_t v[CSQ_SCAN_PER_THREAD];
-        unsigned long long sum = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < CSQ_SCAN_PER_THREAD; ++j) { v[j] = i0 + j < n ? in[i0 + j] : 0u; sum += v[j]; }
-        part[t] = sum;
-        __syncthreads();
-        for (uint32_t off = 1; off < CSQ_SCAN_THREADS; off <<= 1) {
-            const unsigned long long add = t >= off ? part[t - off] : 0ull;
-            __syncthreads();
-            part[t] += add;
-            __syncthreads();
-        }
-        unsigned long long run = carry + part[t] - sum;
-#pragma unroll
-        for (uint32_t j = 0; j < CSQ_SCAN_PER_THREAD; ++j) {
-            if (i0 + j < n) { if (out64) out64[i0 + j] = run; else out32[i0 + j] = uint32_t(run); }
-            run += v[j];
-        }
-        carry += part[CSQ_SCAN_THREADS - 1];
-        __syncthreads();
-    }
-    if (t == 0) {
-        if (out64) out64[n] = carry; else out32[n] = uint32_t(carry);
-        *total = carry;
-    }
-}
-
 inline dim3 lanes(uint32_t n) { return dim3((n + CSQ_THREADS - 1) / CSQ_THREADS); }
 
 }  // namespace
@@ -401,12 +364,6 @@ hipError_t launch_csq_extras(const CsqArgs& a, bool emit, hipStream_t st)
     if (!a.n) return hipSuccess;
     if (emit) csq_extras_kernel<true><<<lanes(a.n), CSQ_THREADS, 0, st>>>(a);
     else csq_extras_kernel<false><<<lanes(a.n), CSQ_THREADS, 0, st>>>(a);
-    return hipGetLastError();
-}
-
-hipError_t launch_csq_scan(const uint32_t* in, uint32_t n, unsigned long long* out64, uint32_t* out32, unsigned long long* total, hipStream_t st)
-{
-    csq_scan_kernel<<<dim3(1), CSQ_SCAN_THREADS, 0, st>>>(in, n, out64, out32, total);
     return hipGetLastError();
 }
 

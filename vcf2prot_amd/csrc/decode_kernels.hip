@@ -20,23 +20,13 @@
 //           step each; inside a record every sample appears once, so thread k places carrier k with no conflict and an
 //           LDS-only barrier separates the records.
 #include "decode_kernels.h"
+#include "block_scan.hpp"
 #include <cstdlib>
 
 namespace v2p {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t dec_wave_incl_scan(uint32_t x)
-{
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, true);   // row_shr:1 (lanes shifted in from outside the row read 0)
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, true);   // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, true);   // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, true);   // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return x;
-}
 
 __device__ __forceinline__ void dec_report(unsigned long long* status, uint64_t field, uint32_t reason)
 {
@@ -334,7 +324,7 @@ __global__ __launch_bounds__(BS) void parse_rows_kernel(DecodeArgs a)
             if (tid == te) tm |= 1u << (Lq - tile0 - te * 16u);
         }
         const uint32_t cnt = uint32_t(__builtin_popcount(tm));
-        const uint32_t incl = dec_wave_incl_scan(cnt);
+        const uint32_t incl = wave_incl_scan(cnt);
         if ((tid & 63u) == 63u) wave_tot[wave] = incl;
         dec_lds_barrier();
         if (tid == 0) s_cnt[(t + 1u) & 1u] = 0u;                               // (the next step's counter: its last readers are a barrier behind)
@@ -367,7 +357,7 @@ __global__ __launch_bounds__(BS) void parse_rows_kernel(DecodeArgs a)
         const uint32_t nw = uint32_t(__builtin_popcount(wm));
         uint32_t k0 = 0u;                                                       // the lane's first entry among the step's
         if (__builtin_amdgcn_ballot_w64(nw != 0u)) {
-            const uint32_t wincl = dec_wave_incl_scan(nw);
+            const uint32_t wincl = wave_incl_scan(nw);
             uint32_t at = 0u;
             if ((tid & 63u) == 63u) at = atomicAdd(&s_cnt[t & 1u], wincl);
             at = uint32_t(__builtin_amdgcn_readlane(int(at), 63));
@@ -432,7 +422,7 @@ __global__ __launch_bounds__(256) void count_kernel(DecodeArgs a, uint32_t n_ran
     for (uint32_t i = tid; i < hn; i += 256u) hist[i] = 0u;
     if (tid < 64u) {                                                            // exclusive prefix of the block's 64 record sizes (one wave)
         static_assert(DEC_ROWBLOCK == 64u, "one wave scans the block's record sizes");
-        const uint32_t n = r0 + tid < r1 ? a.row_nnz[r0 + tid] : 0u, incl = dec_wave_incl_scan(n);
+        const uint32_t n = r0 + tid < r1 ? a.row_nnz[r0 + tid] : 0u, incl = wave_incl_scan(n);
         s_pre[tid] = incl - n;
         if (tid == 63u) s_pre[64] = incl;
     }
@@ -470,7 +460,7 @@ __global__ __launch_bounds__(256) void count_kernel(DecodeArgs a, uint32_t n_ran
     __shared__ uint32_t s_tot;
     if (tid == 0) s_tot = 0u;
     __syncthreads();
-    const uint32_t wsum = dec_wave_incl_scan(mine);
+    const uint32_t wsum = wave_incl_scan(mine);
     if (lane == 63u) atomicAdd(&s_tot, wsum);
     __syncthreads();
     if (tid == 0) a.blk_total[blockIdx.x] = s_tot;                              // (index = record block * n_ranges + range)
@@ -524,28 +514,17 @@ __global__ __launch_bounds__(1024) void scan_haps_kernel(DecodeArgs a)
         if (threadIdx.x == 0) a.status[1] = *a.ovf_used;
         return;
     }
-    __shared__ uint64_t part[16];
-    __shared__ uint64_t carry;
-    const uint32_t n_haps = 2u * a.n_samples, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0) { carry = 0; a.hap_begin[0] = 0; }
-    __syncthreads();
+    __shared__ uint64_t part[1024 / 64];
+    const uint32_t n_haps = 2u * a.n_samples, tid = threadIdx.x;
+    if (tid == 0) a.hap_begin[0] = 0;
+    uint64_t carry = 0;
     for (uint32_t b = 0; b < n_haps; b += 1024u) {
         const uint32_t h = b + tid;
         const uint64_t v = h < n_haps ? a.hap_begin[h + 1u] : 0ull;
-        unsigned long long x = v;                                 // wave inclusive scan, 64-bit, via shuffles
-#pragma unroll
-        for (uint32_t d = 1; d < 64u; d <<= 1) {
-            const unsigned long long y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63u) part[wave] = x;
-        __syncthreads();
-        uint64_t wb = carry;
-        for (uint32_t w = 0; w < wave; ++w) wb += part[w];
-        if (h < n_haps) a.hap_begin[h + 1u] = wb + x;
-        __syncthreads();
-        if (tid == 1023u) carry = wb + x;
-        __syncthreads();
+        uint64_t tot;
+        const uint64_t ex = block_excl_scan<1024>(v, part, &tot);
+        if (h < n_haps) a.hap_begin[h + 1u] = carry + ex + v;
+        carry += tot;
     }
     if (tid == 0) {
         a.status[1] = *a.ovf_used;
@@ -705,7 +684,7 @@ __global__ __launch_bounds__(256) void emit_staged_kernel(DecodeArgs a, uint32_t
         const uint32_t seg = (hn + 255u) / 256u, b = min(tid * seg, hn), e = min(b + seg, hn);
         uint32_t sum = 0u;
         for (uint32_t i = b; i < e; ++i) sum += lcur[i];
-        const uint32_t incl = dec_wave_incl_scan(sum);
+        const uint32_t incl = wave_incl_scan(sum);
         if (lane == 63u) s_ws[wid] = incl;
         __syncthreads();
         uint32_t run = incl - sum;

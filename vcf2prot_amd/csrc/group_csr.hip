@@ -17,11 +17,13 @@
 // groups and members counted, nothing written.  An aborting list (id out of range, poison id, drop_replicate's abort) is reported
 // through status[0] as in group_stats.hip and the emit launch does not run.
 #include "group_csr.h"
+#include "block_scan.hpp"
 
 namespace v2p {
 namespace {
 
-enum : uint32_t { G_ERR, G_ERR_CODE, G_REFUSE, G_NKEYS, G_ABORT_RANK, G_SCAN /* 4 words */ };
+enum : uint32_t { G_ERR, G_ERR_CODE, G_REFUSE, G_NKEYS, G_ABORT_RANK, G_SCAN /* GROUPS_THREADS / 64 words: block_excl_scan's scratch */ };
+static_assert(G_SCAN + GROUPS_THREADS / 64 <= GROUPS_MISC_WORDS, "misc words");
 
 // exclusive popcount prefixes of bits[0, n) into prefix[0, n); returns the total.  Every thread of the workgroup calls it.
 __device__ uint32_t word_prefix(const uint32_t* bits, uint32_t* prefix, uint32_t n, uint32_t* scan, uint32_t tid)
@@ -30,22 +32,8 @@ __device__ uint32_t word_prefix(const uint32_t* bits, uint32_t* prefix, uint32_t
     const uint32_t w0 = min(tid * per, n), w1 = min(w0 + per, n);
     uint32_t sum = 0;
     for (uint32_t w = w0; w < w1; ++w) sum += uint32_t(__popc(bits[w]));
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-    uint32_t inc = sum;
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
-    __syncthreads();                                                   // the readers of an earlier call are done with scan[]
-    if (lane == 63u) scan[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (uint32_t k = 0; k < GROUPS_THREADS / 64u; ++k) {
-        const uint32_t v = scan[k];
-        if (k < wave) base += v;
-        total += v;
-    }
-    uint32_t run = base + inc - sum;
+    uint32_t total;
+    uint32_t run = block_excl_scan<GROUPS_THREADS>(sum, scan, &total);
     for (uint32_t w = w0; w < w1; ++w) { prefix[w] = run; run += uint32_t(__popc(bits[w])); }
     __syncthreads();
     return total;
@@ -223,21 +211,15 @@ __global__ __launch_bounds__(GROUPS_THREADS) void group_csr_kernel(const GroupsA
 // exclusive prefix sums of the lists' {groups, members}: one workgroup, a chunk of consecutive lists per thread
 __global__ __launch_bounds__(GROUPS_THREADS) void group_csr_scan_kernel(const GroupsArgs a)
 {
-    __shared__ unsigned long long sums[2][GROUPS_THREADS];
+    __shared__ unsigned long long scratch[GROUPS_THREADS / 64];
     const uint32_t tid = threadIdx.x, n = a.n_haps;
     const uint32_t per = (n + GROUPS_THREADS - 1u) / GROUPS_THREADS;
     const uint32_t h0 = min(tid * per, n), h1 = min(h0 + per, n);
-    unsigned long long g = 0, m = 0;
+    unsigned long long g = 0, m = 0, g_total, m_total;
     for (uint32_t h = h0; h < h1; ++h) { g += a.counts[2u * h]; m += a.counts[2u * h + 1u]; }
-    sums[0][tid] = g; sums[1][tid] = m;
-    __syncthreads();
-    if (tid < 2u) {
-        unsigned long long run = 0;
-        for (uint32_t t = 0; t < GROUPS_THREADS; ++t) { const unsigned long long v = sums[tid][t]; sums[tid][t] = run; run += v; }
-        (tid ? a.hap_member_begin : a.hap_group_begin)[n] = run;
-    }
-    __syncthreads();
-    g = sums[0][tid]; m = sums[1][tid];
+    g = block_excl_scan<GROUPS_THREADS>(g, scratch, &g_total);
+    m = block_excl_scan<GROUPS_THREADS>(m, scratch, &m_total);
+    if (tid == 0) { a.hap_group_begin[n] = g_total; a.hap_member_begin[n] = m_total; }
     for (uint32_t h = h0; h < h1; ++h) {
         a.hap_group_begin[h] = g; a.hap_member_begin[h] = m;
         g += a.counts[2u * h]; m += a.counts[2u * h + 1u];

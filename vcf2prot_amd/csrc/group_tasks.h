@@ -21,8 +21,10 @@ constexpr uint32_t TASK_AA_LEN_MASK = (1u << 30) - 1u;
 // what step 4b needs of one transcript: by transcript rank, or by slot with -a
 struct TaskTx { int64_t proteome_off; uint64_t header_off[2]; uint32_t ref_len; uint32_t header_len; };
 
-// per item {transcripts (0 / 1), Tasks, alt bytes, arena bytes}; the scan makes exclusive prefix sums of them
+// per item {transcripts (0 / 1), Tasks, alt bytes, arena bytes}; the scan makes exclusive prefix sums of them (block_scan.hpp, through + and -)
 struct TaskCount { unsigned long long tx, tasks, alt, arena; };
+__host__ __device__ inline TaskCount operator+(const TaskCount& x, const TaskCount& y) { return TaskCount{x.tx + y.tx, x.tasks + y.tasks, x.alt + y.alt, x.arena + y.arena}; }
+__host__ __device__ inline TaskCount operator-(const TaskCount& x, const TaskCount& y) { return TaskCount{x.tx - y.tx, x.tasks - y.tasks, x.alt - y.alt, x.arena - y.arena}; }
 
 // why an item aborts (the low byte of the status word)
 enum : uint32_t { TASKS_ABORT_4A = 1, TASKS_ABORT_4B_UNSUPPORTED = 2, TASKS_ABORT_4B_ARITHMETIC = 3, TASKS_ABORT_INSPECT = 4, TASKS_ABORT_RANGE = 5 };
@@ -76,6 +78,8 @@ inline uint64_t tasks_scan_blocks(uint64_t n_items) { return (n_items + TASKS_SC
 
 hipError_t launch_tasks_count(const TasksArgs& a, hipStream_t st);      // counts, kinds, status
 hipError_t launch_tasks_scan(const TasksArgs& a, hipStream_t st);       // base, hap_base
+// its three tile launches alone: base[n + 1] = exclusive prefix sums of counts[n]; block_sums[tasks_scan_blocks(n) + 1] is scratch
+hipError_t launch_tasks_tile_scan(const TaskCount* counts, uint64_t n, TaskCount* base, TaskCount* block_sums, hipStream_t st);
 hipError_t launch_tasks_emit(const TasksArgs& a, hipStream_t st);       // the stream's arrays, final, in place
 hipError_t launch_tasks_sample(const SampleArgs& a, hipStream_t st);
 

@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "group_tasks.h"
+#include "block_scan.hpp"
 
 namespace v2p {
 namespace {
@@ -498,8 +499,7 @@ __global__ __launch_bounds__(TASKS_THREADS) void group_tasks_kernel(const TasksA
     if (EMIT) {
         kind = a.kinds[item];
         if (kind == TASKS_ITEM_DROPPED) return;
-        const TaskCount b = a.base[item];
-        base = TaskCount{b.tx - a.first.tx, b.tasks - a.first.tasks, b.alt - a.first.alt, b.arena - a.first.arena};
+        base = a.base[item] - a.first;
     }
     Sink<EMIT> sink{a, base.tasks, base.alt};
     // transcript_instructions.rs:37-41: a transcript the reference FASTA does not have is skipped
@@ -554,61 +554,33 @@ __global__ __launch_bounds__(TASKS_THREADS) void group_tasks_kernel(const TasksA
 }
 
 // ---- exclusive prefix sums of the items' counts: tile sums, their scan in one workgroup, the tiles again --------------------
-__device__ TaskCount add(const TaskCount& x, const TaskCount& y) { return TaskCount{x.tx + y.tx, x.tasks + y.tasks, x.alt + y.alt, x.arena + y.arena}; }
-
-__global__ __launch_bounds__(TASKS_SCAN_THREADS) void tasks_tile_sums_kernel(const TasksArgs a)
+// a tile per workgroup, TASKS_SCAN_PER_THREAD consecutive items per thread.  APPLY false: the tile's sum into block_sums[tile]; APPLY true, once
+// tasks_tile_scan_kernel has turned block_sums into the tiles' bases: base[] of the tile's items
+template <bool APPLY>
+__global__ __launch_bounds__(TASKS_SCAN_THREADS) void tasks_tile_kernel(const TaskCount* counts, uint64_t n, TaskCount* block_sums, TaskCount* base)
 {
-    __shared__ TaskCount part[TASKS_SCAN_THREADS];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t i0 = (uint64_t(blockIdx.x) * TASKS_SCAN_THREADS + tid) * TASKS_SCAN_PER_THREAD;
-    TaskCount s{0, 0, 0, 0};
-    for (uint32_t k = 0; k < TASKS_SCAN_PER_THREAD; ++k) if (i0 + k < a.n_items) s = add(s, a.counts[i0 + k]);
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t w = TASKS_SCAN_THREADS / 2; w; w >>= 1) {
-        if (tid < w) part[tid] = add(part[tid], part[tid + w]);
-        __syncthreads();
-    }
-    if (tid == 0) a.block_sums[blockIdx.x] = part[0];
+    __shared__ TaskCount scratch[TASKS_SCAN_THREADS / 64];
+    const uint64_t i0 = (uint64_t(blockIdx.x) * TASKS_SCAN_THREADS + threadIdx.x) * TASKS_SCAN_PER_THREAD;
+    TaskCount s{0, 0, 0, 0}, total;
+    for (uint32_t k = 0; k < TASKS_SCAN_PER_THREAD; ++k) if (i0 + k < n) s = s + counts[i0 + k];
+    s = block_excl_scan<TASKS_SCAN_THREADS>(s, scratch, &total);
+    if (!APPLY) { if (threadIdx.x == 0) block_sums[blockIdx.x] = total; return; }
+    s = s + block_sums[blockIdx.x];
+    for (uint32_t k = 0; k < TASKS_SCAN_PER_THREAD; ++k) if (i0 + k < n) { base[i0 + k] = s; s = s + counts[i0 + k]; }
 }
 
-// one workgroup, a chunk of consecutive tiles per thread (group_csr_scan_kernel's shape)
-__global__ __launch_bounds__(TASKS_SCAN_THREADS) void tasks_tile_scan_kernel(const TasksArgs a, uint64_t n_tiles)
+// one workgroup, a chunk of consecutive tiles per thread; the sum of all tiles goes to *total (base[n])
+__global__ __launch_bounds__(TASKS_SCAN_THREADS) void tasks_tile_scan_kernel(TaskCount* block_sums, uint64_t n_tiles, TaskCount* total)
 {
-    __shared__ TaskCount sums[TASKS_SCAN_THREADS];
+    __shared__ TaskCount scratch[TASKS_SCAN_THREADS / 64];
     const uint32_t tid = threadIdx.x;
     const uint64_t per = (n_tiles + TASKS_SCAN_THREADS - 1) / TASKS_SCAN_THREADS;
     const uint64_t t0 = uint64_t(tid) * per < n_tiles ? uint64_t(tid) * per : n_tiles, t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
-    TaskCount s{0, 0, 0, 0};
-    for (uint64_t t = t0; t < t1; ++t) s = add(s, a.block_sums[t]);
-    sums[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        TaskCount run{0, 0, 0, 0};
-        for (uint32_t t = 0; t < TASKS_SCAN_THREADS; ++t) { const TaskCount v = sums[t]; sums[t] = run; run = add(run, v); }
-        a.base[a.n_items] = run;
-    }
-    __syncthreads();
-    s = sums[tid];
-    for (uint64_t t = t0; t < t1; ++t) { const TaskCount v = a.block_sums[t]; a.block_sums[t] = s; s = add(s, v); }
-}
-
-__global__ __launch_bounds__(TASKS_SCAN_THREADS) void tasks_tile_apply_kernel(const TasksArgs a)
-{
-    __shared__ TaskCount part[TASKS_SCAN_THREADS];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t i0 = (uint64_t(blockIdx.x) * TASKS_SCAN_THREADS + tid) * TASKS_SCAN_PER_THREAD;
-    TaskCount s{0, 0, 0, 0};
-    for (uint32_t k = 0; k < TASKS_SCAN_PER_THREAD; ++k) if (i0 + k < a.n_items) s = add(s, a.counts[i0 + k]);
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        TaskCount run = a.block_sums[blockIdx.x];
-        for (uint32_t t = 0; t < TASKS_SCAN_THREADS; ++t) { const TaskCount v = part[t]; part[t] = run; run = add(run, v); }
-    }
-    __syncthreads();
-    s = part[tid];
-    for (uint32_t k = 0; k < TASKS_SCAN_PER_THREAD; ++k) if (i0 + k < a.n_items) { a.base[i0 + k] = s; s = add(s, a.counts[i0 + k]); }
+    TaskCount s{0, 0, 0, 0}, all;
+    for (uint64_t t = t0; t < t1; ++t) s = s + block_sums[t];
+    s = block_excl_scan<TASKS_SCAN_THREADS>(s, scratch, &all);
+    if (tid == 0) *total = all;
+    for (uint64_t t = t0; t < t1; ++t) { const TaskCount v = block_sums[t]; block_sums[t] = s; s = s + v; }
 }
 
 __device__ uint64_t first_item(const TasksArgs& a, uint32_t h) { return a.slot_rank ? uint64_t(h) * a.n_slots : uint64_t(a.hap_group_begin[h]); }
@@ -659,12 +631,19 @@ hipError_t launch_tasks_count(const TasksArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
+hipError_t launch_tasks_tile_scan(const TaskCount* counts, uint64_t n, TaskCount* base, TaskCount* block_sums, hipStream_t st)
+{
+    const uint64_t n_tiles = tasks_scan_blocks(n);
+    if (n_tiles) hipLaunchKernelGGL(tasks_tile_kernel<false>, dim3(uint32_t(n_tiles)), dim3(TASKS_SCAN_THREADS), 0, st, counts, n, block_sums, base);
+    hipLaunchKernelGGL(tasks_tile_scan_kernel, dim3(1), dim3(TASKS_SCAN_THREADS), 0, st, block_sums, n_tiles, base + n);
+    if (n_tiles) hipLaunchKernelGGL(tasks_tile_kernel<true>, dim3(uint32_t(n_tiles)), dim3(TASKS_SCAN_THREADS), 0, st, counts, n, block_sums, base);
+    return hipGetLastError();
+}
+
 hipError_t launch_tasks_scan(const TasksArgs& a, hipStream_t st)
 {
-    const uint64_t n_tiles = tasks_scan_blocks(a.n_items);
-    if (n_tiles) hipLaunchKernelGGL(tasks_tile_sums_kernel, dim3(uint32_t(n_tiles)), dim3(TASKS_SCAN_THREADS), 0, st, a);
-    hipLaunchKernelGGL(tasks_tile_scan_kernel, dim3(1), dim3(TASKS_SCAN_THREADS), 0, st, a, n_tiles);
-    if (n_tiles) hipLaunchKernelGGL(tasks_tile_apply_kernel, dim3(uint32_t(n_tiles)), dim3(TASKS_SCAN_THREADS), 0, st, a);
+    const hipError_t e = launch_tasks_tile_scan(a.counts, a.n_items, a.base, a.block_sums, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tasks_hap_base_kernel, dim3(blocks_for(uint64_t(a.n_haps) + 1, TASKS_SCAN_THREADS)), dim3(TASKS_SCAN_THREADS), 0, st, a);
     return hipGetLastError();
 }

@@ -16,6 +16,7 @@
 
 #include "host/intmap_format.hpp"
 #include "intmap_json.h"
+#include "block_scan.hpp"
 
 namespace v2p {
 namespace {
@@ -239,11 +240,7 @@ __global__ __launch_bounds__(INTMAP_THREADS) void intmap_emit_groups_kernel(cons
             }
             take = fl + (m0 + lane > m_begin ? 1u : 0u);
         }
-        uint32_t inc = take;
-        for (uint32_t off = 1; off < INTMAP_WAVE; off <<= 1) {
-            const uint32_t v = __shfl_up(inc, off, INTMAP_WAVE);
-            if (lane >= off) inc += v;
-        }
+        const uint32_t inc = wave_incl_scan(take);
         const uint32_t excl = inc - take;
         for (uint32_t j = 0; j < cnt; ++j) {
             const uint32_t fl_j = __shfl(fl, j, INTMAP_WAVE);

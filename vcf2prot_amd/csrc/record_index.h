@@ -1,6 +1,6 @@
 // record_index.h -- launchers of the record-index kernels (record_index.hip; include/v2p_frontend.h part 8): v2p_vcf_index_build of
 // host/vcf_index.cpp on the device, from the text the decode keeps resident.  The line pass finds the lines, a tile of the text per
-// workgroup; the record pass counts with a wave per line and emits with a lane per line.  The prefix sums are csq_tables.h's launch_csq_scan.
+// workgroup; the record pass counts with a wave per line and emits with a lane per line.  The prefix sums are device_scan.h's launch_device_scan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -12,6 +12,7 @@
 // A failing line sets the status word and the pass goes on.  No store goes past an array's size.
 #include "record_index.h"
 #include "csq_sup_names.h"
+#include "block_scan.hpp"
 
 namespace v2p {
 namespace {
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(RIDX_LINE_THREADS) void index_lines_emit_kernel(Lin
 {
     constexpr uint32_t CHUNKS = RIDX_LINE_THREADS * RIDX_LINE_LOADS;
     __shared__ uint32_t chunk_cnt[CHUNKS];      // line feeds of every chunk, then the line feeds of the tile in front of it
-    __shared__ uint32_t part[RIDX_LINE_THREADS];
+    __shared__ uint32_t scratch[RIDX_LINE_THREADS / 64];
     const uint32_t t = threadIdx.x;
     const u64 base = u64(blockIdx.x) * RIDX_TILE_BYTES;
     uint32_t f[RIDX_LINE_LOADS][4];
@@ -84,15 +85,8 @@ __global__ __launch_bounds__(RIDX_LINE_THREADS) void index_lines_emit_kernel(Lin
     uint32_t own[RIDX_LINE_LOADS], sum = 0;
 #pragma unroll
     for (uint32_t k = 0; k < RIDX_LINE_LOADS; ++k) { own[k] = chunk_cnt[RIDX_LINE_LOADS * t + k]; sum += own[k]; }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < RIDX_LINE_THREADS; off <<= 1) {
-        const uint32_t add = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
+    uint32_t total;
+    uint32_t run = block_excl_scan<RIDX_LINE_THREADS>(sum, scratch, &total);
 #pragma unroll
     for (uint32_t k = 0; k < RIDX_LINE_LOADS; ++k) { chunk_cnt[RIDX_LINE_LOADS * t + k] = run; run += own[k]; }
     __syncthreads();

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "stitch_kernels.h"
+#include "block_scan.hpp"
 
 namespace v2p {
 
@@ -83,18 +84,6 @@ __device__ __forceinline__ u32x4 imm_block(uint64_t lit, int32_t q)
 
 constexpr uint64_t ADJ_IMM = 1ull << 63;       // s_adj entry of an immediate task: flag | literal bytes
 constexpr uint64_t ADJ_LIT = (1ull << 40) - 1;
-
-// ---- wave64 inclusive add-scan with DPP (row_shr 1/2/4/8, row_bcast 15/31) ----
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x)
-{
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, false);  // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, false);  // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, false);  // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, false);  // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return x;
-}
 
 __device__ __forceinline__ void report(unsigned long long* status, uint64_t index, uint32_t reason)
 {

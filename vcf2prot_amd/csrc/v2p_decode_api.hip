@@ -14,6 +14,7 @@
 #include "../../include/v2p_frontend.h"
 #include "decode_kernels.h"
 #include "csq_tables.h"
+#include "device_scan.h"
 #include "group_csr.h"
 #include "group_stats.h"
 #include "group_tasks.h"
@@ -1100,7 +1101,7 @@ int v2p_decode_intmap_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, cons
     // fragments: lengths, offsets, bytes
     TRY(launch_intmap_fragments(a, false, st), "intmap_fragment_kernel (count)");
     TRY(hipEventRecord(ev[2], st), "hipEventRecord");
-    TRY(launch_csq_scan(a.frag_len, uint32_t(n_csq), a.frag_begin, nullptr, d_totals + 0, st), "csq_scan_kernel (fragments)");
+    TRY(launch_device_scan(a.frag_len, uint32_t(n_csq), a.frag_begin, nullptr, d_totals + 0, st), "device_scan_kernel (fragments)");
     TRY(hipEventRecord(ev[3], st), "hipEventRecord");
     uint64_t frag_bytes = 0;
     TRY(hipMemcpyAsync(&frag_bytes, d_totals + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H(fragment bytes)");
@@ -1115,11 +1116,11 @@ int v2p_decode_intmap_count(v2p_ctx* ctx, v2p_decode* d, const uint8_t* aa, cons
     TRY(launch_intmap_fragments(a, true, st), "intmap_fragment_kernel (emit)");
     TRY(launch_intmap_group_count(a, st), "intmap_group_count_kernel");
     TRY(hipEventRecord(ev[2], st), "hipEventRecord");
-    TRY(launch_csq_scan(a.group_len, uint32_t(gr.n_groups), a.group_begin, nullptr, d_totals + 1, st), "csq_scan_kernel (groups)");
+    TRY(launch_device_scan(a.group_len, uint32_t(gr.n_groups), a.group_begin, nullptr, d_totals + 1, st), "device_scan_kernel (groups)");
     TRY(hipEventRecord(ev[3], st), "hipEventRecord");
     TRY(launch_intmap_proband_count(a, st), "intmap_proband_count_kernel");
     TRY(hipEventRecord(ev[4], st), "hipEventRecord");
-    TRY(launch_csq_scan(a.proband_len, uint32_t(n_samples), a.proband_begin, nullptr, d_totals + 2, st), "csq_scan_kernel (probands)");
+    TRY(launch_device_scan(a.proband_len, uint32_t(n_samples), a.proband_begin, nullptr, d_totals + 2, st), "device_scan_kernel (probands)");
     TRY(hipEventRecord(ev[5], st), "hipEventRecord");
     uint64_t status = 0;
     im.host_proband_begin.assign(n_samples + 1, 0);
@@ -1267,7 +1268,7 @@ int v2p_decode_tables_build(v2p_ctx* ctx, v2p_decode* d, const uint8_t* text, co
         return e == hipSuccess ? hipStreamSynchronize(st) : e;
     };
     TRY(launch_csq_parse(a, false, st), "csq_parse_kernel (count)");
-    if (n) TRY(launch_csq_scan(a.aa_count, n, T.aa_begin.get<unsigned long long>(), nullptr, totals + 0, st), "csq_scan_kernel (aa)");
+    if (n) TRY(launch_device_scan(a.aa_count, n, T.aa_begin.get<unsigned long long>(), nullptr, totals + 0, st), "device_scan_kernel (aa)");
     TRY(read_words(), "D2H(tables status)");
     const uint64_t n_split = host_words[1], n_mut = host_words[2];
     T.n_aa = host_words[5];
@@ -1344,13 +1345,13 @@ int v2p_decode_tables_build(v2p_ctx* ctx, v2p_decode* d, const uint8_t* text, co
     TRY(hipMemsetAsync(d_ident_slots.get<void>(), 0, ident_slots * sizeof(uint32_t), st), "hipMemset(ident_slots)");
     a.ident_slots = d_ident_slots.get<uint32_t>(); a.ident_mask = uint32_t(ident_slots - 1);
     TRY(launch_csq_ident_insert(a, st), "csq_insert_kernel (ident)");
-    if (n) TRY(launch_csq_scan(a.own_label, n, nullptr, d_label_rank.get<uint32_t>(), totals + 1, st), "csq_scan_kernel (labels)");
+    if (n) TRY(launch_device_scan(a.own_label, n, nullptr, d_label_rank.get<uint32_t>(), totals + 1, st), "device_scan_kernel (labels)");
     TRY(launch_csq_ident(a, st), "csq_ident_kernel");
     TRY(hipEventRecord(ev[5], st), "hipEventRecord");
 
     // extras: count, scan, emit
     TRY(launch_csq_extras(a, false, st), "csq_extras_kernel (count)");
-    if (n) TRY(launch_csq_scan(a.extra_count, n, nullptr, T.extra_begin.get<uint32_t>(), totals + 2, st), "csq_scan_kernel (extras)");
+    if (n) TRY(launch_device_scan(a.extra_count, n, nullptr, T.extra_begin.get<uint32_t>(), totals + 2, st), "device_scan_kernel (extras)");
     TRY(read_words(), "D2H(tables status)");
     if (host_words[0] != ~0ull) {
         const uint32_t why = uint32_t(host_words[0] & 0xFF);
@@ -1477,7 +1478,7 @@ int v2p_decode_index_build(v2p_ctx* ctx, v2p_decode* d, v2p_index_info* info)
     la.tile_count = d_tile_count.get<uint32_t>(); la.tile_base = d_tile_base.get<unsigned long long>();
     TRY(hipEventRecord(ev[0], st), "hipEventRecord");
     TRY(launch_index_lines(la, false, st), "index_lines_count_kernel");
-    TRY(launch_csq_scan(la.tile_count, la.n_tiles, d_tile_base.get<unsigned long long>(), nullptr, totals + 0, st), "csq_scan_kernel (tiles)");
+    TRY(launch_device_scan(la.tile_count, la.n_tiles, d_tile_base.get<unsigned long long>(), nullptr, totals + 0, st), "device_scan_kernel (tiles)");
     TRY(hipEventRecord(ev[1], st), "hipEventRecord");
     uint8_t last = 0;
     TRY(hipMemcpyAsync(&last, d_text + n_text - 1, 1, hipMemcpyDeviceToHost, st), "D2H(last byte)");
@@ -1502,8 +1503,8 @@ int v2p_decode_index_build(v2p_ctx* ctx, v2p_decode* d, v2p_index_info* info)
     ra.record_rank = d_rank.get<unsigned long long>(); ra.csq_base = d_base.get<unsigned long long>();
     TRY(launch_index_records(ra, false, st), "index_records_kernel (count)");
     TRY(hipEventRecord(ev[4], st), "hipEventRecord");
-    TRY(launch_csq_scan(ra.is_record, ra.n_lines, d_rank.get<unsigned long long>(), nullptr, totals + 1, st), "csq_scan_kernel (records)");
-    TRY(launch_csq_scan(ra.csq_count, ra.n_lines, d_base.get<unsigned long long>(), nullptr, totals + 2, st), "csq_scan_kernel (consequences)");
+    TRY(launch_device_scan(ra.is_record, ra.n_lines, d_rank.get<unsigned long long>(), nullptr, totals + 1, st), "device_scan_kernel (records)");
+    TRY(launch_device_scan(ra.csq_count, ra.n_lines, d_base.get<unsigned long long>(), nullptr, totals + 2, st), "device_scan_kernel (consequences)");
     TRY(hipEventRecord(ev[5], st), "hipEventRecord");
     TRY(read_words(), "D2H(index status)");
     const uint64_t status = host_words[0], header_line = host_words[1], n_records = host_words[3], n_csq = host_words[4];
