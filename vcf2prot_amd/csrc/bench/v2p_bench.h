@@ -77,7 +77,8 @@ int v2p_batch_download_patch_image(v2p_batch* b, uint64_t* seg, uint32_t* patch,
  * 28 = deep Task vectors stay on the dense rows image and stitch_dense_kernel (never a tile image, never re-written as pieces);
  * 29 = v2p_batch_build_and_execute behaves as if the device had no room for its one-pass scratch (tests of the fallback);
  * 30 = never resident rows: a wave image that is executed again stages its descriptors in every phase, as its first execute does;
- * 31 = resident rows also for the dense wave images the rule leaves without (thin ones: C2) */
+ * 31 = resident rows also for the dense wave images the rule leaves without (thin ones: C2);
+ * 32 = stitchw_kernel's one body of 10 rows for every chunk of a rows image, as before the row-count bodies; 33 = bodies of 10 and 9 rows only */
 int v2p_bench_set_variant(v2p_ctx* ctx, uint32_t variant);
 /* microbenchmark: `blocks` workgroups x 4 waves each issue `iters` 16-byte-per-lane gathers (1 KiB per wave
  * instruction) from a window of `window` bytes at byte misalignment `misalign` (0 = aligned); d_sink: one u32 per wave */

@@ -41,6 +41,7 @@ struct StitchArgs {
     uint32_t        opt_phase_min_chunks = 0;// images with fewer chunks are launched at once
     int32_t         opt_store_sc1 = -1;      // wave images: force (1) / forbid (0) "sc1 nt" row stores
     uint32_t        opt_touch = 0;           // bench builds: 1 = no read-ahead, 2 = the read-ahead as kernels of its own, 4 = one launch for all phases
+    uint32_t        opt_wave_bodies = 0;     // bench builds, rows images: 1 = stitchw_kernel's one body of 10 rows for every chunk, 2 = bodies of 10 and 9 rows only
     uint32_t        rows = 0;                // set by launch_stitch(): a rows image (sir_pack.hpp: every chunk carries CHUNK_CLIP) -- stitchw_kernel's ROWS instance
     uint64_t        img_desc = 0, img_bytes = 0; // the chunk table is a RANGE of a larger image (v2p_batch_build_and_execute: one slice): descriptors and result
                                              // bytes of the range, for the routing (0: n_desc, out_len)

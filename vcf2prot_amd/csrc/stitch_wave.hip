@@ -96,6 +96,25 @@ __device__ __forceinline__ u32x4 wmerge(u32x4 v, u32x4 ld, u32x4 m)      // byte
     return v;
 }
 
+constexpr uint32_t WAVE_ROWS = CHUNK_BYTES_WAVE / 1024u;                // 1 KiB rows of a full chunk
+static_assert(WAVE_ROWS == 10u, "the dispatch is written for bodies of 10, 9 and 8 rows");
+constexpr uint32_t WAVE_ND = (WAVE_ROWS + 3u) / 4u;                      // map dwords per lane of a full chunk
+struct WaveLds {
+    uint32_t map32[64u * WAVE_ND];                                       // one byte per 16-byte block: record covering its first byte
+    WRec rec[CHUNK_TASKS_WAVE + 4];                                      // + sentinels
+    u32x4 patch[CHUNK_TASKS_WAVE + 1];                                   // [t]: record t's own piece, then (owners) the parked tail of the block it starts in; [64]: scrap
+};
+
+// What a chunk of at most R rows does once its records are in LDS: the patch phase's gather, phases C, K and the second half of P, and
+// the ragged edge blocks.  The kernel branches ONCE, on the wave-uniform row count of its chunk, into the body of
+// that many rows and returns from there -- every body is straight-line code from the kernel's entry to its last store, so hipcc counts
+// the outstanding gathers in each of them as it does in a kernel with one body.  R sizes the map dwords a lane scans (ND), the rows
+// gathered (v[R]) and the packed record indices (pk[ND]); a chunk with fewer rows than R runs R rows: sentinel records, dropped stores.
+template <uint32_t R, bool NT, bool SC1>
+__device__ __forceinline__ void wave_rows(WaveLds& L, const u32x4* s_mask, const u32x4* s_one, const uint32_t lane, const uint32_t n, const uint32_t head,
+                                          const uint32_t ptotal, const uint32_t nblk, const uint64_t dst, uint8_t* __restrict__ p_out, const uint64_t dots16,
+                                          const uint64_t g1_addr, const WChk& chk);      // (behind the kernel)
+
 // WPG waves per workgroup, each with its own chunk and its own LDS tables; the waves of a workgroup share nothing but the
 // (identical) mask and selector tables.
 //
@@ -118,7 +137,9 @@ __device__ __forceinline__ u32x4 wmerge(u32x4 v, u32x4 ld, u32x4 m)      // byte
 // arrived, so record and descriptors are requested together -- and the trailing workgroups fill the other buffer for the next phase.
 // An image that is executed AGAIN has RESIDENT rows (launch_stitch): row c of one buffer for the whole chunk table, filled once; p_stage is
 // then the phase's first row, and the trailing workgroups only read the next phase's rows (p_rows_next), records and payload lines.
-template <int WPG, bool NT, bool SC1 = false, bool RIMG = false, bool STG = false>
+// BODIES (other than 0: development library only, A/B: v2p_bench_set_variant 32 / 33): 0 = bodies of 10, 9 and 8 rows, 1 = the one body of
+// 10 rows that every chunk ran before the row-count bodies, 2 = bodies of 10 and 9 rows only.
+template <int WPG, bool NT, bool SC1 = false, bool RIMG = false, bool STG = false, int BODIES = 0>
 __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const uint64_t* __restrict__ p_desc, const Chunk* __restrict__ p_chunks,
                                                             const uint8_t* __restrict__ p_src0, const uint8_t* __restrict__ p_src1,
                                                             uint8_t* __restrict__ p_out, unsigned long long* __restrict__ p_status,
@@ -129,14 +150,6 @@ __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const u
                                                             const uint64_t* __restrict__ p_rows_next = nullptr)
 {
     static_assert(!STG || (RIMG && WPG == 1), "staged descriptors: rows images, one wave per workgroup");
-    constexpr uint32_t ROWS = CHUNK_BYTES_WAVE / 1024u;              // 1 KiB rows of a chunk: all gathered before the first store
-    static_assert(ROWS <= 16u, "a lane's map bytes and record indices are packed four rows to a register");
-    constexpr uint32_t ND = (ROWS + 3u) / 4u;                        // map dwords per lane (4 * ND >= ROWS one-byte counters)
-    struct WaveLds {
-        uint32_t map32[64u * ND];                                    // one byte per 16-byte block: record covering its first byte
-        WRec rec[CHUNK_TASKS_WAVE + 4];                              // + sentinels
-        u32x4 patch[CHUNK_TASKS_WAVE + 1];                           // [t]: record t's own piece, then (owners) the parked tail of the block it starts in; [64]: scrap
-    };
     __shared__ __attribute__((aligned(16))) WaveLds s_all[WPG];
     __shared__ u32x4 s_mask[17];                                     // s_mask[j]: bytes >= j of a block
     __shared__ u32x4 s_one[17];                                      // s_one[j]: byte j of a block alone (16: none) -- where a replaced residue goes
@@ -214,7 +227,7 @@ __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const u
         s_one[jm] = o1;
     }
 #pragma unroll
-    for (uint32_t k = 0; k < ND; ++k) L.map32[ND * lane + k] = 0u;
+    for (uint32_t k = 0; k < WAVE_ND; ++k) L.map32[WAVE_ND * lane + k] = 0u;      // (the whole map, whichever body scans it)
     const uint64_t d = lane < n ? d_raw : 0ull;
 
     // ---- A: lane = descriptor -> one record ----
@@ -277,8 +290,49 @@ __global__ __launch_bounds__(64 * WPG, V2P_WAVE_OCC) void stitchw_kernel(const u
     //      block -- one gather per lane, unconditionally (a lane with nothing to fetch reads the dots): no branch, it flies under
     //      the map and the copy phase's look-ups.  What precedes the record in the block is the covering record's stream, which the
     //      copy phase gathers anyway; what follows it comes from the later records' own pieces. ----
+    //      (ISSUED at the head of the body below.  hipcc lays the bodies out one behind the other, so what is computed here for all of them
+    //      -- the gathered piece, or only its address -- lives THROUGH the ten-row body on the way to the others and was spilled to scratch:
+    //      the kernel has no register to spare.  So the address computed here is the ten-row body's alone, which comes first; the shorter
+    //      bodies work theirs out again from the lane's record in LDS.) ----
     constexpr bool PG = !(V2P_WAVE_ABLATE & 2);
-    const u32x4 g1 = wgather(PG && lane < n && (start & 15u) != 0u && bytes != 0u ? adj + (start & ~15u) : dots16, chk, 1u);
+    const uint64_t g1_addr = PG && lane < n && (start & 15u) != 0u && bytes != 0u ? adj + (start & ~15u) : dots16;
+
+    // ---- the rest in the body of the chunk's row count (block space: a ragged head counts).  A rows image cuts its chunks on 1 KiB rows
+    //      where 64 descriptors are full: a quarter of C3's chunks stop at 9 rows, an eighth at 8 or fewer, and a row that is not there
+    //      costs a look-up, a gather, a merge and a dropped store like any other.  A chunk of fewer than eight rows runs the eight-row body
+    //      (2.7 % of C3's chunks: no body of their own).  Wave-uniform (ptotal comes from v_readlane); no code follows the bodies, and every
+    //      wait inside a body is a counted one.  C3 whole: 6.92 -> 6.85 ms per execute; without the third body 6.87 (profiles/wave_rows_ab.json). ----
+    const uint32_t nrow = (ptotal + 1023u) >> 10;
+    if (BODIES != 1 && nrow < WAVE_ROWS) {
+        if (BODIES == 0 && nrow < WAVE_ROWS - 1u) { wave_rows<WAVE_ROWS - 2u, NT, SC1>(L, s_mask, s_one, lane, n, head, ptotal, nblk, dst, p_out, dots16, g1_addr, chk); return; }
+        wave_rows<WAVE_ROWS - 1u, NT, SC1>(L, s_mask, s_one, lane, n, head, ptotal, nblk, dst, p_out, dots16, g1_addr, chk);
+        return;
+    }
+    wave_rows<WAVE_ROWS, NT, SC1>(L, s_mask, s_one, lane, n, head, ptotal, nblk, dst, p_out, dots16, g1_addr, chk);
+}
+
+template <uint32_t R, bool NT, bool SC1>
+__device__ __forceinline__ void wave_rows(WaveLds& L, const u32x4* s_mask, const u32x4* s_one, const uint32_t lane_id, const uint32_t n, const uint32_t head,
+                                          const uint32_t ptotal, const uint32_t nblk, const uint64_t dst, uint8_t* __restrict__ p_out, const uint64_t dots16,
+                                          const uint64_t g1_addr, const WChk& chk)
+{
+    // (the shorter bodies derive their LDS addresses and block positions from their OWN copy of the lane index: what hipcc computes once
+    // before the branch for all bodies stays in registers through the ten-row body, which has none to spare -- it spilled a gathered row.
+    // The ten-row body itself takes the index as it is: there a copy is one more live register, and spilled as well)
+    uint32_t lane = lane_id;
+    if (R != WAVE_ROWS) asm volatile("" : "+v"(lane));
+    // ---- P, first half (see the kernel): the lane's own stream at the block its record starts in -- the first gather in the body's queue ----
+    u32x4 g1;
+    if constexpr (R == WAVE_ROWS) g1 = wgather(g1_addr, chk, 1u);
+    else {
+        constexpr bool PG = !(V2P_WAVE_ABLATE & 2);
+        const u32x4 t = reinterpret_cast<const u32x4*>(L.rec)[lane];
+        const uint32_t s0 = t[2] & 0xFFFFu, e0 = t[2] >> 16;         // (lanes past the last record hold a sentinel: they read the dots)
+        g1 = wgather(PG && lane < n && (s0 & 15u) != 0u && e0 != s0 ? ((uint64_t(t[1]) << 32) | t[0]) + (s0 & ~15u) : dots16, chk, 1u);
+    }
+    constexpr uint32_t ROWS = R;                                     // all gathered before the first store
+    constexpr uint32_t ND = (ROWS + 3u) / 4u;                        // map dwords per lane (4 * ND >= ROWS one-byte counters): lane l scans blocks [4 ND l, 4 ND (l + 1))
+    static_assert(ND <= WAVE_ND && ROWS <= WAVE_ROWS && 4u * ND >= ROWS, "the LDS tables are sized for a full chunk");
 
     // ---- C: block map = inclusive prefix sum of the marks; ROWS one-byte counters per lane (a chunk has at most 63 marks) ----
     {
@@ -459,6 +513,18 @@ hipError_t launch_stitch_wave(const StitchArgs& a, hipStream_t stream, bool nt, 
         a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, nullptr, nullptr)
 #define V2P_LWS(NTT, SCC) hipLaunchKernelGGL((stitchw_kernel<1, NTT, SCC, true, true>), dim3(tw ? (((nc + 7u) & ~7u) + 8u * tw) : nc), dim3(64), 0, stream, \
         a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, a.stage_cur, a.stage_next, a.rows_next)
+#ifdef V2P_BENCH_VARIANTS
+        // (A/B, v2p_bench_set_variant 32 / 33: the rows instances with the one body of 10 rows / with bodies of 10 and 9 rows only; "nt" and "sc1 nt" stores)
+#define V2P_LWB(SCC, STGG, BOD) hipLaunchKernelGGL((stitchw_kernel<1, true, SCC, true, STGG, BOD>), dim3(tw ? (((nc + 7u) & ~7u) + 8u * tw) : nc), dim3(64), 0, stream, \
+        a.desc, ch, a.src0, a.src1, a.out, a.status, a.dots, nc, a.n_desc, a.src0_len, a.src1_len, a.out_len, a.next_chunks, n_next, 0u, \
+        STGG ? a.stage_cur : nullptr, STGG ? a.stage_next : nullptr, STGG ? a.rows_next : nullptr)
+        if (a.rows && nt && (a.opt_wave_bodies == 1u || a.opt_wave_bodies == 2u)) {
+            const bool stg = a.stage_cur && c0 == 0u && nc == a.n_chunks, one = a.opt_wave_bodies == 1u;
+            if (stg) { if (a.store_sc1) { if (one) V2P_LWB(true, true, 1); else V2P_LWB(true, true, 2); } else { if (one) V2P_LWB(false, true, 1); else V2P_LWB(false, true, 2); } }
+            else { if (a.store_sc1) { if (one) V2P_LWB(true, false, 1); else V2P_LWB(true, false, 2); } else { if (one) V2P_LWB(false, false, 1); else V2P_LWB(false, false, 2); } }
+        } else
+#undef V2P_LWB
+#endif
         if (a.rows && a.stage_cur && c0 == 0u && nc == a.n_chunks) {      // (staged descriptors: the whole phase is one launch, row c of the buffer = chunk c)
             if (nt && a.store_sc1) V2P_LWS(true, true); else if (nt) V2P_LWS(true, false); else V2P_LWS(false, false);
         } else if (a.rows) { if (nt && a.store_sc1) V2P_LWR(true, true); else if (nt) V2P_LWR(true, false); else V2P_LWR(false, false); }

@@ -2325,6 +2325,8 @@ static hipError_t patch_execute(v2p_batch* b, hipStream_t stream)
 // v2p_set_launch_opts: variant 16 / 17 / 18 = how a context's phased wave images are launched (A/B switches: tools/phase_ab.py):
 // ONE launch for all phases / the read-ahead as kernels of its own / no read-ahead
 static uint32_t touch_of(uint32_t variant) { return variant == 16u ? 4u : (variant == 17u ? 2u : (variant == 18u ? 1u : 0u)); }
+// libv2p_bench.so's variants 32 / 33 (A/B): stitchw_kernel's one body of 10 rows for every chunk of a rows image / bodies of 10 and 9 rows only (chunks of at most 8 rows in the 9-row body)
+static uint32_t wave_bodies_of(uint32_t variant) { return variant == 32u ? 1u : (variant == 33u ? 2u : 0u); }
 
 // libv2p_bench.so's variant 19: the phases of a context's wave images in halves on two launch streams (launch_stitch: dual)
 static void dual_of(v2p_ctx* c, StitchArgs& a)
@@ -2424,6 +2426,7 @@ static hipError_t stitch_range(v2p_batch* b, uint64_t desc_bound, uint64_t chunk
                  b->d_out.ptr(), b->out_bytes, reinterpret_cast<unsigned long long*>(b->d_status.ptr())};
     a.opt_phase_bytes = c->launch_opts.phase_bytes; a.opt_phase_min_chunks = c->launch_opts.phase_min_chunks; a.opt_store_sc1 = c->launch_opts.store_sc1;
     a.opt_touch = touch_of(ctx_variant(c));
+    a.opt_wave_bodies = wave_bodies_of(ctx_variant(c));
     dual_of(c, a);
     a.img_desc = img_desc; a.img_bytes = img_bytes;
     const int hint = int(!(c->flags & V2P_FLAG_TEMPORAL)) | b->launch_hint;
@@ -3092,6 +3095,7 @@ static StitchArgs whole_table_args(const v2p_batch* b)
                  b->d_out.ptr(), b->out_bytes, reinterpret_cast<unsigned long long*>(b->d_status.ptr())};
     a.opt_phase_bytes = c->launch_opts.phase_bytes; a.opt_phase_min_chunks = c->launch_opts.phase_min_chunks; a.opt_store_sc1 = c->launch_opts.store_sc1;
     a.opt_touch = touch_of(ctx_variant(c));
+    a.opt_wave_bodies = wave_bodies_of(ctx_variant(c));
     a.img_desc = b->pad_image ? b->n_desc : 0;          // (the routing looks at the descriptors the image holds, not at the array's slots)
     return a;
 }
@@ -3794,7 +3798,7 @@ int v2p_set_launch_opts(v2p_ctx* c, const v2p_launch_opts* opts)
 }
 
 #ifdef V2P_BENCH_VARIANTS
-// libv2p_bench.so only (csrc/bench/v2p_bench.h): the A/B switches 16 .. 31 of the builders and launchers
+// libv2p_bench.so only (csrc/bench/v2p_bench.h): the A/B switches 16 .. 33 of the builders and launchers
 int v2p_bench_set_variant(v2p_ctx* c, uint32_t variant)
 {
     if (!c) return V2P_ERR_INVALID_ARG;
