@@ -56,6 +56,7 @@ extern "C" {
 #define V2P_ERR_NON_BYTE_CHAR   -8   /* a char > 0xFF cannot enter the 1-byte-per-residue batch image */
 #define V2P_ERR_UNSUPPORTED     -9
 #define V2P_ERR_STATE          -10   /* call sequence error (e.g. execute before finalize) */
+#define V2P_ERR_DIGEST_COLLISION -11 /* v2p_unique_add*: two records with equal key, length and digest hold different residues */
 
 /* engines.rs:15 */
 #define V2P_ENGINE_ST  0
@@ -381,6 +382,58 @@ int v2p_batch_bgzf(v2p_batch* b, uint64_t* z_bytes);
 int v2p_batch_bgzf_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len);
 /* copy member bytes [begin, begin+len) to the host */
 int v2p_batch_bgzf_download(v2p_batch* b, uint64_t begin, uint64_t len, uint8_t* out);
+
+/* ---- cohort-wide distinct records: the arena deduplicated on the device (vcf2prot_amd/csrc/unique_records.hip) -------------
+ * A RECORD is one transcript entry of one haplotype of a v2p_txstream: its RESIDUES are the tx_res_len[t] bytes of its arena range
+ * behind the header text (if tx_header_len[t] != 0) and in front of the closing line feed; its KEY is (tx_proteome_off[t], tx_ref_len[t]).
+ * Two records belong to one CLASS iff keys and residues are equal, byte for byte (the header takes no part: _1 and _2 differ).  Classes are
+ * numbered 0, 1, 2, ... in order of first occurrence -- record order, haplotype-major as the stream has it, across successive adds -- and the
+ * result (ids, counts, first records, emitted bytes) is the same from run to run: nothing depends on the order in which atomics arrive.
+ * The rule in ten lines of Python: tests/unique_rule.py.
+ * A set keeps, per class, key, length, a 128-bit digest, the number of records and the global index of the first one, and a copy of the
+ * residues (+ '\n') in a store of its own: the arena a record came from may be recycled as soon as the add returns.
+ * The digest of residues b[0 .. len): D_j = sum_k M_j(k) * W_j,k (mod 2^64), j = 0, 1, where W_0,k = sum over the bytes i of word k
+ * (i div 8 == k, i < len) of (b[i] + 1) * 2^(8 * (i mod 8)) -- the word-wise sum of v2p_batch_digests -- W_1,k is the same word taken
+ * big-endian, (b[i] + 1) * 2^(8 * (7 - i mod 8)), so that a byte which reaches few bits of one sum reaches all of the other, and the
+ * multipliers are forced odd: M_0(k) = splitmix64(k) | 1, M_1(k) = splitmix64(k ^ 0x5851F42D4C957F2D) | 1, splitmix64 as in
+ * v2p_batch_digests.  len == 0: (0, 0).
+ * Equal digests never merge records on their own: every record is compared with its class's residues, and a difference is
+ * V2P_ERR_DIGEST_COLLISION (v2p_last_error_index: the smallest record whose residues differ from its class's), the set left as it was.
+ * Every failed call leaves the set unchanged. */
+typedef struct v2p_unique v2p_unique;
+typedef struct {
+    uint64_t n_records, n_new_classes, n_classes, store_bytes, table_slots;   /* of this add; of the set behind it */
+    float ms_digest, ms_insert, ms_verify, ms_commit;                         /* HIP events on the context's stream: record ranges + digests; table
+                                                                               * insert; compare + representative flags + their scans; store copy + resolve */
+} v2p_unique_info;
+/* expected_classes sizes the first hash table (twice as many slots, a power of two; 0 / 1: the smallest, 64) -- table, class arrays and
+ * store grow by doubling between adds */
+int  v2p_unique_create(v2p_ctx* ctx, uint64_t expected_classes, v2p_unique** out);
+void v2p_unique_destroy(v2p_unique* u);
+/* every record of an EXECUTED batch whose arena has the layout of stream s (a batch built from s, or a host-built one of the same stream):
+ * record offsets come from the batch's own haplotype offsets and the stream's tx_res_len / tx_header_len.  Waits for the context's stream.
+ * class_of (optional): [n_tx] host, the class of every record.  V2P_ERR_STATE: a batch that was never executed or is orphaned;
+ * V2P_ERR_INVALID_ARG: the stream's out_bytes or haplotype count is not the batch's, or a record range leaves the arena (with the record). */
+int  v2p_unique_add(v2p_unique* u, v2p_batch* b, const v2p_stream* s, uint32_t* class_of, v2p_unique_info* info);
+/* The same on caller-owned device memory: record r is d_arena[d_rec_begin[r], + d_rec_len[r]), its key d_rec_key[2 r], [2 r + 1].
+ * d_digest ([2 n], optional) REPLACES the computed digests (tests force collisions with it).  d_arena may have any alignment (aligned
+ * 16-byte blocks inside a record are read with one load) and no byte outside d_arena[0, arena_bytes) is read: a record whose range
+ * leaves it is V2P_ERR_INVALID_ARG with its index.  The call does not look into device memory before launching, so two things are the
+ * CALLER'S obligation and undefined if broken: the four arrays hold n (2 n) readable entries, and d_rec_len[r] < 2^32 - 1.  n < 2^32 - 1.
+ * class_of (optional): [n] host. */
+int  v2p_unique_add_records(v2p_unique* u, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_rec_begin, const uint32_t* d_rec_len,
+                            const uint64_t* d_rec_key, uint64_t n, const uint64_t* d_digest, uint32_t* class_of, v2p_unique_info* info);
+/* where the last call, a successful v2p_unique_add, found its records (tests): rec_begin [n], rec_len [n] host, n = that add's n_records;
+ * V2P_ERR_STATE behind any other call that adds */
+int  v2p_unique_last_ranges(v2p_unique* u, uint64_t* rec_begin, uint32_t* rec_len, uint64_t n);
+int  v2p_unique_counts(const v2p_unique* u, uint64_t* n_classes, uint64_t* n_records, uint64_t* store_bytes);
+/* per class, host arrays of n_classes entries (key: 2 per class); any pointer may be NULL */
+int  v2p_unique_classes(v2p_unique* u, uint64_t* key, uint32_t* len, uint64_t* count, uint64_t* first_record);
+/* File-ready text: for i = 0 .. n, headers[header_begin[i], header_begin[i + 1]) (host; may be empty), the residues of class order[i], '\n',
+ * gathered into ONE device buffer and copied to out (host) in one D2H.  out_len must be the sum of those lengths.  V2P_ERR_INVALID_ARG with
+ * the index: an order entry >= n_classes, a descending header_begin; with index n: a wrong out_len. */
+int  v2p_unique_emit(v2p_unique* u, const uint32_t* order, uint64_t n, const uint8_t* headers, const uint64_t* header_begin,
+                     uint8_t* out, uint64_t out_len);
 
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned

@@ -1,11 +1,15 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
 CPU code and is refused.
 
 -f takes the VCF as text or compressed: a .vcf.gz as bgzip or `bcftools -O z` writes it (BGZF) is inflated on the GPU, member by member;
-any other gzip is inflated on the host first."""
+any other gzip is inflated on the host first.
+
+--write_unique (long option only, not the reference's) writes the cohort's NON-REDUNDANT proteome instead of one FASTA per proband: every
+slice's result stays on the GPU and is deduplicated there (v2p_unique_add), <outdir>/unique_proteins.fasta holds each distinct protein once
+(`>{transcript}_v{k} n={haplotypes that carry it}`) and <outdir>/unique_proteins.tsv which variant k each proband's two haplotypes have."""
 import argparse
 import os
 import subprocess
@@ -29,8 +33,13 @@ def main() -> int:
     ap.add_argument("--device-tables", action="store_true", help="build the file-wide consequence tables on the GPU too, from the resident VCF text (same bytes; opt-in)")
     ap.add_argument("--device-index", action="store_true", help="build the VCF record index on the GPU too, from the resident VCF text (same bytes; opt-in)")
     ap.add_argument("--device-tasks", action="store_true", help="generate instructions and Task vectors (steps 4a / 4b) on the GPU too (same bytes; opt-in)")
+    ap.add_argument("--write_unique", action="store_true",
+                    help="write unique_proteins.fasta / .tsv (each distinct protein once, deduplicated on the GPU) instead of one FASTA per proband; not with -c / --write_bgzf")
+    ap.add_argument("--slice-kb", type=int, default=0, help="cut the cohort into slices of about this many KiB of FASTA text (default: 256 MiB; for tests)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
+    if a.write_unique and (a.write_compressed or a.write_bgzf):          # (before anything is built or created)
+        ap.error("--write_unique writes no per-proband file: it cannot be combined with -c / --write_compressed or --write_bgzf")
     from .engine import Engine
     if Engine.from_str(a.engine) is not Engine.GPU:                      # engines.rs:17-29
         sys.exit("only -g gpu is implemented here; st / mt are the reference's CPU engines")
@@ -60,6 +69,10 @@ def main() -> int:
         cmd.append("--device-tables")
     if a.device_index:
         cmd.append("--device-index")
+    if a.write_unique:
+        cmd.append("--unique")
+    if a.slice_kb > 0:
+        cmd += ["--slice-kb", str(a.slice_kb)]
     return subprocess.run(cmd).returncode
 
 

@@ -17,10 +17,11 @@ V2P_OK = 0
 ERR_NAMES = {
     0: "V2P_OK", -1: "V2P_ERR_INVALID_ARG", -2: "V2P_ERR_HIP", -3: "V2P_ERR_BAD_CODE", -4: "V2P_ERR_RES_OOB",
     -5: "V2P_ERR_SRC_OOB", -6: "V2P_ERR_NOT_CONTIGUOUS", -7: "V2P_ERR_NOT_CANONICAL", -8: "V2P_ERR_NON_BYTE_CHAR",
-    -9: "V2P_ERR_UNSUPPORTED", -10: "V2P_ERR_STATE",
+    -9: "V2P_ERR_UNSUPPORTED", -10: "V2P_ERR_STATE", -11: "V2P_ERR_DIGEST_COLLISION",
 }
 V2P_ERR_INVALID_ARG, V2P_ERR_HIP, V2P_ERR_BAD_CODE, V2P_ERR_RES_OOB, V2P_ERR_SRC_OOB = -1, -2, -3, -4, -5
 V2P_ERR_NOT_CONTIGUOUS, V2P_ERR_NOT_CANONICAL, V2P_ERR_NON_BYTE_CHAR, V2P_ERR_UNSUPPORTED, V2P_ERR_STATE = -6, -7, -8, -9, -10
+V2P_ERR_DIGEST_COLLISION = -11
 V2P_FLAG_DEBUG_GPU, V2P_FLAG_TEMPORAL, V2P_FLAG_RESULT_ORDER = 1, 2, 4
 
 
@@ -108,6 +109,14 @@ HIP_API = {
     "v2p_bgzf_workspace_bytes": (c_uint64, [c_uint64, c_uint64]),
     "v2p_bgzf_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p]),
     "v2p_bgzf_inflate_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "v2p_unique_create": (c_int, [c_void_p, c_uint64, POINTER(c_void_p)]),
+    "v2p_unique_destroy": (None, [c_void_p]),
+    "v2p_unique_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_unique_add_records": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "v2p_unique_last_ranges": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
+    "v2p_unique_counts": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_unique_classes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_unique_emit": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64]),
 }
 
 _hip = None
@@ -118,6 +127,12 @@ class OneShotInfo(ctypes.Structure):
     """v2p_oneshot_info (include/vcf2prot_hip.h)"""
     _fields_ = [("kernel", ctypes.c_int32), ("n_slices", ctypes.c_uint32), ("total_ms", ctypes.c_float), ("build_ms", ctypes.c_float),
                 ("call_wall_ms", ctypes.c_double), ("slice_build_ms", ctypes.c_float * 32), ("tables_ms", ctypes.c_float)]
+
+
+class UniqueInfo(ctypes.Structure):
+    """v2p_unique_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("n_records", c_uint64), ("n_new_classes", c_uint64), ("n_classes", c_uint64), ("store_bytes", c_uint64), ("table_slots", c_uint64),
+                ("ms_digest", ctypes.c_float), ("ms_insert", ctypes.c_float), ("ms_verify", ctypes.c_float), ("ms_commit", ctypes.c_float)]
 
 
 class Routing(ctypes.Structure):

@@ -366,7 +366,7 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index, bool int_map, bool device_int_map)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index, bool int_map, bool device_int_map, bool unique)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -809,7 +809,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     };
     // ---- a slice the rows builders refuse (a 1 KiB row with more than 1 024 descriptors): the HOST builder takes any stream (step 5 on the
     // host: v2p_batch_begin_haplotype / _add_transcript / _end_haplotype + v2p_batch_finalize), on a batch of its own; its arena is downloaded whole ----
-    auto blocking_slice = [&](TxStreamHost& tx, std::vector<uint8_t>& bytes, std::vector<uint64_t>& hob) {
+    auto host_built_batch = [&](TxStreamHost& tx) {
         v2p_txstream st = tx.view();
         v2p_batch* fb = nullptr;
         chk(v2p_batch_create(ctx.raw(), &fb));
@@ -828,10 +828,94 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         chk(v2p_batch_finalize(fb));
         chk(v2p_batch_execute(fb));
         chk(v2p_batch_sync(fb));
-        batch_result(chk, fb, st.n_haps, bgzf, bytes, hob);
+        return fb;
+    };
+    auto blocking_slice = [&](TxStreamHost& tx, std::vector<uint8_t>& bytes, std::vector<uint64_t>& hob) {
+        v2p_batch* fb = host_built_batch(tx);
+        batch_result(chk, fb, tx.hap_tx_begin.size() - 1, bgzf, bytes, hob);
         v2p_batch_destroy(fb);
     };
     uint64_t n_slices = 0, n_fallback = 0;
+    // ---- --unique: every slice's executed arena goes into ONE distinct-record set on the device (v2p_unique_add) -- no arena is downloaded,
+    // no per-proband file written; behind the last slice the set's classes become unique_proteins.fasta (bytes gathered on the device:
+    // v2p_unique_emit) and the records' classes unique_proteins.tsv ----
+    v2p_unique* uq = nullptr;
+    if (unique) chk(v2p_unique_create(ctx.raw(), 0, &uq));
+    struct UniqueGuard { v2p_unique*& u; ~UniqueGuard() { if (u) { v2p_unique_destroy(u); u = nullptr; } } } unique_guard{uq};
+    std::vector<uint32_t> u_class;                                   // the class of every record, slice after slice
+    std::vector<uint64_t> u_hap_begin{0};                            // the first record of every haplotype
+    v2p_unique_info u_sum{};
+    uint64_t u_fasta_bytes = 0, u_tsv_bytes = 0;
+    // an executed batch laid out by the resident stream rs; hap_tx[h]: the transcripts of its haplotype h
+    auto unique_add = [&](v2p_batch* eb, const v2p_stream* rs, const std::vector<uint64_t>& hap_tx) {
+        uint64_t n_tx = 0;
+        chk(v2p_stream_counts(rs, nullptr, &n_tx, nullptr, nullptr));
+        const size_t at = u_class.size();
+        u_class.resize(at + n_tx + 1);
+        v2p_unique_info inf{};
+        chk(v2p_unique_add(uq, eb, rs, u_class.data() + at, &inf));
+        u_class.resize(at + n_tx);
+        for (uint64_t n : hap_tx) u_hap_begin.push_back(u_hap_begin.back() + n);
+        if (u_hap_begin.back() != u_class.size()) { std::fprintf(stderr, "panicked: a slice's stream holds another number of records than its haplotypes\n"); std::exit(101); }
+        u_sum.n_records += inf.n_records; u_sum.n_classes = inf.n_classes; u_sum.store_bytes = inf.store_bytes; u_sum.table_slots = inf.table_slots;
+        u_sum.ms_digest += inf.ms_digest; u_sum.ms_insert += inf.ms_insert; u_sum.ms_verify += inf.ms_verify; u_sum.ms_commit += inf.ms_commit;
+    };
+    auto write_unique = [&]() -> bool {
+        const auto tw = clk::now();
+        uint64_t nc = 0;
+        chk(v2p_unique_counts(uq, &nc, nullptr, nullptr));
+        std::vector<uint64_t> key(2 * nc + 2), count(nc + 1), first(nc + 1);
+        std::vector<uint32_t> len(nc + 1);
+        chk(v2p_unique_classes(uq, key.data(), len.data(), count.data(), first.data()));
+        // a class's transcript: its key is the transcript's place in the resident proteome
+        std::map<std::pair<uint64_t, uint64_t>, const std::string*> by_key;
+        for (const auto& kv : all) by_key.emplace(std::make_pair(kv.second.off, kv.second.len), &kv.first);
+        std::vector<const std::string*> cname(nc);
+        std::vector<uint32_t> order(nc), k_of(nc, 0);
+        for (uint64_t c = 0; c < nc; ++c) {
+            const auto it = by_key.find(std::make_pair(key[2 * c], key[2 * c + 1]));
+            if (it == by_key.end()) { std::fprintf(stderr, "panicked: a class whose key is no transcript of the reference\n"); return false; }
+            cname[c] = it->second; order[c] = uint32_t(c);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return *cname[a] < *cname[b]; });   // by name (bytewise), then class id
+        std::string hdr;
+        std::vector<uint64_t> hdr_begin{0};
+        uint64_t out_len = 0;
+        for (uint64_t i = 0; i < nc; ++i) {
+            const uint32_t c = order[i];
+            k_of[c] = (i && *cname[order[i - 1]] == *cname[c]) ? k_of[order[i - 1]] + 1 : 1;
+            hdr += ">" + *cname[c] + "_v" + std::to_string(k_of[c]) + " n=" + std::to_string(count[c]) + "\n";
+            hdr_begin.push_back(hdr.size());
+            out_len += len[c] + 1u;
+        }
+        out_len += hdr.size();
+        std::vector<uint8_t> text(out_len + 1);
+        chk(v2p_unique_emit(uq, order.data(), nc, reinterpret_cast<const uint8_t*>(hdr.data()), hdr_begin.data(), text.data(), out_len));
+        std::string tsv = "#proband\ttranscript\thap1\thap2\n";
+        for (uint64_t s = 0; s < S; ++s) {
+            uint64_t nb, nl;
+            v2p_vcf_index_sample(idx, s, &nb, &nl);
+            std::map<std::string, std::pair<uint32_t, uint32_t>> row;     // transcripts in name order
+            for (int h = 0; h < 2; ++h)
+                for (uint64_t r = u_hap_begin[2 * s + h]; r < u_hap_begin[2 * s + h + 1]; ++r) {
+                    auto& cell = row[*cname[u_class[r]]];
+                    (h ? cell.second : cell.first) = k_of[u_class[r]];
+                }
+            for (const auto& kv : row)
+                tsv += vcf.substr(nb, nl) + "\t" + kv.first + "\t" + std::to_string(kv.second.first) + "\t" + std::to_string(kv.second.second) + "\n";
+        }
+        const std::string base = std::string(outdir) + "/unique_proteins";
+        std::ofstream ff(base + ".fasta", std::ios::binary), ft(base + ".tsv", std::ios::binary);
+        if (!ff || !ft) { std::fprintf(stderr, "Could not create %s.fasta / .tsv\n", base.c_str()); return false; }
+        ff.write(reinterpret_cast<const char*>(text.data()), std::streamsize(out_len));
+        ft.write(tsv.data(), std::streamsize(tsv.size()));
+        ff.close(); ft.close();
+        if (!ff || !ft) { std::fprintf(stderr, "Could not write %s.fasta / .tsv\n", base.c_str()); return false; }
+        u_fasta_bytes = out_len; u_tsv_bytes = tsv.size();
+        written += out_len + tsv.size();
+        t_write_acc += since(tw);
+        return true;
+    };
     // the two lines every run ends with; tasks_json says where steps 4a / 4b ran
     auto report = [&](const std::string& tasks_json) {
         char stats_seconds[48] = "";
@@ -862,6 +946,11 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
                     tms[0], tms[1], tms[2], tms[3], tms[4], tms[5], tms[6], tinf.name_slots, tinf.ident_slots);
         std::printf(", \"index\": {\"path\": \"%s\", \"ms_lines\": %.3f, \"ms_count\": %.3f, \"ms_scan\": %.3f, \"ms_emit\": %.3f, \"ms_download\": %.3f, "
                     "\"s_context_and_upload\": %.4f}", device_index ? "device" : "host", xms[0], xms[1], xms[2], xms[3], xms[4], t_resident);
+        if (unique)
+            std::printf(", \"unique\": {\"records\": %llu, \"classes\": %llu, \"store_bytes\": %llu, \"table_slots\": %llu, \"fasta_bytes\": %llu, \"tsv_bytes\": %llu, "
+                        "\"ms_digest\": %.3f, \"ms_insert\": %.3f, \"ms_verify\": %.3f, \"ms_commit\": %.3f}", (unsigned long long)u_sum.n_records,
+                        (unsigned long long)u_sum.n_classes, (unsigned long long)u_sum.store_bytes, (unsigned long long)u_sum.table_slots,
+                        (unsigned long long)u_fasta_bytes, (unsigned long long)u_tsv_bytes, u_sum.ms_digest, u_sum.ms_insert, u_sum.ms_verify, u_sum.ms_commit);
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     };
     if (tasks_on_device) {
@@ -909,14 +998,19 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
                 tx.alt.assign(st.n_alt + 64, 0); tx.padded = true;
                 st = tx.view();
                 chk(v2p_stream_download(rs, &st));
-                blocking_slice(tx, bytes, hob);
+                if (unique) {                                                  // (the resident stream lays the host-built arena out as well)
+                    v2p_batch* fb = host_built_batch(tx);
+                    unique_add(fb, rs, std::vector<uint64_t>(h_tx.begin() + 2 * s0, h_tx.begin() + 2 * sm + 2));
+                    v2p_batch_destroy(fb);
+                } else blocking_slice(tx, bytes, hob);
                 ++n_fallback;
             } else {
                 chk(rc);
-                batch_result(chk, b, 2 * (sm + 1 - s0), bgzf, bytes, hob);
+                if (unique) unique_add(b, rs, std::vector<uint64_t>(h_tx.begin() + 2 * s0, h_tx.begin() + 2 * sm + 2));
+                else batch_result(chk, b, 2 * (sm + 1 - s0), bgzf, bytes, hob);
             }
             t_back += since(te);
-            if (!write_probands(s0, sm + 1, bytes.data(), hob.data())) return 101;
+            if (!unique && !write_probands(s0, sm + 1, bytes.data(), hob.data())) return 101;
             chk(v2p_batch_reset(b));
             v2p_stream_destroy(rs);
             ++n_slices; s0 = sm + 1; acc = 0;
@@ -925,6 +1019,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         v2p_decode_tasks_timing(dec, &tms[0], &tms[1], &tms[2], &tms[3]);
         v2p_decode_destroy(dec);
         v2p_csq_tables_destroy(tb);
+        if (unique && !write_unique()) return 101;
         t_build = t_count + t_emit; t_exec = t_run; t_write = t_back + t_write_acc;
         char tj[512];
         std::snprintf(tj, sizeof tj, "{\"path\": \"device\", \"items\": %llu, \"transcripts\": %llu, \"tasks\": %llu, \"alt_bytes\": %llu, \"slice_bytes\": %llu, "
@@ -940,7 +1035,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     // ---- the pipeline ----
     constexpr uint32_t SLOTS = 3;
     v2p_pipeline* pipe = nullptr;
-    if (!host_build) chk(v2p_pipeline_create(ctx.raw(), SLOTS, &pipe));
+    if (!host_build && !unique) chk(v2p_pipeline_create(ctx.raw(), SLOTS, &pipe));
     // (every way out of this function -- a transcript the reference would panic on, a full disk -- ends the pipeline's runner before the
     // context it works on goes)
     struct PipeGuard { v2p_pipeline*& p; ~PipeGuard() { if (p) { v2p_pipeline_destroy(p); p = nullptr; } } } pipe_guard{pipe};
@@ -968,6 +1063,30 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
     uint64_t slice_s0 = 0;
     auto flush = [&](uint64_t s1) -> bool {                      // probands [slice_s0, s1) are complete: off they go
         if (s1 == slice_s0) return true;
+        if (unique) {
+            // --unique: the slice is uploaded, built and executed in one call, waited for, and its arena added to the set where it lies
+            v2p_txstream st = txs_p->view();
+            std::vector<uint64_t> hap_tx;
+            for (size_t h = 0; h + 1 < txs_p->hap_tx_begin.size(); ++h) hap_tx.push_back(txs_p->hap_tx_begin[h + 1] - txs_p->hap_tx_begin[h]);
+            v2p_stream* rs = nullptr;
+            chk(v2p_stream_upload(ctx.raw(), &st, &rs));
+            int rc = v2p_batch_build_and_execute(b, rs, 0, 0);
+            if (rc == V2P_OK) rc = v2p_batch_sync(b);
+            if (rc == V2P_ERR_UNSUPPORTED) {                                   // a slice the rows builders refuse: the host builder, as without the option
+                v2p_batch* fb = host_built_batch(*txs_p);
+                unique_add(fb, rs, hap_tx);
+                v2p_batch_destroy(fb);
+                ++n_fallback;
+            } else {
+                chk(rc);
+                unique_add(b, rs, hap_tx);
+            }
+            chk(v2p_batch_reset(b));
+            v2p_stream_destroy(rs);
+            txs_p.reset(new TxStreamHost());
+            slice_s0 = s1; ++n_slices;
+            return true;
+        }
         if (inflight.size() == SLOTS) { if (!finish(inflight.front())) return false; inflight.erase(inflight.begin()); }
         v2p_txstream st = txs_p->view();
         uint32_t t = 0;
@@ -1059,6 +1178,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         inflight.clear();
         v2p_pipeline_destroy(pipe);
         pipe = nullptr;
+        if (unique && !write_unique()) return 101;
         t_exec = since(t0) - (t_write_acc - w0); t0 = clk::now();
     }
     t_write = host_build ? since(t0) : t_write_acc;
@@ -1165,7 +1285,7 @@ static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
-        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, int_map = false, device_int_map = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
+        bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, int_map = false, device_int_map = false, unique = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
         uint64_t slice_mb = 256;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
@@ -1181,9 +1301,14 @@ int main(int argc, char** argv)
             stats |= !std::strcmp(argv[i], "-s") || !std::strcmp(argv[i], "--stats");
             int_map |= !std::strcmp(argv[i], "-i") || !std::strcmp(argv[i], "--write_int_map");
             device_int_map |= !std::strcmp(argv[i], "--device-int-map");
+            unique |= !std::strcmp(argv[i], "--unique");
         }
         if (bgzf && compressed) { std::fprintf(stderr, "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one\n"); return 2; }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index, int_map, device_int_map); }
+        if (unique && (compressed || bgzf || host_build)) {
+            std::fprintf(stderr, "usage: --unique writes unique_proteins.fasta and unique_proteins.tsv from the device's record set, no per-proband file: it cannot be combined with -c, --bgzf or --host-build\n");
+            return 2;
+        }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index, int_map, device_int_map, unique); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

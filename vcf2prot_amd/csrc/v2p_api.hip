@@ -2193,6 +2193,19 @@ void stream_born_drop(v2p_stream* st)
     delete st;
 }
 
+void batch_arena_view(const ::v2p_batch* b, BatchArenaView* v)
+{
+    *v = BatchArenaView{b->ctx, b->d_out.ptr(), b->out_bytes, b->n_haps, reinterpret_cast<const unsigned long long*>(b->d_hap.ptr()),
+                        b->finalized && b->executed, b->orphaned};
+}
+
+void stream_record_view(const ::v2p_stream* s, StreamRecordView* v)
+{
+    const DevStreamView& d = s->v;
+    *v = StreamRecordView{s->ctx, d.n_haps, d.n_tx, s->out_bytes, reinterpret_cast<const unsigned long long*>(d.hap_tx_begin),
+                          reinterpret_cast<const unsigned long long*>(d.tx_proteome_off), d.tx_ref_len, d.tx_res_len, d.fasta ? d.tx_header_len : nullptr};
+}
+
 int ctx_check_transcript(v2p_ctx* c, uint64_t proteome_off, uint32_t ref_len, uint64_t header_off, uint32_t header_len, std::string* why)
 {
     if (proteome_off + ref_len > c->proteome_len || proteome_off + ref_len < proteome_off) { *why = "transcript outside the resident proteome"; return V2P_ERR_SRC_OOB; }

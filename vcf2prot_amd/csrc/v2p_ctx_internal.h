@@ -8,6 +8,7 @@
 
 struct v2p_ctx;
 struct v2p_stream;
+struct v2p_batch;
 
 namespace v2p {
 hipStream_t ctx_stream(v2p_ctx* c);
@@ -31,6 +32,15 @@ void stream_born_drop(v2p_stream* st);
 // what the host checks of a transcript before a stream may name it: inside the resident proteome, its record header inside the header table
 // and ending in a line feed.  Returns a V2P_ERR_* code and says why.
 int ctx_check_transcript(v2p_ctx* c, uint64_t proteome_off, uint32_t ref_len, uint64_t header_off, uint32_t header_len, std::string* why);
+
+// What the distinct-record set (unique_records.hip) reads of a batch and of a resident stream; both are called with the context locked.
+struct BatchArenaView { v2p_ctx* ctx; const uint8_t* arena; uint64_t out_bytes, n_haps; const unsigned long long* hap_out_begin; bool executed, orphaned; };
+struct StreamRecordView {
+    v2p_ctx* ctx; uint64_t n_haps, n_tx, out_bytes;
+    const unsigned long long *hap_tx_begin, *tx_proteome_off; const uint32_t *tx_ref_len, *tx_res_len, *tx_header_len;   // tx_header_len: nullptr for plain tapes
+};
+void batch_arena_view(const ::v2p_batch* b, BatchArenaView* v);
+void stream_record_view(const ::v2p_stream* s, StreamRecordView* v);
 
 // V2P_DEBUG_POISON=1 (a debugging aid like the reference's DEBUG_* switches; read once): every device buffer is filled with 0xA5 whenever a
 // call (re)sizes it -- also when the allocation is reused -- so that nothing can lean on what fresh or recycled memory happens to hold

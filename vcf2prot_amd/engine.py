@@ -10,6 +10,7 @@ own tests (paths under /root/reference/src/data_structures/InternalRep):
   ``Engine.ST``/``Engine.MT`` are NOT implemented here: this package is the gpu
   plugin only, the CPU engines stay in the Rust host.
 * ``Context`` / ``Batch`` -- thin owners of ``v2p_ctx`` / ``v2p_batch``.
+* ``UniqueSet`` -- owner of a ``v2p_unique``: the distinct records of the arenas added to it (not the reference's: ``--write_unique``).
 
 Error behaviour: the reference panics (process abort); here a ``V2PError`` is
 raised with the same condition (bounds, stream code, contiguity under DEBUG_GPU).
@@ -507,6 +508,81 @@ class Batch:
 
 
 _default_ctx: Optional[Context] = None
+
+
+class UniqueSet:
+    """One ``v2p_unique``: the distinct records (equal transcript key and residues) of every arena added to it, deduplicated on the device;
+    class ids follow first occurrence (the rule: tests/unique_rule.py)."""
+
+    def __init__(self, ctx: Context, expected_classes: int = 0):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.v2p_unique_create(ctx._h, expected_classes, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._lib.v2p_unique_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _info(info: "N.UniqueInfo") -> dict:
+        return {k: getattr(info, k) for k, _ in N.UniqueInfo._fields_}
+
+    def add(self, batch: "Batch", rs: "ResidentStream") -> Tuple[np.ndarray, dict]:
+        """v2p_unique_add: every record of an executed batch laid out by `rs`; returns (class_of [n_tx], info)."""
+        class_of = np.zeros(rs.counts()["n_tx"] + 1, np.uint32)
+        info = N.UniqueInfo()
+        self.ctx._check(self._lib.v2p_unique_add(self._h, batch._h, rs._h, class_of.ctypes.data, ctypes.byref(info)))
+        return class_of[:-1], self._info(info)
+
+    def add_records(self, d_arena: int, arena_bytes: int, d_rec_begin: int, d_rec_len: int, d_rec_key: int, n: int, d_digest: int = 0) -> Tuple[np.ndarray, dict]:
+        """v2p_unique_add_records on raw device pointers (ints)."""
+        class_of = np.zeros(n + 1, np.uint32)
+        info = N.UniqueInfo()
+        self.ctx._check(self._lib.v2p_unique_add_records(self._h, d_arena or None, arena_bytes, d_rec_begin or None, d_rec_len or None, d_rec_key or None, n,
+                                                         d_digest or None, class_of.ctypes.data, ctypes.byref(info)))
+        return class_of[:-1], self._info(info)
+
+    def last_ranges(self, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        begin, length = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint32)
+        self.ctx._check(self._lib.v2p_unique_last_ranges(self._h, begin.ctypes.data, length.ctypes.data, n))
+        return begin[:-1], length[:-1]
+
+    def counts(self) -> Dict[str, int]:
+        v = [ctypes.c_uint64() for _ in range(3)]
+        self.ctx._check(self._lib.v2p_unique_counts(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("n_classes", "n_records", "store_bytes"), (int(x.value) for x in v)))
+
+    def classes(self) -> Dict[str, np.ndarray]:
+        """v2p_unique_classes: key [n, 2], len, count, first_record per class."""
+        n = self.counts()["n_classes"]
+        key, length = np.zeros((n + 1, 2), np.uint64), np.zeros(n + 1, np.uint32)
+        count, first = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        self.ctx._check(self._lib.v2p_unique_classes(self._h, key.ctypes.data, length.ctypes.data, count.ctypes.data, first.ctypes.data))
+        return {"key": key[:n], "len": length[:n], "count": count[:n], "first_record": first[:n]}
+
+    def emit(self, order, headers: Sequence[bytes] = (), out_len: Optional[int] = None) -> bytes:
+        """v2p_unique_emit: header i (none: empty headers), the residues of class order[i], a line feed -- for every i, as one text."""
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        n = int(order.size)
+        headers = list(headers) if len(headers) else [b""] * n
+        hb = np.zeros(n + 1, np.uint64)
+        hb[1:] = np.cumsum([len(h) for h in headers], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(headers) + b"\0", np.uint8)
+        if out_len is None:
+            lens = self.classes()["len"]
+            out_len = int(hb[-1]) + sum(int(lens[c]) + 1 for c in order)
+        out = np.zeros(out_len + 1, np.uint8)
+        self.ctx._check(self._lib.v2p_unique_emit(self._h, order.ctypes.data, n, blob.ctypes.data, hb.ctypes.data, out.ctypes.data, out_len))
+        return out[:out_len].tobytes()
 
 
 def default_context() -> Context:
