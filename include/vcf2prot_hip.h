@@ -353,6 +353,20 @@ int v2p_batch_counts(const v2p_batch* b, uint64_t* n_haps, uint64_t* n_desc, uin
  * v2p_batch_download_image has no descriptors or chunks to hand out, v2p_batch_counts reports pieces and tiles in their place), bit 4 = the batch holds RESIDENT descriptor
  * rows of its image (a wave image that has been executed again) and the next v2p_batch_execute runs from them */
 int v2p_batch_image_form(const v2p_batch* b);
+/* what the last one-pass build of the batch did (diagnostics, tests; read-only): kernel 0 = the batch holds no image of the one-pass
+ * builder.  Two environment variables are test hooks of that builder, read at every build: V2P_ROWS_K = 1 .. 64 takes the place of the
+ * tile size the builder picks from the stream's statistics (a choice of speed: every K gives the same image), V2P_ROWS_SRC64 makes wave
+ * and dense images run the parse's 64-bit source instance whatever the size of the resident reference. */
+typedef struct {
+    int32_t  kernel;             /* 6 / 7: a wave / dense rows image; 9: a tile image; 0: none                                      */
+    uint32_t K;                  /* transcripts per tile of the parse                                                               */
+    uint64_t n_tiles;
+    uint32_t two_pass;           /* 1: a tile overflowed its 256 slots of the padded array (or there was no room for it): count, scan, write */
+    uint32_t cut_emit_pass;      /* 1: a 640-row segment held more chunks than its padded slots: the cutter's emitting pass ran      */
+    uint32_t fell_back;          /* 1: v2p_batch_build_and_execute built in one piece after all (see there)                         */
+    uint32_t src_bits;           /* 32 / 64: the source arithmetic of the parse that wrote the descriptors                          */
+} v2p_build_info;
+int v2p_batch_build_info(const v2p_batch* b, v2p_build_info* info);
 /* result range of haplotype h inside the arena */
 int v2p_batch_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len);
 /* copy arena bytes [begin, begin+len) to the host (1 byte per residue) */

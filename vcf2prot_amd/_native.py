@@ -79,6 +79,7 @@ HIP_API = {
     "v2p_batch_execute": (c_int, [c_void_p]),
     "v2p_batch_sync": (c_int, [c_void_p]),
     "v2p_batch_image_form": (c_int, [c_void_p]),
+    "v2p_batch_build_info": (c_int, [c_void_p, c_void_p]),
     "v2p_batch_counts": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64),
                                  POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_batch_hap_range": (c_int, [c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
@@ -127,6 +128,12 @@ class OneShotInfo(ctypes.Structure):
     """v2p_oneshot_info (include/vcf2prot_hip.h)"""
     _fields_ = [("kernel", ctypes.c_int32), ("n_slices", ctypes.c_uint32), ("total_ms", ctypes.c_float), ("build_ms", ctypes.c_float),
                 ("call_wall_ms", ctypes.c_double), ("slice_build_ms", ctypes.c_float * 32), ("tables_ms", ctypes.c_float)]
+
+
+class BuildInfo(ctypes.Structure):
+    """v2p_build_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("kernel", ctypes.c_int32), ("K", c_uint32), ("n_tiles", c_uint64), ("two_pass", c_uint32), ("cut_emit_pass", c_uint32),
+                ("fell_back", c_uint32), ("src_bits", c_uint32)]
 
 
 class UniqueInfo(ctypes.Structure):

@@ -97,7 +97,8 @@ inline uint32_t rows_chunk_pad_for(uint64_t out_bytes, uint64_t n_items, int mod
 constexpr uint32_t ROWS_PAD_SLOTS = ROWS_TILE_SLOTS;           // descriptor slots per tile in the padded array (= build_rows.hip: ROWS_PAD)
 // the parse: mode ROWS_WAVE / ROWS_DENSE; phase 0: descriptors into the padded array + tile_count (a tile that does not fit its slots
 // is reported: STATUS_ROWS_STAGE), 1: tile_count only, 2: descriptors straight to desc + tile_desc_base[tile] (the two-pass form: any tile)
-hipError_t launch_rows_parse(const RowsArgs& a, int mode, bool fasta, int phase, hipStream_t stream);
+// *src32 (optional): which instance the launch ran -- true = 32-bit source arithmetic (for v2p_batch_build_info)
+hipError_t launch_rows_parse(const RowsArgs& a, int mode, bool fasta, int phase, hipStream_t stream, bool* src32 = nullptr);
 // padded -> dense (tile_desc_base = the scan of tile_count)
 hipError_t launch_rows_compact(const RowsArgs& a, hipStream_t stream);
 hipError_t launch_rows_hap_begin(const RowsArgs& a, hipStream_t stream);

@@ -15,6 +15,7 @@
 // Integer / index work only (no MFMA); the parse is bound by instruction issue -- vector and scalar alike -- see DESIGN.md 8.2a.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <type_traits>
 #include "build_rows.h"
 #include "build_kernels.h"
@@ -822,12 +823,19 @@ static_assert(ROWS_PAD == ROWS_PAD_SLOTS && ROWS_PAD == ROWS_TILE_SLOTS, "build_
 // every source offset a Task of this launch can name fits 32 bits, with room for the longest run behind it (the header table sits behind the proteome)
 static bool rows_src32(const RowsArgs& a) { return a.proteome_len + a.headers_len + (1ull << 16) < (1ull << 32) && a.n_alt + (1ull << 16) < (1ull << 32); }
 
+// (the one-pass form -- what every cohort that fits its tiles runs -- has a 32-bit instance; the two-pass form keeps 64-bit sources; a tile
+// image has 32-bit sources or is not built)
+static bool rows_parse_src32(const RowsArgs& a, int phase)
+{
+    const bool force64 = getenv("V2P_ROWS_SRC64") != nullptr;                  // test hook: exercise the 64-bit source instance on a small reference
+    return phase == PH_PAD && rows_src32(a) && !force64;
+}
+
 template <int MODE, bool FASTA>
-static hipError_t launch_parse_t(const RowsArgs& a, int phase, hipStream_t stream)
+static hipError_t launch_parse_t(const RowsArgs& a, int phase, bool src32, hipStream_t stream)
 {
     const dim3 grid{uint32_t(a.tile1 - a.tile0)};
-    // (the one-pass form -- what every cohort that fits its tiles runs -- has a 32-bit instance; the two-pass form keeps 64-bit sources)
-    if (phase == PH_PAD && rows_src32(a)) hipLaunchKernelGGL((rows_parse_kernel<MODE, FASTA, PH_PAD, true>), grid, dim3(64), 0, stream, a);
+    if (src32) hipLaunchKernelGGL((rows_parse_kernel<MODE, FASTA, PH_PAD, true>), grid, dim3(64), 0, stream, a);
     else if (phase == PH_PAD) hipLaunchKernelGGL((rows_parse_kernel<MODE, FASTA, PH_PAD, false>), grid, dim3(64), 0, stream, a);
     else if (phase == PH_COUNT) hipLaunchKernelGGL((rows_parse_kernel<MODE, FASTA, PH_COUNT, false>), grid, dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((rows_parse_kernel<MODE, FASTA, PH_DIRECT, false>), grid, dim3(64), 0, stream, a);
@@ -842,12 +850,14 @@ static RowsArgs ranged(const RowsArgs& a0)
     return a;
 }
 
-hipError_t launch_rows_parse(const RowsArgs& a0, int mode, bool fasta, int phase, hipStream_t stream)
+hipError_t launch_rows_parse(const RowsArgs& a0, int mode, bool fasta, int phase, hipStream_t stream, bool* src32_out)
 {
     const RowsArgs a = ranged(a0);
+    const bool src32 = mode == ROWS_TILES || rows_parse_src32(a, phase);       // (decided once per launch: what is reported is what runs)
+    if (src32_out) *src32_out = src32;
     if (a.tile1 <= a.tile0) return hipSuccess;
     if (a.tile1 - a.tile0 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (mode == ROWS_DENSE) return fasta ? launch_parse_t<ROWS_DENSE, true>(a, phase, stream) : launch_parse_t<ROWS_DENSE, false>(a, phase, stream);
+    if (mode == ROWS_DENSE) return fasta ? launch_parse_t<ROWS_DENSE, true>(a, phase, src32, stream) : launch_parse_t<ROWS_DENSE, false>(a, phase, src32, stream);
     if (mode == ROWS_TILES) {
         if (phase != PH_PAD || a.tile_slots == 0u || a.tile_slots > 2048u || a.tile_span_max > 16368u || !rows_src32(a)) return hipErrorInvalidValue;   // (a piece's source field: 31 bits)
         const dim3 grid{uint32_t(a.tile1 - a.tile0)};
@@ -855,7 +865,7 @@ hipError_t launch_rows_parse(const RowsArgs& a0, int mode, bool fasta, int phase
         else hipLaunchKernelGGL((rows_parse_kernel<ROWS_TILES, false, PH_PAD, true>), grid, dim3(64), 0, stream, a);
         return hipGetLastError();
     }
-    return fasta ? launch_parse_t<ROWS_WAVE, true>(a, phase, stream) : launch_parse_t<ROWS_WAVE, false>(a, phase, stream);
+    return fasta ? launch_parse_t<ROWS_WAVE, true>(a, phase, src32, stream) : launch_parse_t<ROWS_WAVE, false>(a, phase, src32, stream);
 }
 
 hipError_t launch_rows_compact(const RowsArgs& a0, hipStream_t stream)

@@ -214,6 +214,7 @@ struct v2p_batch {
     int os_kernel = 0;
     uint64_t n_desc = 0, n_chunks = 0, n_payload = 0, out_bytes = 0, n_haps = 0;
     uint32_t max_chunk_tasks = 0;
+    v2p_build_info build_info = {};   // what the last rows / tile build of this batch did (v2p_batch_build_info); kernel 0: none
     int launch_hint = 0;           // stitch_launch_bits() of the chunk table
     // v2p_batch_bgzf: the arena's haplotypes as BGZF members (bgzf_kernels.hip) -- the encoder's workspace, the members back to back,
     // where each haplotype's members start (device and host copies); z_ready until the next reset
@@ -1319,7 +1320,18 @@ static void copy_stats(const DevStreamView& from, DevStreamView& to)
 // (TILE_SPAN_MAX bytes) and whose pieces fit the tile's slots (<= TILE_SLOTS_MAX), with SIX standard deviations to spare on either (a
 // tile that does not fit sends the whole build to the dense rows image: it must not happen by chance).  The largest such K; *slots: a
 // power of two from 256 up that holds the tile's pieces with the same margin.  0: no K does (transcripts of a dozen KiB) -- no tile image.
-static uint32_t rows_pick_k_tiles(const DevStreamView& v, uint32_t* slots)
+// test hook: V2P_ROWS_K = 1 .. 64 takes the place of the K the rules below pick (read at every build; anything else is ignored).  K is a
+// choice of speed -- every K gives the same image -- and it moves every seam of the parse: tests/test_gpu_rows_seams.py
+static uint32_t rows_forced_k()
+{
+    const char* e = getenv("V2P_ROWS_K");
+    if (!e) return 0u;
+    char* end = nullptr;
+    const long k = strtol(e, &end, 10);
+    return end != e && *end == 0 && k >= 1 && k <= 64 ? uint32_t(k) : 0u;
+}
+
+static uint32_t rows_pick_k_tiles_rule(const DevStreamView& v, uint32_t* slots)
 {
     *slots = 256;
     if (v.n_tx == 0) return 1;
@@ -1339,6 +1351,13 @@ static uint32_t rows_pick_k_tiles(const DevStreamView& v, uint32_t* slots)
     return uint32_t(k);
 }
 
+// (... under the test hook: the forced K with the slots the rule picked; a stream the rule gives no tile image still has none)
+static uint32_t rows_pick_k_tiles(const DevStreamView& v, uint32_t* slots)
+{
+    const uint32_t k = rows_pick_k_tiles_rule(v, slots), fk = rows_forced_k();
+    return k != 0u && v.n_tx != 0 && fk != 0u ? fk : k;
+}
+
 // Tiles of K consecutive transcripts, one wave each (K <= 64: the kernel's prologue gives every transcript of the tile a lane).  A
 // wave takes 64 items in its first window and ADV more in every further one, so K is picked to FILL the tile's last window: among
 // the window counts w whose capacity stays below ~360 items (a tile's descriptors must fit its 256 slots of the padded array; one
@@ -1348,6 +1367,7 @@ static uint32_t rows_pick_k(const DevStreamView& v, int mode)
 {
     if (mode == ROWS_TILES) { uint32_t slots; const uint32_t k = rows_pick_k_tiles(v, &slots); return k ? k : 1u; }
     if (v.n_tx == 0) return 1;
+    if (const uint32_t fk = rows_forced_k()) return fk;
     const double m = v.items_mean, var = v.items_var, sd = sqrt(var);
     const double adv = mode == ROWS_DENSE ? 58.0 : 60.0, z = 1.3;
     const double k_cap = v.fasta ? 240.0 / (m + 2.0) : 64.0;         // FASTA: a header and a line feed per transcript on top
@@ -1465,6 +1485,7 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
     const uint32_t K = rows_pick_k(v, mode);
     const uint64_t n_tiles = n_tx ? (n_tx + K - 1) / K : 1;
     auto up8 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+    b->build_info = v2p_build_info{};
     int rc = init_status(c, b->d_status);
     if (rc) return rc;
     struct Cleanup {
@@ -1520,6 +1541,7 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
     // 2. the parse.  One pass: every tile's descriptors into its slots of a padded array, the tiles' counts scanned, a copy kernel
     // compacts.  A tile that does not fit its slots (a transcript with hundreds of tasks ...): the two-pass form -- count, scan, write.
     bool two_pass = n_tiles >= (1ull << 25);
+    bool src32 = false;                                             // the instance that wrote the descriptors, as the launcher picked it
     uint64_t n_desc = 0;
     float ms_parse = 0.f;
     for (int attempt = 0; ; ++attempt) {
@@ -1532,7 +1554,7 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
             else if (pe != hipSuccess) return c->hip_fail(pe, "hipMalloc(padded descriptors)");
             else a.desc_pad = reinterpret_cast<uint64_t*>(guard.pad.ptr());
         }
-        HIP_TRY(c, launch_rows_parse(a, mode, fasta, two_pass ? 1 : 0, c->stream), "launch(parse)");
+        HIP_TRY(c, launch_rows_parse(a, mode, fasta, two_pass ? 1 : 0, c->stream, &src32), "launch(parse)");
         HIP_TRY(c, launch_scan_u32(a.tile_count, n_tiles, a.tile_desc_base, scan_scratch + rows_scan_scratch_entries(n_tiles), c->stream), "launch(scan)");
         HIP_TRY(c, hipEventRecord(guard.ev[3], c->stream), "hipEventRecord");
         HIP_TRY(c, hipMemcpyAsync(&n_desc, d + o_tdbase + n_tiles * 8, 8, hipMemcpyDeviceToHost, c->stream), "D2H(n_desc)");
@@ -1558,7 +1580,7 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
     HIP_TRY(c, b->d_desc.ensure((n_desc ? n_desc : 1) * 8), "hipMalloc(desc)");
     a.desc = reinterpret_cast<uint64_t*>(b->d_desc.ptr()); a.desc_cap = n_desc;
     HIP_TRY(c, hipEventRecord(guard.ev[4], c->stream), "hipEventRecord");
-    if (two_pass) HIP_TRY(c, launch_rows_parse(a, mode, fasta, 2, c->stream), "launch(parse: write)");
+    if (two_pass) HIP_TRY(c, launch_rows_parse(a, mode, fasta, 2, c->stream, &src32), "launch(parse: write)");
     else HIP_TRY(c, launch_rows_compact(a, c->stream), "launch(compact)");
     HIP_TRY(c, launch_rows_hap_begin(a, c->stream), "launch(hap_begin)");
     HIP_TRY(c, launch_rows_cut(a, mode, 2, c->stream), "launch(cut)");
@@ -1627,6 +1649,9 @@ static int build_rows_image(v2p_batch* b, const DevStreamView& v, int mode, floa
     b->uses_proteome = true;
     b->rows_state = 0; b->finalized = true;
     b->n_slices = 0;
+    b->build_info.kernel = mode == ROWS_DENSE ? 7 : 6; b->build_info.K = K; b->build_info.n_tiles = n_tiles;
+    b->build_info.two_pass = two_pass ? 1u : 0u; b->build_info.cut_emit_pass = totals[3] ? 1u : 0u;
+    b->build_info.src_bits = src32 ? 32u : 64u;
     return V2P_OK;
 }
 
@@ -2279,6 +2304,7 @@ static int batch_reset_locked(v2p_batch* b, bool wait)
     b->rows_state = 0;                              // (the resident rows are the image's that is gone)
     b->z_ready = false; b->z_begin.clear();
     b->os_kernel = 0; b->os_build_ms = 0.f; b->os_wall_ms = 0.0; b->os_ahead = false;      // (v2p_batch_oneshot_info: no call to report on)
+    b->build_info = v2p_build_info{};
     stream_detach(b); b->orphaned = false;
     if (b->desc_swapped) { std::swap(b->d_desc, b->d_pad); b->desc_swapped = false; }     // (the large allocation is the padded array's again)
     return V2P_OK;
@@ -2463,6 +2489,7 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
     const uint64_t n_tx = v.n_tx, n_h = v.n_haps;
     const uint32_t K = rows_pick_k(v, mode);
     const uint64_t n_tiles = n_tx ? (n_tx + K - 1) / K : 1;
+    b->build_info = v2p_build_info{};
     if (n_tiles >= (1ull << 25)) { *fallback = true; return V2P_OK; }
     const uint64_t out_bytes = st->out_bytes;
     const uint64_t n_rows = (out_bytes + ROW_BYTES - 1) / ROW_BYTES, n_segs = (n_rows + ROWS_SEG - 1) / ROWS_SEG;
@@ -2599,6 +2626,7 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
     // 3.96 -> 4.34 ms, C4 whole's 2.75 -> 3.07 with three slices -- the small kernels take wave slots and issue cycles from the parse,
     // which is balanced on all of its units, and give back less than they take.  Overlap does not pay on this chip, again (section 4).
     const bool ahead = pad && S > 1;
+    bool os_src32 = false;                                          // the parse instance, as the launcher picked it
     b->os_ahead = ahead;
     if (ahead) {
         OS_TRY(hipStreamWaitEvent(X, b->ev_os[0], 0), "hipStreamWaitEvent");
@@ -2607,7 +2635,7 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
             a.tile0 = T[j]; a.tile1 = T[j + 1];
             const uint64_t nt = T[j + 1] - T[j];
             a.desc_pad = a.desc + T[j] * ROWS_PAD_SLOTS;
-            if (nt) OS_TRY(launch_rows_parse(a, mode, v.fasta, 0, X), "launch(parse)");
+            if (nt) OS_TRY(launch_rows_parse(a, mode, v.fasta, 0, X, &os_src32), "launch(parse)");
             if (j == 0) OS_TRY(launch_scan_u32_from(a.tile_count, nt, a.tile_desc_base, scan_scratch + rows_scan_scratch_entries(n_tiles), 0, X), "launch(scan)");
             else OS_TRY(launch_scan_u32_chained(a.tile_count + T[j], nt, a.tile_desc_base + T[j], scan_scratch + rows_scan_scratch_entries(n_tiles), X), "launch(scan)");
             OS_TRY(hipEventRecord(b->ev_par[j], X), "hipEventRecord");
@@ -2620,7 +2648,7 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
         if (!ahead || j > 0) OS_TRY(hipEventRecord(b->ev_os[2 + 2 * j], B), "hipEventRecord");     // (ahead: slice 0's interval starts with its parse, on X)
         if (nt && !ahead) {
             if (pad) a.desc_pad = a.desc + T[j] * ROWS_PAD_SLOTS;               // (the slice's tiles' own slots of the one array)
-            OS_TRY(launch_rows_parse(a, mode, v.fasta, 0, B), "launch(parse)");
+            OS_TRY(launch_rows_parse(a, mode, v.fasta, 0, B, &os_src32), "launch(parse)");
             OS_TRY(launch_scan_u32_from(a.tile_count + T[j], nt, a.tile_desc_base + T[j], scan_scratch + rows_scan_scratch_entries(n_tiles), desc0, B), "launch(scan)");
             if (!pad) {
                 // the compaction (a copy at the memory's rate) on a stream of its own, next to the cutter (one wave per 640 rows: latency), the
@@ -2694,6 +2722,8 @@ static int build_and_execute_rows(v2p_batch* b, const v2p_stream* st, int mode, 
     b->slice_chunk0[S] = chunk0;
     HIP_TRY(c, hipEventRecord(b->ev_os[1], A), "hipEventRecord");
     b->n_desc = desc0; b->n_chunks = chunk0; b->n_slices = S;
+    b->build_info.kernel = mode == ROWS_DENSE ? 7 : 6; b->build_info.K = K; b->build_info.n_tiles = n_tiles;
+    b->build_info.src_bits = os_src32 ? 32u : 64u;
     b->img.hap_out_begin = st->hap_out_begin;
     b->uses_proteome = true;
     b->rows_state = 0; b->finalized = true;
@@ -2720,6 +2750,7 @@ static int build_tiles(v2p_batch* b, const v2p_stream* st, bool execute, bool* f
     *fallback = false;
     uint32_t slots = 0;
     const uint32_t K = tiles_possible(st) ? rows_pick_k_tiles(v, &slots) : 0u;
+    b->build_info = v2p_build_info{};
     if (K == 0u) { *fallback = true; return V2P_OK; }
     const uint64_t n_tx = v.n_tx, n_h = v.n_haps, out_bytes = st->out_bytes;
     const uint64_t n_tiles = (n_tx + K - 1) / K;
@@ -2821,6 +2852,7 @@ static int build_tiles(v2p_batch* b, const v2p_stream* st, bool execute, bool* f
     b->img.hap_out_begin = st->hap_out_begin;
     b->uses_proteome = true; b->rows_state = 0; b->finalized = true;
     b->n_slices = 1; b->slice_chunk0[0] = 0; b->slice_chunk0[1] = n_tiles; b->os_ahead = false;
+    b->build_info.kernel = 9; b->build_info.K = K; b->build_info.n_tiles = n_tiles; b->build_info.src_bits = 32u;
     if (execute && !executed_in_slices) HIP_TRY(c, tiles_execute(b, A), "launch(stitch: tile image)");
     HIP_TRY(c, hipEventRecord(b->ev_os[1], A), "hipEventRecord");
     if (build_ms) { *build_ms = 0.f; (void)hipEventElapsedTime(build_ms, b->ev_os[0], b->ev_os[3]); }
@@ -2881,6 +2913,7 @@ static int build_and_execute_locked(v2p_batch* b, const v2p_stream* st, int kern
         if (rc == V2P_ERR_UNSUPPORTED && kernel == 0 && mode == ROWS_WAVE) { mode = ROWS_DENSE; rc = build_rows_image(b, st->v, mode, &ms, false); }
         if (rc == V2P_OK) {
             b->os_build_ms = ms;
+            b->build_info.fell_back = 1u;
             const hipError_t e = stitch_range(b, b->n_desc, 0, b->n_chunks, 0, 0, c->stream);
             if (e != hipSuccess) return c->hip_fail(e, "launch(stitch)");
             HIP_TRY(c, hipEventRecord(b->ev_os[1], c->stream), "hipEventRecord");
@@ -3202,6 +3235,14 @@ int v2p_batch_image_form(const v2p_batch* b)
         resident = rows_wanted(b, a, int(!(b->ctx->flags & V2P_FLAG_TEMPORAL)) | b->launch_hint);
     }
     return (b->pad_image ? 1 : 0) | (b->pieces_state == 1 ? 2 : 0) | (b->d_stage.ptr() ? 4 : 0) | (b->is_tiles ? 8 : 0) | (resident ? 16 : 0);
+}
+
+int v2p_batch_build_info(const v2p_batch* b, v2p_build_info* info)
+{
+    if (!b || !info) return V2P_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(b->ctx->mu);
+    *info = b->finalized ? b->build_info : v2p_build_info{};
+    return V2P_OK;
 }
 
 int v2p_batch_hap_range(const v2p_batch* b, uint64_t h, uint64_t* begin, uint64_t* len)

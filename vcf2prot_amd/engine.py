@@ -415,6 +415,13 @@ class Batch:
             self.ctx._check(f)
         return {"padded": bool(f & 1), "pieces": bool(f & 2), "staging_buffers": bool(f & 4), "tiles": bool(f & 8), "resident_rows": bool(f & 16)}
 
+    def build_info(self) -> dict:
+        """v2p_batch_build_info: what the last one-pass build of the batch did (kernel 0: none)."""
+        info = N.BuildInfo()
+        self.ctx._check(self._lib.v2p_batch_build_info(self._h, ctypes.byref(info)))
+        return {"kernel": int(info.kernel), "K": int(info.K), "n_tiles": int(info.n_tiles), "two_pass": bool(info.two_pass),
+                "cut_emit_pass": bool(info.cut_emit_pass), "fell_back": bool(info.fell_back), "src_bits": int(info.src_bits)}
+
     def oneshot_info(self) -> dict:
         info = N.OneShotInfo()
         self.ctx._check(self._lib.v2p_batch_oneshot_info(self._h, ctypes.byref(info)))
