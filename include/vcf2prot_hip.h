@@ -449,6 +449,36 @@ int  v2p_unique_classes(v2p_unique* u, uint64_t* key, uint32_t* len, uint64_t* c
 int  v2p_unique_emit(v2p_unique* u, const uint32_t* order, uint64_t n, const uint8_t* headers, const uint64_t* header_begin,
                      uint8_t* out, uint64_t out_len);
 
+/* ---- cohort-wide variant peptides: the distinct records' K-mers filtered on the device (vcf2prot_amd/csrc/variant_peptides.hip) ----
+ * K is fixed per set, 1 <= K <= 16.  The BACKGROUND is the set of all K-byte windows s[i, i + K) of every reference sequence s: a window
+ * never spans two sequences, and a sequence shorter than K has none.  A VARIANT PEPTIDE is a K-byte window r[i, i + K) of some class's
+ * residues (v2p_unique_*) that is not in the background; windows never span two classes and never include the store's line feed.  Bytes
+ * are bytes: '*', 'X', '.' and any value 0 .. 255 take part like any residue.  Per distinct variant peptide: occ, the sum of count[c]
+ * over the classes c and offsets i at which it occurs (occurrences in haplotype records: twice in one protein counts twice), and first,
+ * the smallest (class id, offset) at which it occurs.  Peptides are delivered in ascending `first`.  A window is its own key, so equality
+ * is exact; nothing depends on the order in which atomics arrive or on a table's size.  The rule in Python: tests/peptides_rule.py. */
+typedef struct v2p_peptides v2p_peptides;
+typedef struct { uint64_t k, n_ref_windows, n_ref_kmers, ref_table_slots,      /* the background: windows inserted, distinct ones, slots */
+                 n_windows, n_novel_windows, n_peptides, table_slots;          /* the scan: windows probed, those not in the background, distinct ones, slots */
+                 float ms_ref_build, ms_filter, ms_insert, ms_collect; } v2p_peptides_info;   /* HIP events on the context's stream: the create's upload +
+                                                                               * build; probe + count + list (with the host's one look at the count);
+                                                                               * table insert; first-occurrence flags + scan + emit (with one look) */
+/* ref: HOST bytes; sequence j = ref[seq_begin[j], + seq_len[j]); builds the background on the device.  Sequences may overlap and come in
+ * any order.  V2P_ERR_INVALID_ARG: k == 0 or k > 16; a sequence whose range leaves ref (v2p_last_error_index: the sequence).  n_seq == 0 is
+ * legal: with no background every window is a variant peptide. */
+int  v2p_peptides_create(v2p_ctx*, uint32_t k, const uint8_t* ref, uint64_t ref_bytes,
+                         const uint64_t* seq_begin, const uint32_t* seq_len, uint64_t n_seq, v2p_peptides** out);
+void v2p_peptides_destroy(v2p_peptides*);
+/* every window of every class u holds NOW, with the classes' current counts; replaces the result of an earlier scan.  An empty set is
+ * legal.  V2P_ERR_INVALID_ARG: u belongs to another context.  A failed scan leaves the earlier result. */
+int  v2p_peptides_scan(v2p_peptides*, v2p_unique* u, v2p_peptides_info* info);
+/* V2P_ERR_STATE before the first scan */
+int  v2p_peptides_count(const v2p_peptides*, uint64_t* n);
+/* n must equal the count (V2P_ERR_INVALID_ARG); text [n * k], occ / first_class / first_offset [n]; any pointer may be NULL.
+ * V2P_ERR_STATE before the first scan. */
+int  v2p_peptides_download(v2p_peptides*, uint8_t* text, uint64_t* occ,
+                           uint32_t* first_class, uint32_t* first_offset, uint64_t n);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.

@@ -1,4 +1,4 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]]] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
@@ -9,7 +9,11 @@ any other gzip is inflated on the host first.
 
 --write_unique (long option only, not the reference's) writes the cohort's NON-REDUNDANT proteome instead of one FASTA per proband: every
 slice's result stays on the GPU and is deduplicated there (v2p_unique_add), <outdir>/unique_proteins.fasta holds each distinct protein once
-(`>{transcript}_v{k} n={haplotypes that carry it}`) and <outdir>/unique_proteins.tsv which variant k each proband's two haplotypes have."""
+(`>{transcript}_v{k} n={haplotypes that carry it}`) and <outdir>/unique_proteins.tsv which variant k each proband's two haplotypes have.
+
+--write_peptides K[,K...] (with --write_unique; at most eight lengths, each 1-16) adds <outdir>/variant_peptides_k{K}.tsv: the K-residue
+windows of those distinct proteins that occur in no sequence of the -r file, each once (`peptide, occurrences in haplotype records, the
+first protein that has it, 1-based position`), sorted bytewise.  The windows are filtered and deduplicated on the GPU (v2p_peptides_*)."""
 import argparse
 import os
 import subprocess
@@ -35,11 +39,20 @@ def main() -> int:
     ap.add_argument("--device-tasks", action="store_true", help="generate instructions and Task vectors (steps 4a / 4b) on the GPU too (same bytes; opt-in)")
     ap.add_argument("--write_unique", action="store_true",
                     help="write unique_proteins.fasta / .tsv (each distinct protein once, deduplicated on the GPU) instead of one FASTA per proband; not with -c / --write_bgzf")
+    ap.add_argument("--write_peptides", metavar="K[,K...]", default=None,
+                    help="with --write_unique: also write variant_peptides_k{K}.tsv, the K-residue windows of the distinct proteins that occur nowhere in the "
+                         "-r proteome (filtered on the GPU); at most eight lengths, each 1-16")
     ap.add_argument("--slice-kb", type=int, default=0, help="cut the cohort into slices of about this many KiB of FASTA text (default: 256 MiB; for tests)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
     if a.write_unique and (a.write_compressed or a.write_bgzf):          # (before anything is built or created)
         ap.error("--write_unique writes no per-proband file: it cannot be combined with -c / --write_compressed or --write_bgzf")
+    if a.write_peptides is not None:
+        ks = a.write_peptides.split(",")
+        if not a.write_unique:
+            ap.error("--write_peptides filters the distinct proteins of --write_unique: give --write_unique too")
+        if not all(k.isascii() and k.isdigit() and len(k) <= 2 and 1 <= int(k) <= 16 for k in ks) or len({int(k) for k in ks}) > 8:
+            ap.error("--write_peptides takes K[,K...]: at most eight window lengths, each 1-16")
     from .engine import Engine
     if Engine.from_str(a.engine) is not Engine.GPU:                      # engines.rs:17-29
         sys.exit("only -g gpu is implemented here; st / mt are the reference's CPU engines")
@@ -71,6 +84,8 @@ def main() -> int:
         cmd.append("--device-index")
     if a.write_unique:
         cmd.append("--unique")
+    if a.write_peptides is not None:
+        cmd += ["--peptides", a.write_peptides]
     if a.slice_kb > 0:
         cmd += ["--slice-kb", str(a.slice_kb)]
     return subprocess.run(cmd).returncode

@@ -118,6 +118,11 @@ HIP_API = {
     "v2p_unique_counts": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_unique_classes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_unique_emit": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64]),
+    "v2p_peptides_create": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "v2p_peptides_destroy": (None, [c_void_p]),
+    "v2p_peptides_scan": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "v2p_peptides_count": (c_int, [c_void_p, POINTER(c_uint64)]),
+    "v2p_peptides_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
 }
 
 _hip = None
@@ -140,6 +145,13 @@ class UniqueInfo(ctypes.Structure):
     """v2p_unique_info (include/vcf2prot_hip.h)"""
     _fields_ = [("n_records", c_uint64), ("n_new_classes", c_uint64), ("n_classes", c_uint64), ("store_bytes", c_uint64), ("table_slots", c_uint64),
                 ("ms_digest", ctypes.c_float), ("ms_insert", ctypes.c_float), ("ms_verify", ctypes.c_float), ("ms_commit", ctypes.c_float)]
+
+
+class PeptidesInfo(ctypes.Structure):
+    """v2p_peptides_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("k", c_uint64), ("n_ref_windows", c_uint64), ("n_ref_kmers", c_uint64), ("ref_table_slots", c_uint64), ("n_windows", c_uint64),
+                ("n_novel_windows", c_uint64), ("n_peptides", c_uint64), ("table_slots", c_uint64),
+                ("ms_ref_build", ctypes.c_float), ("ms_filter", ctypes.c_float), ("ms_insert", ctypes.c_float), ("ms_collect", ctypes.c_float)]
 
 
 class Routing(ctypes.Structure):

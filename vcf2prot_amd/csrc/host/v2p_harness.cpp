@@ -366,7 +366,8 @@ static bool write_stats_files(const std::string& outdir, const std::vector<std::
 }
 
 static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* outdir, bool no_test, bool write_all, bool compressed, bool host_build, uint64_t slice_bytes,
-                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index, bool int_map, bool device_int_map, bool unique)
+                    bool bgzf, bool stats, bool host_groups, bool device_tasks, bool device_tables, bool device_index, bool int_map, bool device_int_map, bool unique,
+                    const std::vector<uint32_t>& peptide_ks)
 {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
@@ -860,6 +861,50 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         u_sum.n_records += inf.n_records; u_sum.n_classes = inf.n_classes; u_sum.store_bytes = inf.store_bytes; u_sum.table_slots = inf.table_slots;
         u_sum.ms_digest += inf.ms_digest; u_sum.ms_insert += inf.ms_insert; u_sum.ms_verify += inf.ms_verify; u_sum.ms_commit += inf.ms_commit;
     };
+    // ---- --peptides K[,K...]: behind the set's files, per K the variant peptides of its classes -- the K-residue windows that occur in no
+    // sequence of the -r file (every one of them, not only the transcripts the VCF touches), filtered and deduplicated on the device
+    // (v2p_peptides_*) -- as variant_peptides_k{K}.tsv, sorted bytewise by peptide; class_name[c]: class c's name in unique_proteins.fasta ----
+    std::string pep_json;
+    auto write_peptides = [&](const std::vector<std::string>& class_name) -> bool {
+        std::string blob;
+        std::vector<uint64_t> seq_begin;
+        std::vector<uint32_t> seq_len;
+        for (const auto& kv : ref) { seq_begin.push_back(blob.size()); seq_len.push_back(uint32_t(kv.second.size())); blob += kv.second; }
+        seq_begin.push_back(0); seq_len.push_back(0);
+        for (const uint32_t K : peptide_ks) {
+            v2p_peptides* ps = nullptr;
+            chk(v2p_peptides_create(ctx.raw(), K, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), &ps));
+            struct Guard { v2p_peptides* p; ~Guard() { v2p_peptides_destroy(p); } } guard{ps};
+            v2p_peptides_info inf{};
+            chk(v2p_peptides_scan(ps, uq, &inf));
+            const uint64_t n = inf.n_peptides;
+            std::vector<uint8_t> text(n * K + 1);
+            std::vector<uint64_t> occ(n + 1);
+            std::vector<uint32_t> fc(n + 1), fo(n + 1), order(n);
+            chk(v2p_peptides_download(ps, text.data(), occ.data(), fc.data(), fo.data(), n));
+            for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::memcmp(&text[uint64_t(a) * K], &text[uint64_t(b) * K], K) < 0; });
+            std::string tsv = "#peptide\toccurrences\tfirst_protein\tposition\n";
+            for (const uint32_t i : order) {
+                tsv.append(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K);
+                tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
+            }
+            const std::string path = std::string(outdir) + "/variant_peptides_k" + std::to_string(K) + ".tsv";
+            std::ofstream f(path, std::ios::binary);
+            if (f) f.write(tsv.data(), std::streamsize(tsv.size()));
+            f.close();
+            if (!f) { std::fprintf(stderr, "Could not write %s\n", path.c_str()); return false; }
+            written += tsv.size();
+            char buf[640];
+            std::snprintf(buf, sizeof buf, "%s\"%u\": {\"n_ref_windows\": %llu, \"n_ref_kmers\": %llu, \"ref_table_slots\": %llu, \"n_windows\": %llu, \"n_novel_windows\": %llu, "
+                          "\"n_peptides\": %llu, \"table_slots\": %llu, \"tsv_bytes\": %llu, \"ms_ref_build\": %.3f, \"ms_filter\": %.3f, \"ms_insert\": %.3f, \"ms_collect\": %.3f}",
+                          pep_json.empty() ? "" : ", ", K, (unsigned long long)inf.n_ref_windows, (unsigned long long)inf.n_ref_kmers, (unsigned long long)inf.ref_table_slots,
+                          (unsigned long long)inf.n_windows, (unsigned long long)inf.n_novel_windows, (unsigned long long)inf.n_peptides, (unsigned long long)inf.table_slots,
+                          (unsigned long long)tsv.size(), inf.ms_ref_build, inf.ms_filter, inf.ms_insert, inf.ms_collect);
+            pep_json += buf;
+        }
+        return true;
+    };
     auto write_unique = [&]() -> bool {
         const auto tw = clk::now();
         uint64_t nc = 0;
@@ -913,6 +958,11 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
         if (!ff || !ft) { std::fprintf(stderr, "Could not write %s.fasta / .tsv\n", base.c_str()); return false; }
         u_fasta_bytes = out_len; u_tsv_bytes = tsv.size();
         written += out_len + tsv.size();
+        if (!peptide_ks.empty()) {
+            std::vector<std::string> class_name(nc);
+            for (uint64_t c = 0; c < nc; ++c) class_name[c] = *cname[c] + "_v" + std::to_string(k_of[c]);
+            if (!write_peptides(class_name)) return false;
+        }
         t_write_acc += since(tw);
         return true;
     };
@@ -951,6 +1001,7 @@ static int vcf_mode(const char* vcf_path, const char* fasta_path, const char* ou
                         "\"ms_digest\": %.3f, \"ms_insert\": %.3f, \"ms_verify\": %.3f, \"ms_commit\": %.3f}", (unsigned long long)u_sum.n_records,
                         (unsigned long long)u_sum.n_classes, (unsigned long long)u_sum.store_bytes, (unsigned long long)u_sum.table_slots,
                         (unsigned long long)u_fasta_bytes, (unsigned long long)u_tsv_bytes, u_sum.ms_digest, u_sum.ms_insert, u_sum.ms_verify, u_sum.ms_commit);
+        if (!peptide_ks.empty()) std::printf(", \"peptides\": {%s}", pep_json.c_str());
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     };
     if (tasks_on_device) {
@@ -1280,15 +1331,32 @@ static int sharded(const char* preset, uint32_t samples, int n_devices, bool ove
     return 0;
 }
 
-static uint64_t vcf_slice_kb = 0;       // vcf --slice-kb K: slices of K KiB of FASTA text (tests: several slices out of a small file)
+// --peptides K[,K...]: decimal window lengths, each 1 .. 16, at most eight distinct ones (a repeated value counts once)
+static bool parse_peptide_ks(const char* s, std::vector<uint32_t>& ks)
+{
+    ks.clear();
+    for (const char* p = s;; ++p) {
+        uint32_t v = 0, digits = 0;
+        for (; *p >= '0' && *p <= '9' && digits < 2; ++p, ++digits) v = 10 * v + uint32_t(*p - '0');
+        if (!digits || v < 1 || v > 16 || (*p && *p != ',')) return false;
+        if (std::find(ks.begin(), ks.end(), v) == ks.end()) ks.push_back(v);
+        if (!*p) break;
+    }
+    return ks.size() <= 8;
+}
+
+static uint64_t vcf_slice_kb = 0;     // vcf --slice-kb K: slices of K KiB of FASTA text (tests: several slices out of a small file)
 
 int main(int argc, char** argv)
 {
     if (argc >= 5 && !std::strcmp(argv[1], "vcf")) {
         bool no_test = false, write_all = false, compressed = false, host_build = false, bgzf = false, stats = false, int_map = false, device_int_map = false, unique = false, host_groups = false, device_tasks = false, device_tables = false, device_index = false;
         uint64_t slice_mb = 256;
+        std::vector<uint32_t> peptide_ks;
+        const char* peptides_arg = nullptr;
         for (int i = 5; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--slice-kb") && i + 1 < argc) { slice_mb = 0; vcf_slice_kb = std::strtoull(argv[++i], nullptr, 10); continue; }
+            if (!std::strcmp(argv[i], "--peptides")) { peptides_arg = i + 1 < argc ? argv[++i] : ""; continue; }
             no_test |= !std::strcmp(argv[i], "--no-test");
             host_build |= !std::strcmp(argv[i], "--host-build");
             host_groups |= !std::strcmp(argv[i], "--host-groups");
@@ -1308,7 +1376,11 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "usage: --unique writes unique_proteins.fasta and unique_proteins.tsv from the device's record set, no per-proband file: it cannot be combined with -c, --bgzf or --host-build\n");
             return 2;
         }
-        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index, int_map, device_int_map, unique); }
+        if (peptides_arg && (!unique || !parse_peptide_ks(peptides_arg, peptide_ks))) {
+            std::fprintf(stderr, "usage: --peptides K[,K...] writes variant_peptides_k{K}.tsv from the classes of --unique: it needs --unique and at most eight window lengths, each 1 .. 16\n");
+            return 2;
+        }
+        try { return vcf_mode(argv[2], argv[3], argv[4], no_test, write_all, compressed, host_build, slice_mb ? slice_mb << 20 : (vcf_slice_kb ? vcf_slice_kb << 10 : 1), bgzf, stats, host_groups, device_tasks, device_tables, device_index, int_map, device_int_map, unique, peptide_ks); }
         catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 101; }
     }
     if (argc >= 3 && !std::strcmp(argv[1], "shard")) {              // the cut rule alone (no GPU): one "begin end" line per rank

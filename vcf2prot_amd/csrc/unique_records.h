@@ -22,6 +22,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+struct v2p_ctx;
+struct v2p_unique;
+
 namespace v2p {
 
 constexpr unsigned long long UNIQUE_EMPTY = ~0ull;
@@ -77,5 +80,10 @@ hipError_t launch_unique_resolve(const UniqueArgs& a, hipStream_t st);
 hipError_t launch_unique_rollback(const UniqueArgs& a, hipStream_t st);
 hipError_t launch_unique_rebuild(const UniqueClasses& cls, uint64_t n_classes, unsigned long long* slots, uint64_t slot_mask, hipStream_t st);
 hipError_t launch_unique_emit(const UniqueEmitArgs& a, hipStream_t st);
+
+// What the variant-peptide set (variant_peptides.hip) reads of a distinct-record set: the classes and the store as they are NOW (an add may
+// move both).  Called with the context locked.
+struct UniqueStoreView { v2p_ctx* ctx; UniqueClasses cls; uint64_t n_classes; const uint8_t* store; uint64_t store_bytes; };
+void unique_store_view(const ::v2p_unique* u, UniqueStoreView* v);
 
 }  // namespace v2p

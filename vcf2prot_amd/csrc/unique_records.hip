@@ -292,6 +292,13 @@ struct v2p_unique {
     }
 };
 
+namespace v2p {
+void unique_store_view(const ::v2p_unique* u, UniqueStoreView* v)
+{
+    *v = UniqueStoreView{u->ctx, u->classes(), u->n_classes, u->store.get<uint8_t>(), u->store_bytes};
+}
+}  // namespace v2p
+
 namespace {
 
 struct CtxLock {

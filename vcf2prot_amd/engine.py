@@ -592,6 +592,70 @@ class UniqueSet:
         return out[:out_len].tobytes()
 
 
+class PeptideSet:
+    """One ``v2p_peptides``: the K-byte windows of a UniqueSet's classes that occur in no reference sequence, each once, filtered and
+    deduplicated on the device (the rule: tests/peptides_rule.py).  ``reference``: the sequences as bytes."""
+
+    def __init__(self, ctx: Context, k: int, reference: Sequence[bytes] = ()):
+        self.ctx, self.k = ctx, k
+        self._lib = ctx._lib
+        reference = [bytes(s) for s in reference]
+        lens = np.asarray([len(s) for s in reference] + [0], np.uint32)
+        begin = np.zeros(len(reference) + 1, np.uint64)
+        begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(reference) + b"\0", np.uint8)
+        self._create(blob, int(begin[-1]), begin, lens, len(reference))
+
+    def _create(self, blob: np.ndarray, ref_bytes: int, begin: np.ndarray, lens: np.ndarray, n_seq: int):
+        """v2p_peptides_create on the arrays as given (tests hand it ranges that leave the reference)"""
+        h = ctypes.c_void_p()
+        self._h = None
+        self.ctx._check(self._lib.v2p_peptides_create(self.ctx._h, self.k, blob.ctypes.data, ref_bytes, begin.ctypes.data, lens.ctypes.data, n_seq, ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_arrays(cls, ctx: Context, k: int, blob: np.ndarray, seq_begin, seq_len) -> "PeptideSet":
+        """the reference as one uint8 array and a sequence table (sequences may overlap)"""
+        self = cls.__new__(cls)
+        self.ctx, self.k, self._lib = ctx, k, ctx._lib
+        blob = np.ascontiguousarray(blob, np.uint8)
+        begin, lens = np.ascontiguousarray(seq_begin, np.uint64), np.ascontiguousarray(seq_len, np.uint32)
+        pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
+        self._create(pad(blob), int(blob.size), pad(begin), pad(lens), int(begin.size))
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._lib.v2p_peptides_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scan(self, uset: "UniqueSet") -> dict:
+        """v2p_peptides_scan: every window of every class the set holds now; returns the info."""
+        info = N.PeptidesInfo()
+        self.ctx._check(self._lib.v2p_peptides_scan(self._h, uset._h, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in N.PeptidesInfo._fields_}
+
+    def count(self) -> int:
+        n = ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_peptides_count(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def download(self, n: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_peptides_download: text [n, k], occ, first_class, first_offset, in ascending (first_class, first_offset)."""
+        if n is None:
+            n = self.count()
+        text = np.zeros((n + 1, self.k), np.uint8)
+        occ, cls, off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32)
+        self.ctx._check(self._lib.v2p_peptides_download(self._h, text.ctypes.data, occ.ctypes.data, cls.ctypes.data, off.ctypes.data, n))
+        return {"text": text[:n], "occ": occ[:n], "first_class": cls[:n], "first_offset": off[:n]}
+
+
 def default_context() -> Context:
     global _default_ctx
     if _default_ctx is None or _default_ctx._h is None:
