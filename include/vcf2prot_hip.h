@@ -592,6 +592,33 @@ int v2p_order_chunks_for_xcds(v2p_chunk* chunks, uint64_t n_chunks, const uint64
  * out_bytes == d_hap_begin[n_haps] (the grid is sized by the one, the walk by the other).  Pinned by tests/test_gpu_digest.py. */
 int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_hap_begin, uint64_t n_haps,
                       uint64_t out_bytes, uint64_t* d_digests);
+/* The kernels of PIECE and TILE images (vcf2prot_amd/csrc/dense_pieces.h) on caller-owned device memory: no context, no batch.  The buffer
+ * contract is v2p_stitch_launch_opts's: 32 readable bytes either side of each source, d_out 16-byte aligned.  Pinned by
+ * tests/test_gpu_pieces_rule.py.
+ *
+ * v2p_pieces_build_launch: the conversion a dense rows image gets the first time it is executed AGAIN -- the count pass, the scan of the
+ * chunks' counts, ONE look by the host at the status word and the total (the call waits for the stream there), the write pass.  d_count
+ * [n_chunks] receives every chunk's pieces, d_base [n_chunks + 1] their exclusive sum and the total, d_pieces [capacity] and d_chunks2
+ * [n_chunks] the image; d_status is one device uint64 initialised to ~0.  *status receives the status word, *n_pieces the total.  The
+ * write pass is launched only when the status word is clean and 0 < total <= capacity: otherwise d_pieces and d_chunks2 are left alone
+ * (V2P_OK; a status word that is not ~0 is index << 8 | 9 -- a chunk or descriptor the form does not take, the smallest reported). */
+int v2p_pieces_build_launch(void* hip_stream,
+                            const uint64_t* d_desc, uint64_t n_desc, const v2p_chunk* d_chunks, uint32_t n_chunks,
+                            uint64_t src0_len, uint64_t src1_len, uint64_t out_len,
+                            uint32_t* d_count, uint64_t* d_base, uint64_t* d_pieces, uint64_t capacity, v2p_chunk* d_chunks2,
+                            uint64_t* d_status, uint64_t* status, uint64_t* n_pieces);
+/* stitch_pieces_kernel on a piece image: enqueued on hip_stream, no host wait.  The kernel trusts its builder: a piece must lie inside its
+ * chunk's span and inside its source; a chunk record whose span exceeds 12288 or whose range leaves d_out[0, out_len) writes nothing. */
+int v2p_pieces_exec_launch(void* hip_stream, const uint64_t* d_pieces, const v2p_chunk* d_chunks2, uint32_t n_chunks,
+                           const uint8_t* d_src0, const uint8_t* d_src1, uint8_t* d_out, uint64_t out_len, int nontemporal);
+/* stitch_tiles_kernel on tiles [tile0, tile0 + n_tiles) of a TILE image: tile t owns d_pieces[tile_slots t, tile_slots (t + 1)), the first
+ * d_tile_count[t] of them, and writes d_out[d_tile_res_base[t], d_tile_res_base[t + 1]).  Enqueued on hip_stream, no host wait.  Nothing is
+ * written unless *d_status is ~0; a tile of more than 16368 bytes or more than tile_slots pieces, or one that ends beyond out_len, is not
+ * written.  tile_slots 0 or above 2048: V2P_ERR_INVALID_ARG, nothing launched. */
+int v2p_tiles_exec_launch(void* hip_stream, const uint64_t* d_pieces, uint32_t tile_slots, const uint32_t* d_tile_count,
+                          const uint64_t* d_tile_res_base, uint64_t n_tiles, uint64_t tile0,
+                          const uint8_t* d_src0, const uint8_t* d_src1, uint8_t* d_out, uint64_t out_len,
+                          const uint64_t* d_status, int nontemporal);
 /* BGZF members of the ranges [d_range_begin[r], d_range_begin[r + 1]) of d_in (ascending; n_bytes = their span) on caller-owned device
  * memory, enqueued on hip_stream with no host wait: d_workspace (256-byte aligned) holds v2p_bgzf_workspace_bytes(n_bytes, n_ranges);
  * d_out_begin [n_ranges + 1] receives where each range's members start in d_out and their total.  d_out needs the total

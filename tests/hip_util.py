@@ -163,3 +163,117 @@ def stitch_launch(desc, chunks, src0, src1, out_len, opts=None, guard=4096):
     assert rc == 0, rc
     guards = bool((got[:guard] == 0xA5).all() and (got[guard + out_len:] == 0xA5).all() and (st[:guard] == 0xA5).all() and (st[guard + 8:] == 0xA5).all())
     return got[guard:guard + out_len].copy(), int(st[guard:guard + 8].view(np.uint64)[0]), guards
+
+
+class _Guarded:
+    """a payload between two guard regions of 0xA5 on the device"""
+
+    def __init__(self, payload: np.ndarray, guard: int):
+        payload = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+        self.n, self.guard = payload.size, guard
+        tail = (-self.n) % 16
+        host = np.full(guard + self.n + guard + tail, 0xA5, np.uint8)
+        host[guard:guard + self.n] = payload
+        self.buf = DevBuf.of(host, pad=256)
+        self.ptr = self.buf.ptr + guard
+        assert self.ptr % 16 == 0
+
+    def fetch(self):
+        """-> (payload bytes, both guards untouched)"""
+        got = self.buf.download()
+        return got[self.guard:self.guard + self.n].copy(), bool((got[:self.guard] == 0xA5).all() and (got[self.guard + self.n:] == 0xA5).all())
+
+    def free(self):
+        self.buf.free()
+
+
+def _padded_sources(src0, src1):
+    """both sources with exactly PAD_BYTES (32) of 0xEE either side"""
+    out = []
+    for s in (src0, src1):
+        h = np.full(32 + len(s) + 32, 0xEE, np.uint8)
+        h[32:32 + len(s)] = s
+        out.append(DevBuf.of(h))
+    return out
+
+
+def _synced(what):
+    sync = hip().hipDeviceSynchronize()
+    if sync != 0:                                                     # a fault: nothing more goes to this GPU from this process
+        import pytest
+        pytest.exit(f"{what} left HIP error {sync} behind", returncode=3)
+
+
+def pieces_exec_launch(pieces, chunks2, src0, src1, out_len, nontemporal=1, guard=4096):
+    """v2p_pieces_exec_launch (include/vcf2prot_hip.h) on a hand-built or a built piece image: the sources and the arena as for
+    stitch_launch, pieces and chunk records between guards.  Returns (arena [out_len], every guard untouched)."""
+    from vcf2prot_amd import _native as N
+    pieces = np.ascontiguousarray(pieces, np.uint64)
+    chunks2 = np.ascontiguousarray(chunks2, np.uint64).reshape(-1, 2)
+    d_pieces, d_chunks2 = _Guarded(pieces, guard), _Guarded(chunks2, guard)
+    srcs = _padded_sources(src0, src1)
+    d_out = _Guarded(np.full(out_len, 0x5A, np.uint8), guard)
+    rc = N.hip_lib().v2p_pieces_exec_launch(None, d_pieces.ptr, d_chunks2.ptr, chunks2.shape[0], srcs[0].ptr + 32, srcs[1].ptr + 32, d_out.ptr, out_len, nontemporal)
+    _synced("v2p_pieces_exec_launch")
+    (got, g0), (_, g1), (_, g2) = d_out.fetch(), d_pieces.fetch(), d_chunks2.fetch()
+    for b in (d_pieces, d_chunks2, d_out, *srcs):
+        b.free()
+    assert rc == 0, rc
+    return got, g0 and g1 and g2
+
+
+def pieces_launch(desc, chunks, src0, src1, out_len, capacity, nontemporal=1, guard=4096):
+    """v2p_pieces_build_launch on a descriptor image -- count [n_chunks], base [n_chunks + 1], pieces [capacity], chunks2 [n_chunks] and the
+    status word each between guard regions of 0xA5 and themselves 0xA5 before the call (the status word all ones) -- and, if the image was
+    converted, v2p_pieces_exec_launch on what it wrote.  Returns dict(status, total, device_status, converted, count, base, pieces, chunks2
+    (as written, or None: all four untouched where not converted -- count and base aside, which pass 0 and the scan write), arena
+    [out_len] (0x5A where nothing was executed), guards)."""
+    from vcf2prot_amd import _native as N
+    lib = N.hip_lib()
+    desc = np.ascontiguousarray(desc, np.uint64)
+    chunks = np.ascontiguousarray(chunks, np.uint64).reshape(-1, 2)
+    nc = chunks.shape[0]
+    poison = np.uint64((1 << 36) | (1000 << 40))
+    d_desc = DevBuf.of(np.concatenate([np.full(2, poison, np.uint64), desc, np.full(4, poison, np.uint64)]))
+    d_chunks = DevBuf.of(chunks)
+    d_count, d_base = _Guarded(np.full(4 * nc, 0xA5, np.uint8), guard), _Guarded(np.full(8 * (nc + 1), 0xA5, np.uint8), guard)
+    d_pieces, d_chunks2 = _Guarded(np.full(8 * capacity, 0xA5, np.uint8), guard), _Guarded(np.full(16 * nc, 0xA5, np.uint8), guard)
+    d_status = _Guarded(np.full(8, 0xFF, np.uint8), guard)
+    status, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib.v2p_pieces_build_launch(None, d_desc.ptr + 16, desc.size, d_chunks.ptr, nc, len(src0), len(src1), out_len,
+                                     d_count.ptr, d_base.ptr, d_pieces.ptr, capacity, d_chunks2.ptr, d_status.ptr, ctypes.byref(status), ctypes.byref(total))
+    _synced("v2p_pieces_build_launch")
+    fetched = [b.fetch() for b in (d_count, d_base, d_pieces, d_chunks2, d_status)]
+    for b in (d_desc, d_chunks, d_count, d_base, d_pieces, d_chunks2, d_status):
+        b.free()
+    assert rc == 0, rc
+    guards = all(g for _, g in fetched)
+    count, base, pieces, chunks2, st = (f[0] for f in fetched)
+    untouched = bool((pieces == 0xA5).all() and (chunks2 == 0xA5).all())
+    out = dict(status=int(status.value), total=int(total.value), device_status=int(st.view(np.uint64)[0]), converted=not untouched,
+               count=count.view(np.uint32).copy(), base=base.view(np.uint64).copy(), pieces=None, chunks2=None, guards=guards,
+               arena=np.full(out_len, 0x5A, np.uint8))
+    if not untouched:
+        out["pieces"], out["chunks2"] = pieces.view(np.uint64).copy(), chunks2.view(np.uint64).reshape(-1, 2).copy()
+        if out["status"] == 2 ** 64 - 1 and 0 < out["total"] <= capacity:
+            out["arena"], g = pieces_exec_launch(out["pieces"], out["chunks2"], src0, src1, out_len, nontemporal, guard)
+            out["guards"] = guards and g
+    return out
+
+
+def tiles_launch(pieces, tile_slots, tile_count, tile_res_base, n_tiles, tile0, src0, src1, out_len, status=2 ** 64 - 1, nontemporal=1, guard=4096):
+    """v2p_tiles_exec_launch on a hand-built tile image: pieces, both tables and the status word between guards, the sources and the arena
+    as for stitch_launch.  Returns (return code, arena [out_len], status word afterwards, every guard untouched)."""
+    from vcf2prot_amd import _native as N
+    d_pieces = _Guarded(np.ascontiguousarray(pieces, np.uint64), guard)
+    d_count, d_base = _Guarded(np.ascontiguousarray(tile_count, np.uint32), guard), _Guarded(np.ascontiguousarray(tile_res_base, np.uint64), guard)
+    d_status = _Guarded(np.array([status], np.uint64), guard)
+    srcs = _padded_sources(src0, src1)
+    d_out = _Guarded(np.full(out_len, 0x5A, np.uint8), guard)
+    rc = N.hip_lib().v2p_tiles_exec_launch(None, d_pieces.ptr, tile_slots, d_count.ptr, d_base.ptr, n_tiles, tile0, srcs[0].ptr + 32, srcs[1].ptr + 32,
+                                           d_out.ptr, out_len, d_status.ptr, nontemporal)
+    _synced("v2p_tiles_exec_launch")
+    fetched = [b.fetch() for b in (d_out, d_status, d_pieces, d_count, d_base)]
+    for b in (d_pieces, d_count, d_base, d_status, d_out, *srcs):
+        b.free()
+    return int(rc), fetched[0][0], int(fetched[1][0].view(np.uint64)[0]), all(g for _, g in fetched)

@@ -22,6 +22,9 @@ def test_hip_library_exports_every_declared_symbol(built):
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/vcf2prot_hip.h but not exported"
     assert set(names) == set(N.HIP_API), "python binding table out of sync with the header"
+    # the raw launchers on caller-owned device memory, the ways in of the launch-level GPU suites
+    for n in ("v2p_stitch_launch_opts", "v2p_digest_launch", "v2p_pieces_build_launch", "v2p_pieces_exec_launch", "v2p_tiles_exec_launch"):
+        assert n in names, n
 
 
 def test_host_library_exports_every_declared_symbol(built):

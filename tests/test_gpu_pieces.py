@@ -1,6 +1,7 @@
 """PIECE images (csrc/dense_pieces.h): a dense rows image that is executed AGAIN is re-written, once, as pieces of <= 16 result bytes with
 their positions and substituted residues, and stitch_pieces_kernel executes those.  Bit-exact against the dense kernel's arena (the first
-execute), the oracle and the reference's own Task dumps; an image the form does not take stays on the dense kernel."""
+execute), the oracle and the reference's own Task dumps; an image the form does not take stays on the dense kernel
+(test_hand_built_image_at_the_piece_limit: a chunk of 2 048 pieces).  The kernels on their own: tests/test_gpu_pieces_rule.py."""
 import numpy as np
 import pytest
 
@@ -59,3 +60,26 @@ def test_random_streams_from_pieces(built, gpu_ctx, seed, shape):
         assert got.size == w.size and np.array_equal(got, w), (seed, shape, h)
     b.close()
     rs.close()
+
+
+@pytest.mark.parametrize("name,converted", [("pieces_2047_accepted", True), ("pieces_2048_are_refused", False)])
+def test_hand_built_image_at_the_piece_limit(built, gpu_ctx, name, converted):
+    """A hand-built dense rows image (skip == clip == 0) through set_packed / finalize, executed three times with the arena scribbled in
+    between: a chunk of 2 047 pieces runs from pieces from the second execute on, one of 2 048 stays on the dense kernel -- and every byte
+    is the rule's on every execute, whichever kernel wrote it."""
+    import pieces_cases as C
+    import stitch_rule as R
+    im = C.built(name)
+    want, status = R.run_rule(im)                                     # (the dense kernel takes both images)
+    assert status == R.STATUS_CLEAN
+    gpu_ctx.upload_proteome(im.src0)
+    desc, chunks = im.arrays()
+    b = gpu_ctx.batch()
+    b.set_packed(desc, chunks, im.src1, np.array([0, im.out_len], np.uint64))
+    b.finalize()
+    for k in range(3):
+        b.scribble(R.SENTINEL); b.execute(); b.sync()
+        assert b.image_form()["pieces"] == (converted and k >= 1), (name, k)
+        got = b.download(0, im.out_len)
+        assert np.array_equal(got, np.frombuffer(want, np.uint8)), (name, k, int(np.nonzero(got != np.frombuffer(want, np.uint8))[0][0]))
+    b.close()

@@ -103,6 +103,11 @@ HIP_API = {
     "v2p_routing_rules": (c_int, [c_uint64, c_uint64, c_uint64, c_uint64, c_int, c_void_p]),
     "v2p_order_chunks_for_xcds": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, c_uint64]),
     "v2p_digest_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
+    "v2p_pieces_build_launch": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint64, c_uint64, c_uint64,
+                                        c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_pieces_exec_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_int]),
+    "v2p_tiles_exec_launch": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64,
+                                      c_void_p, c_int]),
     "v2p_batch_bgzf": (c_int, [c_void_p, POINTER(c_uint64)]),
     "v2p_pipeline_bgzf_info": (c_int, [c_void_p, ctypes.c_uint32, POINTER(c_void_p), POINTER(c_uint64)]),
     "v2p_batch_bgzf_hap_range": (c_int, [c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -80,7 +80,7 @@ __device__ __forceinline__ uint64_t pack_piece(uint32_t space, uint64_t src, uin
            (uint64_t(lit ? 1u : 0u) << 55) | (uint64_t(byte & 0xFFu) << 56);
 }
 
-// the pieces of one descriptor: ranges of <= 32 bytes from its first byte on, a range holding at most ONE substituted residue (two inside
+// the pieces of one descriptor: ranges of <= 16 bytes (PIECE_BYTES) from its first byte on, a range holding at most ONE substituted residue (two inside
 // one range: it ends in front of the second); EMIT = false: how many
 template <bool EMIT>
 __device__ __forceinline__ uint32_t cut_pieces(const Dec& r, uint32_t off, uint64_t* out)

@@ -3097,6 +3097,35 @@ static bool pieces_eligible(const v2p_batch* b)
     return b->finalized && !b->is_patch && !b->is_tiles && (h & 2) && (h & 8) && !(h & 4) && (h & 16) && (h & 32) && b->n_chunks != 0 && ctx_variant(b->ctx) != 28u &&
            ctx_variant(b->ctx) != 3u && ctx_variant(b->ctx) != 8u;
 }
+// The conversion's device sequence, on buffers its caller holds (to_pieces; v2p_pieces_build_launch): pass 0, the scan of the chunks' counts,
+// ONE look by the host at the status word and the total, pass 1.  a.count [n_chunks], a.base [n_chunks + 1], a.status (~0) are the
+// caller's, tile_scratch holds scan_tiles_for(n_chunks + 1) entries; place(total) says where the pieces and the chunk records go (false:
+// no room for them).  Pass 1 is launched only for a clean status word and a total that is not 0 and that place() takes: *converted.
+// The stream is waited for before the return (the callers' scratch dies with them).  *what: the step a HIP error came from.
+static hipError_t pieces_convert(PieceBuildArgs& a, uint64_t* tile_scratch, hipStream_t stream, uint64_t* total, unsigned long long* stw, bool* converted,
+                                 const char** what, const std::function<bool(uint64_t)>& place)
+{
+    *total = 0; *stw = ~0ull; *converted = false;
+    hipError_t e;
+    *what = "launch(pieces: count)";
+    if ((e = launch_pieces_build(a, 0, stream)) != hipSuccess) return e;
+    *what = "launch(scan)";
+    if ((e = launch_scan_u32(a.count, a.n_chunks, const_cast<uint64_t*>(a.base), tile_scratch, stream)) != hipSuccess) return e;
+    *what = "D2H(pieces)";
+    if ((e = hipMemcpyAsync(total, a.base + a.n_chunks, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    *what = "D2H(status)";
+    if ((e = hipMemcpyAsync(stw, a.status, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    *what = "hipStreamSynchronize";
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    if (*stw != ~0ull || *total == 0 || !place(*total)) return hipSuccess;
+    *what = "launch(pieces: write)";
+    if ((e = launch_pieces_build(a, 1, stream)) != hipSuccess) return e;
+    *what = "hipStreamSynchronize";
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    *converted = true;
+    return hipSuccess;
+}
+
 static int to_pieces(v2p_batch* b)
 {
     v2p_ctx* c = b->ctx;
@@ -3115,19 +3144,20 @@ static int to_pieces(v2p_batch* b)
     a.src0_len = c->proteome_len + c->headers_len; a.src1_len = b->n_payload; a.out_len = b->out_bytes;
     a.count = reinterpret_cast<uint32_t*>(cnt.ptr()); a.base = reinterpret_cast<const uint64_t*>(basebuf.ptr());
     a.status = reinterpret_cast<unsigned long long*>(st.ptr());
-    HIP_TRY(c, launch_pieces_build(a, 0, c->stream), "launch(pieces: count)");
-    HIP_TRY(c, launch_scan_u32(a.count, nc, const_cast<uint64_t*>(a.base), reinterpret_cast<uint64_t*>(scratch.ptr()), c->stream), "launch(scan)");
     uint64_t total = 0;
     unsigned long long stw = ~0ull;
-    HIP_TRY(c, hipMemcpyAsync(&total, basebuf.ptr() + nc * 8, 8, hipMemcpyDeviceToHost, c->stream), "D2H(pieces)");
-    HIP_TRY(c, hipMemcpyAsync(&stw, st.ptr(), 8, hipMemcpyDeviceToHost, c->stream), "D2H(status)");
-    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    if (stw != ~0ull || total == 0 || total >= (1ull << 40)) return V2P_OK;            // (not converted: the dense kernel executes the image, and reports what it refuses)
-    if (b->d_pieces.ensure(total * 8) != hipSuccess || b->d_chunks2.ensure(nc * sizeof(Chunk)) != hipSuccess) { (void)hipGetLastError(); return V2P_OK; }
+    bool converted = false;
+    const char* what = "";
+    // (not converted: the dense kernel executes the image, and reports what it refuses)
+    const hipError_t e = pieces_convert(a, reinterpret_cast<uint64_t*>(scratch.ptr()), c->stream, &total, &stw, &converted, &what, [&](uint64_t n) {
+        if (n >= (1ull << 40)) return false;
+        if (b->d_pieces.ensure(n * 8) != hipSuccess || b->d_chunks2.ensure(nc * sizeof(Chunk)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        a.pieces = reinterpret_cast<uint64_t*>(b->d_pieces.ptr()); a.chunks2 = reinterpret_cast<Chunk*>(b->d_chunks2.ptr());
+        return true;
+    });
+    HIP_TRY(c, e, what);
+    if (!converted) return V2P_OK;
     b->n_pieces = total; b->pieces_src0_len = a.src0_len; b->pieces_src1_len = a.src1_len;
-    a.pieces = reinterpret_cast<uint64_t*>(b->d_pieces.ptr()); a.chunks2 = reinterpret_cast<Chunk*>(b->d_chunks2.ptr());
-    HIP_TRY(c, launch_pieces_build(a, 1, c->stream), "launch(pieces: write)");
-    HIP_TRY(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");                 // (the scratch above is released on return)
     b->pieces_state = 1;
     return V2P_OK;
 }
@@ -3890,6 +3920,58 @@ int v2p_digest_launch(void* hip_stream, const uint8_t* d_out, const uint64_t* d_
     if (!d_out || !d_hap_begin || !d_digests) return V2P_ERR_INVALID_ARG;
     DigestArgs a{d_out, d_hap_begin, n_haps, d_digests};
     return launch_digest(a, out_bytes,reinterpret_cast<hipStream_t>(hip_stream)) == hipSuccess ? V2P_OK : V2P_ERR_HIP;
+}
+
+int v2p_pieces_build_launch(void* hip_stream,
+                            const uint64_t* d_desc, uint64_t n_desc, const v2p_chunk* d_chunks, uint32_t n_chunks,
+                            uint64_t src0_len, uint64_t src1_len, uint64_t out_len,
+                            uint32_t* d_count, uint64_t* d_base, uint64_t* d_pieces, uint64_t capacity, v2p_chunk* d_chunks2,
+                            uint64_t* d_status, uint64_t* status, uint64_t* n_pieces)
+{
+    if (!d_chunks || !d_count || !d_base || !d_chunks2 || !d_status || !status || !n_pieces || (n_desc && !d_desc) || (capacity && !d_pieces)) return V2P_ERR_INVALID_ARG;
+    *status = ~0ull; *n_pieces = 0;
+    if (n_chunks == 0) return V2P_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+    DevBuf scratch;                                                  // (the scan's tile sums: the launcher's own, gone when it returns)
+    struct Rel { DevBuf& s; ~Rel() { s.release(); } } rel{scratch};
+    if (scratch.ensure_exact(scan_tiles_for(uint64_t(n_chunks) + 1) * 8 + 64) != hipSuccess) { (void)hipGetLastError(); return V2P_ERR_HIP; }
+    PieceBuildArgs a{};
+    a.desc = d_desc; a.n_desc = n_desc; a.chunks = reinterpret_cast<const Chunk*>(d_chunks); a.n_chunks = n_chunks;
+    a.src0_len = src0_len; a.src1_len = src1_len; a.out_len = out_len;
+    a.count = d_count; a.base = d_base; a.pieces = d_pieces; a.chunks2 = reinterpret_cast<Chunk*>(d_chunks2);
+    a.status = reinterpret_cast<unsigned long long*>(d_status);
+    unsigned long long stw = ~0ull;
+    bool converted = false;
+    const char* what = "";
+    const hipError_t e = pieces_convert(a, reinterpret_cast<uint64_t*>(scratch.ptr()), stream, n_pieces, &stw, &converted, &what,
+                                        [&](uint64_t n) { return n <= capacity; });
+    *status = stw;
+    return e == hipSuccess ? V2P_OK : V2P_ERR_HIP;
+}
+
+int v2p_pieces_exec_launch(void* hip_stream, const uint64_t* d_pieces, const v2p_chunk* d_chunks2, uint32_t n_chunks,
+                           const uint8_t* d_src0, const uint8_t* d_src1, uint8_t* d_out, uint64_t out_len, int nontemporal)
+{
+    if (n_chunks == 0) return V2P_OK;
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) || !d_out || !d_pieces || !d_chunks2 || !d_src0 || !d_src1) return V2P_ERR_INVALID_ARG;
+    PieceExecArgs a{d_pieces, reinterpret_cast<const Chunk*>(d_chunks2), n_chunks, d_src0, d_src1, d_out, out_len};
+    return launch_stitch_pieces(a, reinterpret_cast<hipStream_t>(hip_stream), nontemporal != 0) == hipSuccess ? V2P_OK : V2P_ERR_HIP;
+}
+
+int v2p_tiles_exec_launch(void* hip_stream, const uint64_t* d_pieces, uint32_t tile_slots, const uint32_t* d_tile_count,
+                          const uint64_t* d_tile_res_base, uint64_t n_tiles, uint64_t tile0,
+                          const uint8_t* d_src0, const uint8_t* d_src1, uint8_t* d_out, uint64_t out_len,
+                          const uint64_t* d_status, int nontemporal)
+{
+    if (tile_slots == 0u || tile_slots > TILE_SLOTS_MAX || n_tiles > 0x7FFFFFFFull) return V2P_ERR_INVALID_ARG;      // (what launch_stitch_tiles refuses)
+    if (n_tiles == 0) return V2P_OK;
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) || !d_out || !d_pieces || !d_tile_count || !d_tile_res_base || !d_src0 || !d_src1 || !d_status) return V2P_ERR_INVALID_ARG;
+    TileExecArgs a{};
+    a.pieces = d_pieces; a.tile_slots = tile_slots; a.tile_count = d_tile_count; a.tile_res_base = d_tile_res_base; a.n_tiles = n_tiles;
+    a.src0 = d_src0; a.src1 = d_src1; a.out = d_out; a.out_len = out_len;
+    a.status = reinterpret_cast<const unsigned long long*>(d_status); a.tile0 = tile0;
+    const hipError_t e = launch_stitch_tiles(a, reinterpret_cast<hipStream_t>(hip_stream), nontemporal != 0);
+    return e == hipSuccess ? V2P_OK : (e == hipErrorInvalidValue ? V2P_ERR_INVALID_ARG : V2P_ERR_HIP);
 }
 
 int v2p_stitch_launch_bits(const v2p_chunk* chunks, uint64_t n_chunks)
