@@ -119,7 +119,8 @@ def build_bench(force: bool = False, verbose: bool = False) -> str:
 
 
 HARNESS_BIN = os.path.join(LIBDIR, "v2p_harness")
-HARNESS_DEPS = [os.path.join("host", "v2p_harness.cpp"), os.path.join("host", "ppgg_gpu.hpp"), os.path.join("host", "intmap_format.hpp"), "inflate_format.hpp", "bgzf_format.hpp",
+HARNESS_SOURCES = [os.path.join("host", "v2p_harness.cpp"), os.path.join("host", "vcf_mode.cpp")]
+HARNESS_DEPS = HARNESS_SOURCES + [os.path.join("host", "vcf_mode.hpp"), os.path.join("host", "ppgg_gpu.hpp"), os.path.join("host", "intmap_format.hpp"), "inflate_format.hpp", "bgzf_format.hpp",
                 os.path.join(ROOT, "include", "vcf2prot_hip.h"), os.path.join(ROOT, "include", "v2p_cohort.h"),
                 os.path.join(ROOT, "include", "v2p_frontend.h"), os.path.join(ROOT, "include", "v2p_step4a.h"),
                 os.path.join(ROOT, "include", "v2p_step4b.h")]
@@ -128,7 +129,7 @@ HARNESS_DEPS = [os.path.join("host", "v2p_harness.cpp"), os.path.join("host", "p
 def build_harness(force: bool = False, verbose: bool = False) -> str:
     """C++ host harness (the role of the reference's exec::execute) linked against both libraries."""
     if force or _stale(HARNESS_BIN, HARNESS_DEPS) or _stale(HARNESS_BIN, [HIP_LIB, COHORT_LIB]):
-        cmd = ["g++", "-O2", "-std=c++17", "-pthread", "-Wall", os.path.join(CSRC, "host", "v2p_harness.cpp"),
+        cmd = ["g++", "-O2", "-std=c++17", "-pthread", "-Wall", *[os.path.join(CSRC, s) for s in HARNESS_SOURCES],
                "-L" + LIBDIR, "-lvcf2prot_hip", "-lv2p_cohort", "-lz", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + "/opt/rocm/lib",
                "-o", HARNESS_BIN]
         if verbose:
