@@ -479,6 +479,44 @@ int  v2p_peptides_count(const v2p_peptides*, uint64_t* n);
 int  v2p_peptides_download(v2p_peptides*, uint8_t* text, uint64_t* occ,
                            uint32_t* first_class, uint32_t* first_offset, uint64_t n);
 
+/* ---- cohort-wide variant tryptic peptides: the distinct records digested on the device (vcf2prot_amd/csrc/tryptic_digest.hip) ----
+ * Fixed per set: M missed cleavages, 0 <= M <= 4, and product lengths 1 <= MIN <= MAX <= 64.  A sequence s of n > 0 bytes has BOUNDARIES at
+ * 0, at n, and at every i in 1 .. n - 1 with s[i - 1] in {K, R} and s[i] != P (bytes are bytes: only 0x4B, 0x52 and 0x50 mean anything); an
+ * empty sequence has none.  With boundaries b_0 < ... < b_m its PRODUCTS are s[b_a, b_j) with a < j <= a + M + 1 and MIN <= b_j - b_a <= MAX.
+ * The BACKGROUND is the set of product texts of every reference sequence.  A VARIANT TRYPTIC PEPTIDE is a product text of some class's
+ * residues (never two classes', never the store's line feed) that is not in the background.  Per distinct text: occ, the sum of count[c]
+ * over every (class, offset, length) at which it is a product, and first, the smallest (class id, offset).  Peptides are delivered in
+ * ascending (first class, first offset, length).  Equality is exact on length and bytes: two texts that agree in any hash but differ are
+ * two peptides, and nothing depends on the order in which atomics arrive or on a table's size.  The rule in Python: tests/tryptic_rule.py. */
+typedef struct v2p_tryptic v2p_tryptic;
+typedef struct { uint64_t missed, min_len, max_len,
+                 n_ref_products, n_ref_peptides, ref_table_slots,       /* the background: products inserted, distinct texts, slots */
+                 n_boundaries, n_products, n_novel_products,           /* the scan: start boundaries over all classes, products probed, those not in the background, */
+                 n_peptides, text_bytes, table_slots;                  /* distinct ones, the bytes of their texts, slots */
+                 float ms_ref_build, ms_mark, ms_filter, ms_insert, ms_collect; } v2p_tryptic_info;   /* HIP events on the context's stream: the create's upload +
+                                                                               * boundaries + count + build (with the host's two looks at counts); the boundary bitmap and the
+                                                                               * list of starts (with one look); probe + count + list of novel products (with one look); table
+                                                                               * insert; first-occurrence flags + two scans + emit (with one look) */
+/* ref: HOST bytes; sequence j = ref[seq_begin[j], + seq_len[j]); builds the background on the device.  Sequences may overlap and come in
+ * any order (the device gets a copy in which they lie back to back).  hash_mask is ANDed onto the 64-bit hash of a product, from which a
+ * probe's start and a slot's tag are taken: pass ~0; tests pass small masks so that different texts share both and only the comparison of
+ * bytes keeps them apart.  V2P_ERR_INVALID_ARG: parameters outside the ranges above; a sequence whose range leaves ref (v2p_last_error_index:
+ * the sequence).  V2P_ERR_UNSUPPORTED: sequences of 2^40 bytes in all (a slot holds a position in 40 bits).  n_seq == 0 is legal: with no
+ * background every product is a variant peptide. */
+int  v2p_tryptic_create(v2p_ctx*, uint32_t missed, uint32_t min_len, uint32_t max_len, uint64_t hash_mask, const uint8_t* ref, uint64_t ref_bytes,
+                        const uint64_t* seq_begin, const uint32_t* seq_len, uint64_t n_seq, v2p_tryptic** out);
+void v2p_tryptic_destroy(v2p_tryptic*);
+/* every product of every class u holds NOW, with the classes' current counts; replaces the result of an earlier scan.  An empty set is
+ * legal.  V2P_ERR_INVALID_ARG: u belongs to another context; V2P_ERR_UNSUPPORTED: a store of 2^40 bytes.  A failed scan leaves the earlier
+ * result.  While it runs the scan holds 13 bytes per start boundary (about one store byte in ten) and 20 per novel product. */
+int  v2p_tryptic_scan(v2p_tryptic*, v2p_unique* u, v2p_tryptic_info* info);
+/* the number of peptides and the bytes of their texts; V2P_ERR_STATE before the first scan */
+int  v2p_tryptic_count(const v2p_tryptic*, uint64_t* n, uint64_t* text_bytes);
+/* n and text_bytes must be what v2p_tryptic_count gives (V2P_ERR_INVALID_ARG); peptide i is text[text_begin[i], text_begin[i + 1]);
+ * text [text_bytes], text_begin [n + 1], occ / first_class / first_offset [n]; any pointer may be NULL.  V2P_ERR_STATE before the first scan. */
+int  v2p_tryptic_download(v2p_tryptic*, uint8_t* text, uint64_t* text_begin, uint64_t* occ,
+                          uint32_t* first_class, uint32_t* first_offset, uint64_t n, uint64_t text_bytes);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.

@@ -1,4 +1,4 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]]] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]] [--write_tryptic M,MIN,MAX]] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
@@ -13,7 +13,11 @@ slice's result stays on the GPU and is deduplicated there (v2p_unique_add), <out
 
 --write_peptides K[,K...] (with --write_unique; at most eight lengths, each 1-16) adds <outdir>/variant_peptides_k{K}.tsv: the K-residue
 windows of those distinct proteins that occur in no sequence of the -r file, each once (`peptide, occurrences in haplotype records, the
-first protein that has it, 1-based position`), sorted bytewise.  The windows are filtered and deduplicated on the GPU (v2p_peptides_*)."""
+first protein that has it, 1-based position`), sorted bytewise.  The windows are filtered and deduplicated on the GPU (v2p_peptides_*).
+
+--write_tryptic M,MIN,MAX (with --write_unique; M missed cleavages 0-4, lengths 1 <= MIN <= MAX <= 64) adds <outdir>/tryptic_peptides.tsv: the
+products of a tryptic digest of those distinct proteins (cleavage after K or R unless P follows) that are no product of any sequence of the
+-r file, each once, in the same four columns, sorted bytewise.  Digested, filtered and deduplicated on the GPU (v2p_tryptic_*)."""
 import argparse
 import os
 import subprocess
@@ -42,6 +46,9 @@ def main() -> int:
     ap.add_argument("--write_peptides", metavar="K[,K...]", default=None,
                     help="with --write_unique: also write variant_peptides_k{K}.tsv, the K-residue windows of the distinct proteins that occur nowhere in the "
                          "-r proteome (filtered on the GPU); at most eight lengths, each 1-16")
+    ap.add_argument("--write_tryptic", metavar="M,MIN,MAX", default=None,
+                    help="with --write_unique: also write tryptic_peptides.tsv, the tryptic peptides of the distinct proteins (M missed cleavages, MIN to MAX "
+                         "residues) that the digest of the -r proteome does not give (digested on the GPU); M 0-4, 1 <= MIN <= MAX <= 64")
     ap.add_argument("--slice-kb", type=int, default=0, help="cut the cohort into slices of about this many KiB of FASTA text (default: 256 MiB; for tests)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
@@ -53,6 +60,12 @@ def main() -> int:
             ap.error("--write_peptides filters the distinct proteins of --write_unique: give --write_unique too")
         if not all(k.isascii() and k.isdigit() and len(k) <= 2 and 1 <= int(k) <= 16 for k in ks) or len({int(k) for k in ks}) > 8:
             ap.error("--write_peptides takes K[,K...]: at most eight window lengths, each 1-16")
+    if a.write_tryptic is not None:
+        t = a.write_tryptic.split(",")
+        if not a.write_unique:
+            ap.error("--write_tryptic digests the distinct proteins of --write_unique: give --write_unique too")
+        if len(t) != 3 or not all(x.isascii() and x.isdigit() and len(x) <= 3 for x in t) or not (int(t[0]) <= 4 and 1 <= int(t[1]) <= int(t[2]) <= 64):
+            ap.error("--write_tryptic takes M,MIN,MAX: missed cleavages 0-4 and peptide lengths 1 <= MIN <= MAX <= 64")
     from .engine import Engine
     if Engine.from_str(a.engine) is not Engine.GPU:                      # engines.rs:17-29
         sys.exit("only -g gpu is implemented here; st / mt are the reference's CPU engines")
@@ -86,6 +99,8 @@ def main() -> int:
         cmd.append("--unique")
     if a.write_peptides is not None:
         cmd += ["--peptides", a.write_peptides]
+    if a.write_tryptic is not None:
+        cmd += ["--tryptic", a.write_tryptic]
     if a.slice_kb > 0:
         cmd += ["--slice-kb", str(a.slice_kb)]
     return subprocess.run(cmd).returncode

@@ -128,6 +128,11 @@ HIP_API = {
     "v2p_peptides_scan": (c_int, [c_void_p, c_void_p, c_void_p]),
     "v2p_peptides_count": (c_int, [c_void_p, POINTER(c_uint64)]),
     "v2p_peptides_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
+    "v2p_tryptic_create": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "v2p_tryptic_destroy": (None, [c_void_p]),
+    "v2p_tryptic_scan": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "v2p_tryptic_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_tryptic_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64]),
 }
 
 _hip = None
@@ -157,6 +162,15 @@ class PeptidesInfo(ctypes.Structure):
     _fields_ = [("k", c_uint64), ("n_ref_windows", c_uint64), ("n_ref_kmers", c_uint64), ("ref_table_slots", c_uint64), ("n_windows", c_uint64),
                 ("n_novel_windows", c_uint64), ("n_peptides", c_uint64), ("table_slots", c_uint64),
                 ("ms_ref_build", ctypes.c_float), ("ms_filter", ctypes.c_float), ("ms_insert", ctypes.c_float), ("ms_collect", ctypes.c_float)]
+
+
+class TrypticInfo(ctypes.Structure):
+    """v2p_tryptic_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("missed", c_uint64), ("min_len", c_uint64), ("max_len", c_uint64), ("n_ref_products", c_uint64), ("n_ref_peptides", c_uint64),
+                ("ref_table_slots", c_uint64), ("n_boundaries", c_uint64), ("n_products", c_uint64), ("n_novel_products", c_uint64),
+                ("n_peptides", c_uint64), ("text_bytes", c_uint64), ("table_slots", c_uint64),
+                ("ms_ref_build", ctypes.c_float), ("ms_mark", ctypes.c_float), ("ms_filter", ctypes.c_float), ("ms_insert", ctypes.c_float),
+                ("ms_collect", ctypes.c_float)]
 
 
 class Routing(ctypes.Structure):

@@ -21,6 +21,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <vector>
 
@@ -51,6 +52,7 @@ using Batch = Owned<v2p_batch, v2p_batch_destroy>;
 using Pipeline = Owned<v2p_pipeline, v2p_pipeline_destroy>;
 using Unique = Owned<v2p_unique, v2p_unique_destroy>;
 using Peptides = Owned<v2p_peptides, v2p_peptides_destroy>;
+using Tryptic = Owned<v2p_tryptic, v2p_tryptic_destroy>;
 using Stream = Owned<v2p_stream, v2p_stream_destroy>;
 
 // the end of a run that cannot go on: the line is thrown, main() prints it and exits with 101
@@ -243,14 +245,29 @@ static bool parse_peptide_ks(const char* s, std::vector<uint32_t>& ks)
     return ks.size() <= 8;
 }
 
+// --tryptic M,MIN,MAX: three decimal numbers, 0 <= M <= 4 and 1 <= MIN <= MAX <= 64
+static bool parse_tryptic(const char* s, VcfOptions& o)
+{
+    uint32_t v[3];
+    const char* p = s;
+    for (int k = 0; k < 3; ++k, ++p) {
+        uint32_t digits = 0;
+        for (v[k] = 0; *p >= '0' && *p <= '9' && digits < 3; ++p, ++digits) v[k] = 10 * v[k] + uint32_t(*p - '0');
+        if (!digits || *p != (k < 2 ? ',' : '\0')) return false;
+    }
+    o.tryptic_missed = v[0]; o.tryptic_min = v[1]; o.tryptic_max = v[2];
+    return v[0] <= 4 && v[1] >= 1 && v[1] <= v[2] && v[2] <= 64;
+}
+
 bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
 {
     o.vcf_path = argv[2]; o.fasta_path = argv[3]; o.outdir = argv[4];
-    const char* peptides_arg = nullptr;
+    const char *peptides_arg = nullptr, *tryptic_arg = nullptr;
     auto is = [&](int i, const char* a, const char* b = nullptr) { return !std::strcmp(argv[i], a) || (b && !std::strcmp(argv[i], b)); };
     for (int i = 5; i < argc; ++i) {
         if (is(i, "--slice-kb") && i + 1 < argc) { const uint64_t kb = std::strtoull(argv[++i], nullptr, 10); o.slice_bytes = kb ? kb << 10 : 1; continue; }
         if (is(i, "--peptides")) { peptides_arg = i + 1 < argc ? argv[++i] : ""; continue; }
+        if (is(i, "--tryptic")) { tryptic_arg = i + 1 < argc ? argv[++i] : ""; continue; }
         o.no_test |= is(i, "--no-test");
         o.host_build |= is(i, "--host-build");
         o.host_groups |= is(i, "--host-groups");
@@ -271,6 +288,9 @@ bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
         refusal = "usage: --unique writes unique_proteins.fasta and unique_proteins.tsv from the device's record set, no per-proband file: it cannot be combined with -c, --bgzf or --host-build";
     else if (peptides_arg && (!o.unique || !parse_peptide_ks(peptides_arg, o.peptide_ks)))
         refusal = "usage: --peptides K[,K...] writes variant_peptides_k{K}.tsv from the classes of --unique: it needs --unique and at most eight window lengths, each 1 .. 16";
+    else if (tryptic_arg && (!o.unique || !parse_tryptic(tryptic_arg, o)))
+        refusal = "usage: --tryptic M,MIN,MAX writes tryptic_peptides.tsv from the classes of --unique: it needs --unique, 0 .. 4 missed cleavages and lengths 1 <= MIN <= MAX <= 64";
+    o.tryptic = tryptic_arg && !refusal;
     if (refusal) { std::fprintf(stderr, "%s\n", refusal); *exit_code = 2; }
     return !refusal;
 }
@@ -287,7 +307,7 @@ struct Report {
     float ims[3] = {}, xms[5] = {}, kms[4] = {}, tms[7] = {}, sms[2] = {}, gms[5] = {}, jms[5] = {};
     v2p_tables_info tinf{}; v2p_stats_info sinfo{}; v2p_groups_info ginfo{}; v2p_unique_info u_sum{};
     bool tables_on_device = false, device_groups = false, tasks_on_device = false, int_map_on_device = false;
-    std::string pep_json;
+    std::string pep_json, tryptic_json;
 
     void print(const VcfOptions& opt, const std::string& tasks_json) const      // tasks_json says where steps 4a / 4b ran
     {
@@ -325,6 +345,7 @@ struct Report {
                         (unsigned long long)u_sum.n_classes, (unsigned long long)u_sum.store_bytes, (unsigned long long)u_sum.table_slots,
                         (unsigned long long)u_fasta_bytes, (unsigned long long)u_tsv_bytes, u_sum.ms_digest, u_sum.ms_insert, u_sum.ms_verify, u_sum.ms_commit);
         if (!opt.peptide_ks.empty()) std::printf(", \"peptides\": {%s}", pep_json.c_str());
+        if (opt.tryptic) std::printf(", \"tryptic\": {%s}", tryptic_json.c_str());
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     }
 };
@@ -833,13 +854,26 @@ struct UniqueSink {
     // ---- --peptides K[,K...]: behind the set's files, per K the variant peptides of its classes -- the K-residue windows that occur in no
     // sequence of the -r file (every one of them, not only the transcripts the VCF touches), filtered and deduplicated on the device
     // (v2p_peptides_*) -- as variant_peptides_k{K}.tsv, sorted bytewise by peptide; class_name[c]: class c's name in unique_proteins.fasta ----
+    // every sequence of the -r file in one blob, for the backgrounds
+    void reference_blob(std::string& blob, std::vector<uint64_t>& seq_begin, std::vector<uint32_t>& seq_len) const
+    {
+        for (const auto& kv : ref) { seq_begin.push_back(blob.size()); seq_len.push_back(uint32_t(kv.second.size())); blob += kv.second; }
+        seq_begin.push_back(0); seq_len.push_back(0);
+    }
+    void write_tsv(const std::string& path, const std::string& tsv)
+    {
+        std::ofstream f(path, std::ios::binary);
+        if (f) f.write(tsv.data(), std::streamsize(tsv.size()));
+        f.close();
+        if (!f) fail("Could not write %s", path.c_str());
+        rep.written += tsv.size();
+    }
     void write_peptides(const std::vector<std::string>& class_name)
     {
         std::string blob;
         std::vector<uint64_t> seq_begin;
         std::vector<uint32_t> seq_len;
-        for (const auto& kv : ref) { seq_begin.push_back(blob.size()); seq_len.push_back(uint32_t(kv.second.size())); blob += kv.second; }
-        seq_begin.push_back(0); seq_len.push_back(0);
+        reference_blob(blob, seq_begin, seq_len);
         for (const uint32_t K : opt.peptide_ks) {
             Peptides ps;
             chk(ctx, v2p_peptides_create(ctx.raw(), K, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ps)));
@@ -857,12 +891,7 @@ struct UniqueSink {
                 tsv.append(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K);
                 tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
             }
-            const std::string path = std::string(opt.outdir) + "/variant_peptides_k" + std::to_string(K) + ".tsv";
-            std::ofstream f(path, std::ios::binary);
-            if (f) f.write(tsv.data(), std::streamsize(tsv.size()));
-            f.close();
-            if (!f) fail("Could not write %s", path.c_str());
-            rep.written += tsv.size();
+            write_tsv(std::string(opt.outdir) + "/variant_peptides_k" + std::to_string(K) + ".tsv", tsv);
             char buf[640];
             std::snprintf(buf, sizeof buf, "%s\"%u\": {\"n_ref_windows\": %llu, \"n_ref_kmers\": %llu, \"ref_table_slots\": %llu, \"n_windows\": %llu, \"n_novel_windows\": %llu, "
                           "\"n_peptides\": %llu, \"table_slots\": %llu, \"tsv_bytes\": %llu, \"ms_ref_build\": %.3f, \"ms_filter\": %.3f, \"ms_insert\": %.3f, \"ms_collect\": %.3f}",
@@ -871,6 +900,45 @@ struct UniqueSink {
                           (unsigned long long)tsv.size(), inf.ms_ref_build, inf.ms_filter, inf.ms_insert, inf.ms_collect);
             rep.pep_json += buf;
         }
+    }
+    // ---- --tryptic M,MIN,MAX: behind those, the variant tryptic peptides of the set's classes -- the products of a tryptic digest that are
+    // no product of any sequence of the -r file, digested, filtered and deduplicated on the device (v2p_tryptic_*) -- as tryptic_peptides.tsv,
+    // sorted bytewise by peptide ----
+    void write_tryptic(const std::vector<std::string>& class_name)
+    {
+        std::string blob;
+        std::vector<uint64_t> seq_begin;
+        std::vector<uint32_t> seq_len;
+        reference_blob(blob, seq_begin, seq_len);
+        Tryptic ts;
+        chk(ctx, v2p_tryptic_create(ctx.raw(), opt.tryptic_missed, opt.tryptic_min, opt.tryptic_max, ~0ull, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(),
+                                    seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ts)));
+        v2p_tryptic_info inf{};
+        chk(ctx, v2p_tryptic_scan(ts.get(), uq, &inf));
+        const uint64_t n = inf.n_peptides;
+        std::vector<uint8_t> text(inf.text_bytes + 1);
+        std::vector<uint64_t> begin(n + 2), occ(n + 1);
+        std::vector<uint32_t> fc(n + 1), fo(n + 1), order(n);
+        chk(ctx, v2p_tryptic_download(ts.get(), text.data(), begin.data(), occ.data(), fc.data(), fo.data(), n, inf.text_bytes));
+        for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
+        auto peptide = [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[begin[i]]), size_t(begin[i + 1] - begin[i])); };
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return peptide(a) < peptide(b); });   // (char_traits<char>::compare orders as bytes)
+        std::string tsv = "#peptide\toccurrences\tfirst_protein\tposition\n";
+        for (const uint32_t i : order) {
+            tsv.append(peptide(i));
+            tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/tryptic_peptides.tsv", tsv);
+        char buf[800];
+        std::snprintf(buf, sizeof buf, "\"missed\": %llu, \"min_len\": %llu, \"max_len\": %llu, \"n_ref_products\": %llu, \"n_ref_peptides\": %llu, \"ref_table_slots\": %llu, "
+                      "\"n_boundaries\": %llu, \"n_products\": %llu, \"n_novel_products\": %llu, \"n_peptides\": %llu, \"text_bytes\": %llu, \"table_slots\": %llu, "
+                      "\"tsv_bytes\": %llu, \"ms_ref_build\": %.3f, \"ms_mark\": %.3f, \"ms_filter\": %.3f, \"ms_insert\": %.3f, \"ms_collect\": %.3f",
+                      (unsigned long long)inf.missed, (unsigned long long)inf.min_len, (unsigned long long)inf.max_len, (unsigned long long)inf.n_ref_products,
+                      (unsigned long long)inf.n_ref_peptides, (unsigned long long)inf.ref_table_slots, (unsigned long long)inf.n_boundaries,
+                      (unsigned long long)inf.n_products, (unsigned long long)inf.n_novel_products, (unsigned long long)inf.n_peptides,
+                      (unsigned long long)inf.text_bytes, (unsigned long long)inf.table_slots, (unsigned long long)tsv.size(),
+                      inf.ms_ref_build, inf.ms_mark, inf.ms_filter, inf.ms_insert, inf.ms_collect);
+        rep.tryptic_json = buf;
     }
     void write_files()
     {
@@ -924,10 +992,11 @@ struct UniqueSink {
         if (!ff || !ft) fail("Could not write %s.fasta / .tsv", base.c_str());
         rep.u_fasta_bytes = out_len; rep.u_tsv_bytes = tsv.size();
         rep.written += out_len + tsv.size();
-        if (!opt.peptide_ks.empty()) {
+        if (!opt.peptide_ks.empty() || opt.tryptic) {
             std::vector<std::string> class_name(nc);
             for (uint64_t c = 0; c < nc; ++c) class_name[c] = *cname[c] + "_v" + std::to_string(k_of[c]);
-            write_peptides(class_name);
+            if (!opt.peptide_ks.empty()) write_peptides(class_name);
+            if (opt.tryptic) write_tryptic(class_name);
         }
         rep.t_write_acc += sw.seconds();
     }

@@ -9,6 +9,8 @@ struct VcfOptions {
          device_tables = false, device_index = false, int_map = false, device_int_map = false, unique = false;
     uint64_t slice_bytes = 256ull << 20;     // --slice-kb K: slices of K KiB of FASTA text (tests: several slices out of a small file)
     std::vector<uint32_t> peptide_ks;        // --peptides K[,K...]
+    bool tryptic = false;                    // --tryptic M,MIN,MAX
+    uint32_t tryptic_missed = 0, tryptic_min = 0, tryptic_max = 0;
 };
 
 // argv = {harness, "vcf", in.vcf, reference.fasta, outdir, flags...}; an argument that is no flag is ignored.  false: a combination that is

@@ -1,0 +1,674 @@
+// tryptic_digest.hip -- the variant tryptic-peptide set on gfx950 (tryptic_digest.h has the rule's device form, the hash, the tables and the
+// stages; the C ABI is v2p_tryptic_* of include/vcf2prot_hip.h).  Create: [reference bytes, sequence table] -> packed copy -> mark -> scan ->
+// one look -> list -> count -> one look -> background table.  One scan: mark -> scan -> one look -> list -> filter -> scan -> one look ->
+// compact -> insert -> firsts -> two scans -> one look -> emit.
+// Plain vector loads and stores, ordinary device-scope atomics.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/vcf2prot_hip.h"
+#include "block_scan.hpp"
+#include "device_scan.h"
+#include "tryptic_digest.h"
+#include "unique_records.h"
+#include "v2p_ctx_internal.h"
+
+namespace v2p {
+namespace {
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t word_mult(uint32_t k) { return splitmix64(k) | 1u; }
+__device__ __forceinline__ uint64_t hash_final(uint64_t h, uint32_t len, uint64_t hash_mask) { return splitmix64(h ^ (len * 0x9E3779B97F4A7C15ull)) & hash_mask; }
+// the low r bytes of a word, 1 <= r <= 8
+__device__ __forceinline__ uint64_t low_bytes(uint32_t r) { return r >= 8u ? ~0ull : (1ull << (8u * r)) - 1u; }
+
+// the aligned 8-byte word at offset a (a multiple of 8, a < limit; base is 8-byte aligned) of a buffer of `limit` bytes: one load if the
+// whole word is inside, else its bytes below `limit` (the others 0)
+__device__ __forceinline__ uint64_t load_aligned(const uint8_t* base, uint64_t a, uint64_t limit)
+{
+    if (a + 8u <= limit) return *reinterpret_cast<const uint64_t*>(base + a);
+    uint64_t v = 0;
+    for (uint64_t i = a; i < limit; ++i) v |= uint64_t(base[i]) << (8u * uint32_t(i - a));
+    return v;
+}
+
+// the 8 bytes at base[pos ..), pos < limit, little-endian; bytes at or beyond `limit` are 0
+__device__ __forceinline__ uint64_t load_word(const uint8_t* base, uint64_t limit, uint64_t pos)
+{
+    const uint32_t sh = uint32_t(pos) & 7u;
+    const uint64_t a = pos - sh;
+    const uint64_t lo = load_aligned(base, a, limit);
+    if (sh == 0u) return lo;
+    const uint64_t hi = a + 8u < limit ? load_aligned(base, a + 8u, limit) : 0ull;
+    return (lo >> (8u * sh)) | (hi << (64u - 8u * sh));
+}
+
+// the last entry of begin[lo .. hi] that is <= p (begin ascends, begin[lo] <= p)
+__device__ __forceinline__ uint64_t last_at_or_before(const unsigned long long* begin, uint64_t lo, uint64_t hi, uint64_t p)
+{
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1u) >> 1;
+        if (begin[mid] <= p) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// the sequences of a tile's first and last byte, found by thread 0 for every lane to search between
+__device__ __forceinline__ void tile_classes(const TryText& t, uint64_t tile0, uint64_t* s_range)
+{
+    if (threadIdx.x == 0) {
+        const uint64_t last = (tile0 + TRY_TILE < t.n_bytes ? tile0 + TRY_TILE : t.n_bytes) - 1u;
+        s_range[0] = last_at_or_before(t.begin, 0, t.n_seq - 1u, tile0);
+        s_range[1] = last_at_or_before(t.begin, s_range[0], t.n_seq - 1u, last);
+    }
+}
+
+__device__ __forceinline__ bool is_start(const TryText& t, uint64_t p) { return p < t.n_bytes && ((t.marks[p >> 6] >> (p & 63u)) & 1u); }
+
+// The next boundaries of start boundary p of sequence c, at most missed + 1 of them and none beyond p + max_len: bit i stands for the
+// boundary at p + 1 + i, which ends a product of i + 1 bytes.  The sequence's end is the last of them.
+__device__ __forceinline__ uint64_t next_boundaries(const TryText& t, const TryParams& par, uint64_t p, uint64_t c)
+{
+    const uint64_t span = t.begin[c] + t.len[c] - p;                 // bytes from p to the sequence's end, >= 1
+    const uint32_t s = uint32_t(p) & 63u;
+    const uint64_t w0 = t.marks[p >> 6], w1 = t.marks[(p >> 6) + 1u];   // (the bitmap has a word behind its last tile)
+    uint64_t bits = s == 63u ? w1 : (w0 >> (s + 1u)) | (w1 << (63u - s));
+    const uint64_t inside = span - 1u < par.max_len ? span - 1u : par.max_len;   // boundaries inside the sequence sit at p + 1 .. p + inside
+    bits &= inside >= 64u ? ~0ull : (1ull << inside) - 1u;
+    if (span <= par.max_len) bits |= 1ull << (span - 1u);
+    uint64_t kept = 0;
+    for (uint32_t j = 0; j <= par.missed && bits; ++j) {
+        const uint64_t low = bits & (0 - bits);
+        kept |= low; bits ^= low;
+    }
+    return kept;
+}
+// ... of which these end a product (bit L - 1: a product of L bytes)
+__device__ __forceinline__ uint64_t product_ends(const TryParams& par, uint64_t kept) { return kept & ~((1ull << (par.min_len - 1u)) - 1u); }
+
+// f(L, bit, hash) for every product of start p in ascending length; ends: its product mask.  The sum over whole words is carried along.
+template <class F>
+__device__ __forceinline__ void for_products(const TryText& t, const TryParams& par, uint64_t p, uint64_t ends, F f)
+{
+    if (!ends) return;
+    uint64_t sum = 0, word = load_word(t.bytes, t.n_bytes, p);
+    uint32_t k = 0;
+    while (ends) {
+        const uint32_t i = uint32_t(__builtin_ctzll(ends));
+        const uint64_t bit = 1ull << i;
+        ends ^= bit;
+        while (k < (i >> 3)) {                                       // (byte p + 8 k <= p + i lies inside the product: inside the buffer)
+            sum += word_mult(k) * word;
+            ++k;
+            word = load_word(t.bytes, t.n_bytes, p + 8u * k);
+        }
+        const uint64_t h = sum + word_mult(k) * (word & low_bytes((i & 7u) + 1u));
+        f(i + 1u, bit, hash_final(h, i + 1u, par.hash_mask));
+    }
+}
+
+__device__ __forceinline__ uint64_t hash_of(const TryText& t, const TryParams& par, uint64_t p, uint32_t len)
+{
+    uint64_t out = 0;
+    for_products(t, par, p, 1ull << (len - 1u), [&](uint32_t, uint64_t, uint64_t h) { out = h; });
+    return out;
+}
+
+__device__ __forceinline__ bool texts_equal(const TryText& x, uint64_t px, const TryText& y, uint64_t py, uint32_t len)
+{
+    for (uint32_t o = 0; o < len; o += 8u) {
+        const uint64_t d = load_word(x.bytes, x.n_bytes, px + o) ^ load_word(y.bytes, y.n_bytes, py + o);
+        if (d & low_bytes(len - o)) return false;
+    }
+    return true;
+}
+
+__device__ __forceinline__ unsigned long long slot_word(uint64_t h, uint32_t len, uint64_t p)
+{
+    return ((h >> TRY_TAG_SHIFT) << TRY_TAG_SHIFT) | (uint64_t(len - 1u) << TRY_POS_BITS) | p;
+}
+
+// the slot of the product t[p, p + len) with hash h: claimed, or found taken by an equal text (whose position is lowered to p if p is
+// smaller).  *claimed: this call took an empty slot.  ~0: no slot (a table more than full: never, with half the slots free).
+__device__ __forceinline__ uint64_t table_insert(const TryTable tb, const TryText& t, uint64_t p, uint32_t len, uint64_t h, bool* claimed)
+{
+    const unsigned long long mine = slot_word(h, len, p);
+    uint64_t i = h & tb.slot_mask;
+    for (uint64_t probe = 0; probe <= tb.slot_mask; ++probe, i = (i + 1u) & tb.slot_mask) {
+        unsigned long long v = __hip_atomic_load(&tb.slots[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v == TRY_EMPTY) {
+            v = atomicCAS(&tb.slots[i], TRY_EMPTY, mine);
+            if (v == TRY_EMPTY) { *claimed = true; return i; }
+        }
+        if ((v ^ mine) >> TRY_POS_BITS) continue;                    // another tag or length: another text
+        if (texts_equal(t, p, t, v & TRY_POS_MASK, len)) {           // (any representative a slot ever had holds the slot's text)
+            if (mine < v) atomicMin(&tb.slots[i], mine);
+            return i;
+        }
+    }
+    return ~0ull;
+}
+
+// read-only, behind a launch boundary: is the product t[p, p + len) with hash h a text of the table over `ref`?
+__device__ __forceinline__ bool table_holds(const TryTable tb, const TryText& ref, const TryText& t, uint64_t p, uint32_t len, uint64_t h)
+{
+    const unsigned long long mine = slot_word(h, len, 0);
+    uint64_t i = h & tb.slot_mask;
+    for (uint64_t probe = 0; probe <= tb.slot_mask; ++probe, i = (i + 1u) & tb.slot_mask) {
+        const unsigned long long v = tb.slots[i];
+        if (v == TRY_EMPTY) return false;
+        if ((v ^ mine) >> TRY_POS_BITS) continue;
+        if (texts_equal(t, p, ref, v & TRY_POS_MASK, len)) return true;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(TRY_THREADS) void try_mark_kernel(TryScanArgs a)
+{
+    __shared__ uint64_t s_range[2];
+    __shared__ uint32_t s_n;
+    const TryText& t = a.text;
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;          // (the grid has a block per tile that begins inside the text)
+    if (threadIdx.x == 0) s_n = 0;
+    tile_classes(t, tile0, s_range);
+    __syncthreads();
+    const uint64_t c_lo = s_range[0], c_hi = s_range[1];
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t p = tile0 + step * TRY_THREADS + threadIdx.x;
+        bool start = false;
+        if (p < t.n_bytes) {
+            const uint64_t c = last_at_or_before(t.begin, c_lo, c_hi, p);
+            const uint64_t off = p - t.begin[c];
+            if (off < t.len[c]) {                                    // (a class's line feed sits at off == len: in no sequence)
+                if (off == 0) start = true;
+                else {
+                    const uint8_t before = t.bytes[p - 1u], own = t.bytes[p];   // (off > 0: p - 1 is a byte of the same sequence)
+                    start = (before == 0x4Bu || before == 0x52u) && own != 0x50u;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(start);
+        if ((threadIdx.x & 63u) == 0u) {
+            a.marks_out[p >> 6] = m;                                 // (p is the wave's first position, a multiple of 64; marks covers whole tiles)
+            if (m) atomicAdd(&s_n, uint32_t(__popcll(m)));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.tile_count[blockIdx.x] = s_n;
+}
+
+// the start boundaries of a tile, listed behind those of the tiles before it, each with its sequence
+__global__ __launch_bounds__(TRY_THREADS) void try_list_kernel(TryScanArgs a)
+{
+    __shared__ uint64_t s_range[2];
+    __shared__ uint32_t scratch[TRY_THREADS / 64];
+    const TryText& t = a.text;
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;
+    uint64_t at = a.tile_begin[blockIdx.x];
+    if (a.tile_begin[blockIdx.x + 1] == at) return;                  // (the whole workgroup)
+    tile_classes(t, tile0, s_range);
+    __syncthreads();
+    const uint64_t c_lo = s_range[0], c_hi = s_range[1];
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t p = tile0 + step * TRY_THREADS + threadIdx.x;
+        const bool start = is_start(t, p);
+        uint32_t total;
+        const uint64_t o = at + block_excl_scan<TRY_THREADS>(start ? 1u : 0u, scratch, &total);
+        if (start && o < t.n_starts) { a.start_pos_out[o] = p; a.start_seq_out[o] = uint32_t(last_at_or_before(t.begin, c_lo, c_hi, p)); }
+        at += total;
+    }
+}
+
+enum { MODE_COUNT = 0, MODE_BUILD = 1, MODE_FILTER = 2 };
+
+// a lane per start boundary of a.text; its products are counted / put into a.table / looked up in a.ref_table
+template <int MODE>
+__global__ __launch_bounds__(TRY_THREADS) void try_products_kernel(TryScanArgs a)
+{
+    __shared__ uint32_t s_products, s_hits;                          // s_hits: slots claimed (build) / novel products (filter)
+    const TryText& t = a.text;
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;          // (the grid has a block per tile of the list of starts)
+    if (threadIdx.x == 0) s_products = s_hits = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t i = tile0 + step * TRY_THREADS + threadIdx.x;
+        uint64_t kept = 0, p = 0;
+        if (i < t.n_starts) { p = t.start_pos[i]; kept = next_boundaries(t, a.par, p, t.start_seq[i]); }
+        const uint64_t ends = product_ends(a.par, kept);
+        uint32_t hits = 0, novel = 0;
+        bool lost = false;
+        if (MODE == MODE_BUILD)
+            for_products(t, a.par, p, ends, [&](uint32_t len, uint64_t, uint64_t h) {
+                bool claimed = false;
+                if (table_insert(a.table, t, p, len, h, &claimed) == ~0ull) lost = true;
+                hits += claimed ? 1u : 0u;
+            });
+        if (MODE == MODE_FILTER) {
+            for_products(t, a.par, p, ends, [&](uint32_t len, uint64_t bit, uint64_t h) {
+                if (!table_holds(a.ref_table, a.ref, t, p, len, h)) novel |= 1u << __popcll(kept & (bit - 1u));   // (its ordinal among the next boundaries)
+            });
+            hits = uint32_t(__popc(novel));
+            if (i < t.n_starts) a.novel[i] = uint8_t(novel);
+        }
+        if (ends) atomicAdd(&s_products, uint32_t(__popcll(ends)));
+        if (hits) atomicAdd(&s_hits, hits);
+        if (lost) atomicAdd(&a.status[TRY_ST_FULL], 1ull);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_products) atomicAdd(&a.status[TRY_ST_PRODUCTS], (unsigned long long)s_products);
+        if (MODE == MODE_BUILD && s_hits) atomicAdd(&a.status[TRY_ST_CLAIMED], (unsigned long long)s_hits);
+        if (MODE == MODE_FILTER) a.tile_count[blockIdx.x] = s_hits;
+    }
+}
+
+__global__ __launch_bounds__(TRY_THREADS) void try_compact_kernel(TryScanArgs a)
+{
+    __shared__ uint32_t scratch[TRY_THREADS / 64];
+    const TryText& t = a.text;
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;
+    uint64_t at = a.tile_begin[blockIdx.x];
+    if (a.tile_begin[blockIdx.x + 1] == at) return;                  // (the whole workgroup)
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t s = tile0 + step * TRY_THREADS + threadIdx.x;
+        const uint32_t novel = s < t.n_starts ? a.novel[s] : 0u;
+        uint32_t total;
+        uint64_t o = at + block_excl_scan<TRY_THREADS>(uint32_t(__popc(novel)), scratch, &total);
+        if (novel) {
+            const uint64_t p = t.start_pos[s];
+            const uint32_t c = t.start_seq[s];
+            uint64_t kept = next_boundaries(t, a.par, p, c);
+            for (uint32_t ord = 0; kept; ++ord) {                    // ascending length
+                const uint32_t i = uint32_t(__builtin_ctzll(kept));
+                kept ^= 1ull << i;
+                if (!((novel >> ord) & 1u)) continue;
+                if (o < a.n_novel) { a.item[o] = (uint64_t(i) << TRY_POS_BITS) | p; a.cls[o] = c; }
+                ++o;
+            }
+        }
+        at += total;
+    }
+}
+
+__global__ __launch_bounds__(TRY_THREADS) void try_insert_kernel(TryScanArgs a)
+{
+    const uint64_t j = uint64_t(blockIdx.x) * TRY_THREADS + threadIdx.x;
+    if (j >= a.n_novel) return;
+    const uint64_t p = a.item[j] & TRY_POS_MASK;
+    const uint32_t len = uint32_t(a.item[j] >> TRY_POS_BITS) + 1u;
+    bool claimed = false;
+    const uint64_t i = table_insert(a.table, a.text, p, len, hash_of(a.text, a.par, p, len), &claimed);
+    if (i == ~0ull) { a.slot_of[j] = 0; atomicAdd(&a.status[TRY_ST_FULL], 1ull); return; }
+    a.slot_of[j] = i;
+    atomicAdd(&a.occ[i], a.cls_count[a.cls[j]]);
+}
+
+// entry j of the list is its peptide's first occurrence: the slot it settled in ended with its position
+__device__ __forceinline__ bool is_first(const TryScanArgs& a, uint64_t j)
+{
+    return j < a.n_novel && ((a.table.slots[a.slot_of[j]] ^ a.item[j]) & TRY_POS_MASK) == 0;
+}
+
+__global__ __launch_bounds__(TRY_THREADS) void try_firsts_kernel(TryScanArgs a)
+{
+    __shared__ uint32_t s_n, s_bytes;
+    if (threadIdx.x == 0) s_n = s_bytes = 0;
+    __syncthreads();
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t j = tile0 + step * TRY_THREADS + threadIdx.x;
+        if (is_first(a, j)) { atomicAdd(&s_n, 1u); atomicAdd(&s_bytes, uint32_t(a.item[j] >> TRY_POS_BITS) + 1u); }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { a.tile_count[blockIdx.x] = s_n; a.tile_bytes[blockIdx.x] = s_bytes; }
+}
+
+__global__ __launch_bounds__(TRY_THREADS) void try_emit_kernel(TryScanArgs a)
+{
+    __shared__ uint32_t scratch[TRY_THREADS / 64];
+    const TryText& t = a.text;
+    const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;
+    uint64_t at = a.tile_begin[blockIdx.x], text_at = a.tile_text[blockIdx.x];
+    const uint64_t end = a.tile_begin[blockIdx.x + 1], text_end = a.tile_text[blockIdx.x + 1];
+    if (end == at) return;
+#pragma unroll 1
+    for (uint32_t step = 0; step < TRY_STEPS; ++step) {
+        const uint64_t j = tile0 + step * TRY_THREADS + threadIdx.x;
+        const bool first = is_first(a, j);
+        const uint32_t len = first ? uint32_t(a.item[j] >> TRY_POS_BITS) + 1u : 0u;
+        uint32_t total, total_bytes;
+        const uint64_t e = at + block_excl_scan<TRY_THREADS>(first ? 1u : 0u, scratch, &total);
+        const uint64_t x = text_at + block_excl_scan<TRY_THREADS>(len, scratch, &total_bytes);
+        if (first && e < end && x + len <= text_end) {
+            const uint64_t p = a.item[j] & TRY_POS_MASK;
+            const uint32_t c = a.cls[j];
+            for (uint32_t o = 0; o < len; o += 8u) {
+                const uint64_t w = load_word(t.bytes, t.n_bytes, p + o);
+                for (uint32_t b = 0; b < 8u && o + b < len; ++b) a.out_text[x + o + b] = uint8_t(w >> (8u * b));
+            }
+            a.out_text_begin[e] = x;
+            a.out_occ[e] = a.occ[a.slot_of[j]];
+            a.out_class[e] = c;
+            a.out_offset[e] = uint32_t(p - t.begin[c]);
+        }
+        at += total; text_at += total_bytes;
+    }
+}
+
+inline dim3 grid_of(uint64_t blocks) { return dim3(uint32_t(blocks)); }
+
+}  // namespace
+
+#define TRY_LAUNCH(kernel, blocks, a) do { if (blocks) kernel<<<grid_of(blocks), TRY_THREADS, 0, st>>>(a); return hipGetLastError(); } while (0)
+hipError_t launch_try_mark(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_mark_kernel, try_tiles(a.text.n_bytes), a); }
+hipError_t launch_try_list(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_list_kernel, try_tiles(a.text.n_bytes), a); }
+hipError_t launch_try_count(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_COUNT>, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_build(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_BUILD>, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_filter(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_FILTER>, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_compact(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_compact_kernel, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_insert(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_insert_kernel, (a.n_novel + TRY_THREADS - 1) / TRY_THREADS, a); }
+hipError_t launch_try_firsts(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_firsts_kernel, try_tiles(a.n_novel), a); }
+hipError_t launch_try_emit(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_emit_kernel, try_tiles(a.n_novel), a); }
+
+}  // namespace v2p
+
+// ---- the C ABI -------------------------------------------------------------------------------------------------------------------
+using namespace v2p;
+
+struct v2p_tryptic {
+    v2p_ctx* ctx = nullptr;
+    TryParams par{};
+    uint64_t ref_bytes = 0, n_seq = 0, n_ref_products = 0, n_ref_peptides = 0, ref_table_slots = 0;
+    float ms_ref_build = 0.f;
+    DevMem ref, ref_slots, status;
+    // the last scan's result
+    bool scanned = false;
+    uint64_t n_peptides = 0, text_bytes = 0;
+    DevMem text, text_begin, occ, first_class, first_offset;
+    Events<5> ev;
+};
+
+namespace {
+
+struct CtxLock {
+    v2p_ctx* c;
+    explicit CtxLock(v2p_ctx* ctx) : c(ctx) { ctx_lock(c); }
+    ~CtxLock() { ctx_unlock(c); }
+};
+
+int hip_fail(v2p_ctx* c, hipError_t e, const char* what) { return ctx_fail(c, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), -1); }
+#define T_TRY(expr, what) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return hip_fail(c, e__, what); } while (0)
+
+// a power of two, at least twice n and at least 64
+uint64_t slots_for(uint64_t n)
+{
+    uint64_t s = 64;
+    while (s < 2 * n) s *= 2;
+    return s;
+}
+size_t some(uint64_t bytes) { return size_t(bytes ? bytes : 16); }   // (no allocation of nothing)
+uint64_t mark_words(uint64_t n_bytes) { return 16 * try_tiles(n_bytes) + 1; }
+
+// what list_starts makes for a text
+struct Starts { DevMem marks, tile_count, tile_begin, pos, seq; uint64_t n = 0; };
+
+// mark -> scan -> ONE look at the number of starts -> list: a.text gets its bitmap and its list of start boundaries (a.status is zero)
+int list_starts(v2p_ctx* c, TryScanArgs& a, Starts& s, hipStream_t st)
+{
+    const uint64_t tiles = try_tiles(a.text.n_bytes);
+    T_TRY(s.marks.alloc(8 * mark_words(a.text.n_bytes)), "hipMalloc(tryptic boundaries)");
+    T_TRY(s.tile_count.alloc(some(4 * tiles)), "hipMalloc(tryptic tiles)");
+    T_TRY(s.tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(tryptic tiles)");
+    a.text.marks = a.marks_out = s.marks.get<unsigned long long>();
+    a.tile_count = s.tile_count.get<uint32_t>(); a.tile_begin = s.tile_begin.get<unsigned long long>();
+    T_TRY(hipMemsetAsync(a.marks_out, 0, 8 * mark_words(a.text.n_bytes), st), "hipMemset(tryptic boundaries)");
+    T_TRY(launch_try_mark(a, st), "launch(tryptic mark)");
+    T_TRY(launch_device_scan(a.tile_count, uint32_t(tiles), s.tile_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_BOUNDARIES, st), "launch(scan)");
+    unsigned long long n = 0;
+    T_TRY(hipMemcpyAsync(&n, a.status + TRY_ST_BOUNDARIES, 8, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    s.n = n;
+    T_TRY(s.pos.alloc(some(8 * s.n)), "hipMalloc(tryptic starts)");
+    T_TRY(s.seq.alloc(some(4 * s.n)), "hipMalloc(tryptic starts)");
+    a.text.start_pos = a.start_pos_out = s.pos.get<unsigned long long>(); a.text.start_seq = a.start_seq_out = s.seq.get<uint32_t>(); a.text.n_starts = s.n;
+    if (s.n) T_TRY(launch_try_list(a, st), "launch(tryptic list)");
+    return V2P_OK;
+}
+
+// packed: the sequences back to back; begin [n_seq] where each starts in it
+int build_background(v2p_tryptic* t, const std::vector<uint8_t>& packed, const std::vector<unsigned long long>& begin, const uint32_t* seq_len)
+{
+    v2p_ctx* c = t->ctx;
+    hipStream_t st = ctx_stream(c);
+    const uint64_t n_seq = t->n_seq;
+    DevMem d_begin, d_len;                                   // the sequence table and the list of starts: for the build alone
+    Starts starts;
+    T_TRY(t->ev.create(), "hipEventCreate");
+    T_TRY(t->status.alloc(8 * TRY_ST_WORDS), "hipMalloc(tryptic status)");
+    T_TRY(t->ref.alloc(some(t->ref_bytes)), "hipMalloc(tryptic reference)");
+    T_TRY(d_begin.alloc(some(8 * n_seq)), "hipMalloc(tryptic sequences)");
+    T_TRY(d_len.alloc(some(4 * n_seq)), "hipMalloc(tryptic sequences)");
+    T_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
+    if (t->ref_bytes) T_TRY(hipMemcpyAsync(t->ref.get<void>(), packed.data(), t->ref_bytes, hipMemcpyHostToDevice, st), "H2D(reference)");
+    if (n_seq) {
+        T_TRY(hipMemcpyAsync(d_begin.get<void>(), begin.data(), 8 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
+        T_TRY(hipMemcpyAsync(d_len.get<void>(), seq_len, 4 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
+    }
+    T_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    TryScanArgs a{};
+    a.par = t->par;
+    a.text = TryText{t->ref.get<uint8_t>(), t->ref_bytes, d_begin.get<unsigned long long>(), d_len.get<uint32_t>(), n_seq, nullptr, nullptr, nullptr, 0};
+    a.status = t->status.get<unsigned long long>();
+    const int rc = list_starts(c, a, starts, st);
+    if (rc != V2P_OK) return rc;
+    unsigned long long h_status[TRY_ST_WORDS];
+    T_TRY(launch_try_count(a, st), "launch(tryptic count)");
+    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    t->n_ref_products = h_status[TRY_ST_PRODUCTS];
+    t->ref_table_slots = slots_for(t->n_ref_products);
+    T_TRY(t->ref_slots.alloc(8 * t->ref_table_slots), "hipMalloc(tryptic background)");
+    T_TRY(hipMemsetAsync(t->ref_slots.get<void>(), 0xFF, 8 * t->ref_table_slots, st), "hipMemset(tryptic background)");
+    T_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    a.table = TryTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
+    T_TRY(launch_try_build(a, st), "launch(tryptic build)");
+    T_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
+    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (h_status[TRY_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the background table is full (internal)", -1);
+    t->n_ref_peptides = h_status[TRY_ST_CLAIMED];
+    (void)hipEventElapsedTime(&t->ms_ref_build, t->ev[0], t->ev[1]);
+    return V2P_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2p_tryptic_create(v2p_ctx* c, uint32_t missed, uint32_t min_len, uint32_t max_len, uint64_t hash_mask, const uint8_t* ref, uint64_t ref_bytes,
+                       const uint64_t* seq_begin, const uint32_t* seq_len, uint64_t n_seq, v2p_tryptic** out)
+{
+    if (!c || !out) return V2P_ERR_INVALID_ARG;
+    *out = nullptr;
+    CtxLock lk(c);
+    if (missed > TRY_MAX_MISSED || min_len == 0 || min_len > max_len || max_len > TRY_MAX_LEN)
+        return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_create: missed cleavages 0 .. 4 and lengths 1 <= min <= max <= 64", -1);
+    if ((n_seq && (!seq_begin || !seq_len)) || (ref_bytes && !ref)) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_create: null argument", -1);
+    if (n_seq >= (1ull << 31)) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_create: 2^31 sequences", -1);
+    uint64_t total = 0;                                      // (below 2^63: fewer than 2^31 lengths of 32 bits)
+    for (uint64_t j = 0; j < n_seq; ++j) {
+        if (seq_len[j] > ref_bytes || seq_begin[j] > ref_bytes - seq_len[j])
+            return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_create: a sequence's range leaves the reference", int64_t(j));
+        total += seq_len[j];
+    }
+    // the slot's position field holds 40 bits: a longer reference would wrap
+    if (total >= TRY_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_create: reference sequences of 2^40 bytes", -1);
+    // the device digests a text of sequences in ascending order that share no byte: the host packs them back to back
+    std::vector<uint8_t> packed;
+    std::vector<unsigned long long> begin;
+    try { packed.resize(total); begin.resize(n_seq); } catch (...) { return ctx_fail(c, V2P_ERR_HIP, "out of host memory", -1); }
+    total = 0;
+    for (uint64_t j = 0; j < n_seq; ++j) {
+        begin[j] = total;
+        if (seq_len[j]) std::memcpy(packed.data() + total, ref + seq_begin[j], seq_len[j]);
+        total += seq_len[j];
+    }
+    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    v2p_tryptic* t = new (std::nothrow) v2p_tryptic();
+    if (!t) return ctx_fail(c, V2P_ERR_HIP, "out of host memory", -1);
+    t->ctx = c; t->par = TryParams{missed, min_len, max_len, hash_mask}; t->ref_bytes = total; t->n_seq = n_seq;
+    const int rc = build_background(t, packed, begin, seq_len);
+    if (rc != V2P_OK) { (void)hipStreamSynchronize(ctx_stream(c)); delete t; return rc; }
+    *out = t;
+    return V2P_OK;
+}
+
+void v2p_tryptic_destroy(v2p_tryptic* t)
+{
+    if (!t) return;
+    CtxLock lk(t->ctx);
+    (void)hipSetDevice(ctx_device(t->ctx));
+    (void)hipStreamSynchronize(ctx_stream(t->ctx));
+    delete t;
+}
+
+int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
+{
+    if (!t || !u) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = t->ctx;
+    CtxLock lk(c);
+    UniqueStoreView uv;
+    unique_store_view(u, &uv);
+    if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_scan: the tryptic set and the record set belong to different contexts", -1);
+    if (uv.store_bytes >= TRY_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: a store of 2^40 bytes", -1);
+    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    hipStream_t st = ctx_stream(c);
+    // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
+    Starts starts;
+    DevMem novel, start_count, start_begin, list_count, list_begin, tile_bytes, tile_text, item, cls, slot_of, slots, occ, text, text_begin, out_occ, out_class, out_offset;
+    TryScanArgs a{};
+    a.par = t->par;
+    a.text = TryText{uv.store, uv.store_bytes, uv.cls.store_begin, uv.cls.len, uv.n_classes, nullptr, nullptr, nullptr, 0};
+    a.ref = TryText{t->ref.get<uint8_t>(), t->ref_bytes, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0};   // (a probe compares bytes: it needs no sequence)
+    a.ref_table = TryTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
+    a.cls_count = uv.cls.count;
+    a.status = t->status.get<unsigned long long>();
+    unsigned long long h_status[TRY_ST_WORDS];
+    T_TRY(hipMemsetAsync(a.status, 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    T_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
+    // the start boundaries: bitmap, count, list
+    const int rc = list_starts(c, a, starts, st);
+    if (rc != V2P_OK) return rc;
+    T_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
+    // filter: every product of every start probed in the background; the novel ones counted per tile of starts, listed in (position, length) order
+    const uint64_t start_tiles = try_tiles(starts.n);
+    T_TRY(novel.alloc(some(starts.n)), "hipMalloc(tryptic flags)");
+    T_TRY(start_count.alloc(some(4 * start_tiles)), "hipMalloc(tryptic tiles)");
+    T_TRY(start_begin.alloc(8 * (start_tiles + 1)), "hipMalloc(tryptic tiles)");
+    a.novel = novel.get<uint8_t>(); a.tile_count = start_count.get<uint32_t>(); a.tile_begin = start_begin.get<unsigned long long>();
+    T_TRY(launch_try_filter(a, st), "launch(tryptic filter)");
+    T_TRY(launch_device_scan(a.tile_count, uint32_t(start_tiles), start_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_NOVEL, st), "launch(scan)");
+    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    const uint64_t n_boundaries = h_status[TRY_ST_BOUNDARIES], n_products = h_status[TRY_ST_PRODUCTS], n_novel = h_status[TRY_ST_NOVEL];
+    a.n_novel = n_novel;
+    const uint64_t table_slots = slots_for(n_novel), list_tiles = try_tiles(n_novel);
+    if (list_tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: 2^42 novel products", -1);
+    T_TRY(item.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
+    T_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(tryptic list)");
+    T_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
+    T_TRY(list_count.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");      // (a start has up to five products: the list may have more tiles than the starts)
+    T_TRY(list_begin.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
+    T_TRY(tile_bytes.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");
+    T_TRY(tile_text.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
+    T_TRY(slots.alloc(8 * table_slots), "hipMalloc(tryptic table)");
+    T_TRY(occ.alloc(8 * table_slots), "hipMalloc(tryptic table)");
+    a.item = item.get<unsigned long long>(); a.cls = cls.get<uint32_t>(); a.slot_of = slot_of.get<unsigned long long>();
+    a.tile_bytes = tile_bytes.get<uint32_t>(); a.tile_text = tile_text.get<unsigned long long>();
+    a.table = TryTable{slots.get<unsigned long long>(), table_slots - 1}; a.occ = occ.get<unsigned long long>();
+    if (n_novel) T_TRY(launch_try_compact(a, st), "launch(tryptic compact)");
+    T_TRY(hipEventRecord(t->ev[2], st), "hipEventRecord");
+    // insert: the smallest position and the summed class counts per distinct text
+    T_TRY(hipMemsetAsync(a.table.slots, 0xFF, 8 * table_slots, st), "hipMemset(tryptic table)");
+    T_TRY(hipMemsetAsync(a.occ, 0, 8 * table_slots, st), "hipMemset(tryptic table)");
+    T_TRY(launch_try_insert(a, st), "launch(tryptic insert)");
+    T_TRY(hipEventRecord(t->ev[3], st), "hipEventRecord");
+    // collect: the list entries that are their peptide's first occurrence, in list order; peptide ids and text offsets from two scans
+    a.tile_count = list_count.get<uint32_t>(); a.tile_begin = list_begin.get<unsigned long long>();
+    T_TRY(launch_try_firsts(a, st), "launch(tryptic firsts)");
+    T_TRY(launch_device_scan(a.tile_count, uint32_t(list_tiles), list_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_PEPTIDES, st), "launch(scan)");
+    T_TRY(launch_device_scan(a.tile_bytes, uint32_t(list_tiles), tile_text.get<unsigned long long>(), nullptr, a.status + TRY_ST_TEXT, st), "launch(scan)");
+    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (h_status[TRY_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the peptide table is full (internal)", -1);
+    const uint64_t n_peptides = h_status[TRY_ST_PEPTIDES], text_bytes = h_status[TRY_ST_TEXT];
+    T_TRY(text.alloc(some(text_bytes)), "hipMalloc(tryptic result)");
+    T_TRY(text_begin.alloc(8 * (n_peptides + 1)), "hipMalloc(tryptic result)");
+    T_TRY(out_occ.alloc(some(8 * n_peptides)), "hipMalloc(tryptic result)");
+    T_TRY(out_class.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
+    T_TRY(out_offset.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
+    a.out_text = text.get<uint8_t>(); a.out_text_begin = text_begin.get<unsigned long long>(); a.out_occ = out_occ.get<unsigned long long>();
+    a.out_class = out_class.get<uint32_t>(); a.out_offset = out_offset.get<uint32_t>();
+    if (n_peptides) T_TRY(launch_try_emit(a, st), "launch(tryptic emit)");
+    const unsigned long long h_end = text_bytes;
+    T_TRY(hipMemcpyAsync(a.out_text_begin + n_peptides, &h_end, 8, hipMemcpyHostToDevice, st), "H2D(tryptic result)");
+    T_TRY(hipEventRecord(t->ev[4], st), "hipEventRecord");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    t->text = std::move(text); t->text_begin = std::move(text_begin); t->occ = std::move(out_occ);
+    t->first_class = std::move(out_class); t->first_offset = std::move(out_offset);
+    t->n_peptides = n_peptides; t->text_bytes = text_bytes; t->scanned = true;
+    if (info) {
+        float ms[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&ms[k], t->ev[k], t->ev[k + 1]);
+        *info = v2p_tryptic_info{t->par.missed, t->par.min_len, t->par.max_len, t->n_ref_products, t->n_ref_peptides, t->ref_table_slots,
+                                 n_boundaries, n_products, n_novel, n_peptides, text_bytes, table_slots, t->ms_ref_build, ms[0], ms[1], ms[2], ms[3]};
+    }
+    return V2P_OK;
+}
+
+int v2p_tryptic_count(const v2p_tryptic* t, uint64_t* n, uint64_t* text_bytes)
+{
+    if (!t) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(t->ctx);
+    if (!t->scanned) return ctx_fail(t->ctx, V2P_ERR_STATE, "v2p_tryptic_count: no scan yet", -1);
+    if (n) *n = t->n_peptides;
+    if (text_bytes) *text_bytes = t->text_bytes;
+    return V2P_OK;
+}
+
+int v2p_tryptic_download(v2p_tryptic* t, uint8_t* text, uint64_t* text_begin, uint64_t* occ, uint32_t* first_class, uint32_t* first_offset, uint64_t n,
+                         uint64_t text_bytes)
+{
+    if (!t) return V2P_ERR_INVALID_ARG;
+    v2p_ctx* c = t->ctx;
+    CtxLock lk(c);
+    if (!t->scanned) return ctx_fail(c, V2P_ERR_STATE, "v2p_tryptic_download: no scan yet", -1);
+    if (n != t->n_peptides || text_bytes != t->text_bytes)
+        return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_download: n or text_bytes is not what v2p_tryptic_count gives", -1);
+    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    hipStream_t st = ctx_stream(c);
+    if (text && text_bytes) T_TRY(hipMemcpyAsync(text, t->text.get<void>(), text_bytes, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (text_begin) T_TRY(hipMemcpyAsync(text_begin, t->text_begin.get<void>(), 8 * (n + 1), hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (occ && n) T_TRY(hipMemcpyAsync(occ, t->occ.get<void>(), 8 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (first_class && n) T_TRY(hipMemcpyAsync(first_class, t->first_class.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (first_offset && n) T_TRY(hipMemcpyAsync(first_offset, t->first_offset.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return V2P_OK;
+}
+
+}  // extern "C"

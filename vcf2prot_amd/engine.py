@@ -656,6 +656,75 @@ class PeptideSet:
         return {"text": text[:n], "occ": occ[:n], "first_class": cls[:n], "first_offset": off[:n]}
 
 
+class TrypticSet:
+    """One ``v2p_tryptic``: the tryptic products (cleavage after K or R unless P follows, ``missed`` missed cleavages, ``min_len`` ..
+    ``max_len`` bytes) of a UniqueSet's classes that are no product of any reference sequence, each once, digested, filtered and
+    deduplicated on the device (the rule: tests/tryptic_rule.py).  ``reference``: the sequences as bytes.  ``hash_mask`` is for tests."""
+
+    def __init__(self, ctx: Context, missed: int, min_len: int, max_len: int, reference: Sequence[bytes] = (), hash_mask: int = 2 ** 64 - 1):
+        self.ctx, self.params, self.hash_mask = ctx, (missed, min_len, max_len), hash_mask
+        self._lib = ctx._lib
+        reference = [bytes(s) for s in reference]
+        lens = np.asarray([len(s) for s in reference] + [0], np.uint32)
+        begin = np.zeros(len(reference) + 1, np.uint64)
+        begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(reference) + b"\0", np.uint8)
+        self._create(blob, int(begin[-1]), begin, lens, len(reference))
+
+    def _create(self, blob: np.ndarray, ref_bytes: int, begin: np.ndarray, lens: np.ndarray, n_seq: int):
+        """v2p_tryptic_create on the arrays as given (tests hand it ranges that leave the reference)"""
+        h = ctypes.c_void_p()
+        self._h = None
+        self.ctx._check(self._lib.v2p_tryptic_create(self.ctx._h, *self.params, self.hash_mask, blob.ctypes.data, ref_bytes, begin.ctypes.data,
+                                                     lens.ctypes.data, n_seq, ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_arrays(cls, ctx: Context, missed: int, min_len: int, max_len: int, blob: np.ndarray, seq_begin, seq_len, hash_mask: int = 2 ** 64 - 1) -> "TrypticSet":
+        """the reference as one uint8 array and a sequence table (sequences may overlap)"""
+        self = cls.__new__(cls)
+        self.ctx, self.params, self.hash_mask, self._lib = ctx, (missed, min_len, max_len), hash_mask, ctx._lib
+        blob = np.ascontiguousarray(blob, np.uint8)
+        begin, lens = np.ascontiguousarray(seq_begin, np.uint64), np.ascontiguousarray(seq_len, np.uint32)
+        pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
+        self._create(pad(blob), int(blob.size), pad(begin), pad(lens), int(begin.size))
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._lib.v2p_tryptic_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scan(self, uset: "UniqueSet") -> dict:
+        """v2p_tryptic_scan: every product of every class the set holds now; returns the info."""
+        info = N.TrypticInfo()
+        self.ctx._check(self._lib.v2p_tryptic_scan(self._h, uset._h, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in N.TrypticInfo._fields_}
+
+    def count(self) -> Tuple[int, int]:
+        """(peptides, bytes of their texts)"""
+        n, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_tryptic_count(self._h, ctypes.byref(n), ctypes.byref(nbytes)))
+        return int(n.value), int(nbytes.value)
+
+    def download(self, n: Optional[int] = None, text_bytes: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_tryptic_download: text, text_begin [n + 1], occ, first_class, first_offset, in ascending (first_class, first_offset, length)."""
+        if n is None or text_bytes is None:
+            have = self.count()
+            n, text_bytes = (have[0] if n is None else n), (have[1] if text_bytes is None else text_bytes)
+        text, begin = np.zeros(text_bytes + 1, np.uint8), np.zeros(n + 2, np.uint64)
+        occ, cls, off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32)
+        self.ctx._check(self._lib.v2p_tryptic_download(self._h, text.ctypes.data, begin.ctypes.data, occ.ctypes.data, cls.ctypes.data, off.ctypes.data,
+                                                       n, text_bytes))
+        return {"text": text[:text_bytes], "text_begin": begin[:n + 1], "occ": occ[:n], "first_class": cls[:n], "first_offset": off[:n]}
+
+
 def default_context() -> Context:
     global _default_ctx
     if _default_ctx is None or _default_ctx._h is None:
