@@ -855,10 +855,13 @@ struct UniqueSink {
     // sequence of the -r file (every one of them, not only the transcripts the VCF touches), filtered and deduplicated on the device
     // (v2p_peptides_*) -- as variant_peptides_k{K}.tsv, sorted bytewise by peptide; class_name[c]: class c's name in unique_proteins.fasta ----
     // every sequence of the -r file in one blob, for the backgrounds
-    void reference_blob(std::string& blob, std::vector<uint64_t>& seq_begin, std::vector<uint32_t>& seq_len) const
+    struct RefBlob { std::string blob; std::vector<uint64_t> seq_begin; std::vector<uint32_t> seq_len; };
+    RefBlob reference_blob() const
     {
-        for (const auto& kv : ref) { seq_begin.push_back(blob.size()); seq_len.push_back(uint32_t(kv.second.size())); blob += kv.second; }
-        seq_begin.push_back(0); seq_len.push_back(0);
+        RefBlob r;
+        for (const auto& kv : ref) { r.seq_begin.push_back(r.blob.size()); r.seq_len.push_back(uint32_t(kv.second.size())); r.blob += kv.second; }
+        r.seq_begin.push_back(0); r.seq_len.push_back(0);
+        return r;
     }
     void write_tsv(const std::string& path, const std::string& tsv)
     {
@@ -868,12 +871,23 @@ struct UniqueSink {
         if (!f) fail("Could not write %s", path.c_str());
         rep.written += tsv.size();
     }
+    // the TSV of n peptides, peptide(i) -> string_view the i-th one's bytes, sorted bytewise by peptide (char_traits<char>::compare orders as bytes)
+    template <class Peptide>
+    static std::string peptide_tsv(uint64_t n, Peptide peptide, const std::vector<uint64_t>& occ, const std::vector<uint32_t>& fc, const std::vector<uint32_t>& fo, const std::vector<std::string>& class_name)
+    {
+        std::vector<uint32_t> order(n);
+        for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return peptide(a) < peptide(b); });
+        std::string tsv = "#peptide\toccurrences\tfirst_protein\tposition\n";
+        for (const uint32_t i : order) {
+            tsv.append(peptide(i));
+            tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
+        }
+        return tsv;
+    }
     void write_peptides(const std::vector<std::string>& class_name)
     {
-        std::string blob;
-        std::vector<uint64_t> seq_begin;
-        std::vector<uint32_t> seq_len;
-        reference_blob(blob, seq_begin, seq_len);
+        const auto [blob, seq_begin, seq_len] = reference_blob();
         for (const uint32_t K : opt.peptide_ks) {
             Peptides ps;
             chk(ctx, v2p_peptides_create(ctx.raw(), K, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ps)));
@@ -882,15 +896,9 @@ struct UniqueSink {
             const uint64_t n = inf.n_peptides;
             std::vector<uint8_t> text(n * K + 1);
             std::vector<uint64_t> occ(n + 1);
-            std::vector<uint32_t> fc(n + 1), fo(n + 1), order(n);
+            std::vector<uint32_t> fc(n + 1), fo(n + 1);
             chk(ctx, v2p_peptides_download(ps.get(), text.data(), occ.data(), fc.data(), fo.data(), n));
-            for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
-            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::memcmp(&text[uint64_t(a) * K], &text[uint64_t(b) * K], K) < 0; });
-            std::string tsv = "#peptide\toccurrences\tfirst_protein\tposition\n";
-            for (const uint32_t i : order) {
-                tsv.append(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K);
-                tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
-            }
+            const std::string tsv = peptide_tsv(n, [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K); }, occ, fc, fo, class_name);
             write_tsv(std::string(opt.outdir) + "/variant_peptides_k" + std::to_string(K) + ".tsv", tsv);
             char buf[640];
             std::snprintf(buf, sizeof buf, "%s\"%u\": {\"n_ref_windows\": %llu, \"n_ref_kmers\": %llu, \"ref_table_slots\": %llu, \"n_windows\": %llu, \"n_novel_windows\": %llu, "
@@ -906,10 +914,7 @@ struct UniqueSink {
     // sorted bytewise by peptide ----
     void write_tryptic(const std::vector<std::string>& class_name)
     {
-        std::string blob;
-        std::vector<uint64_t> seq_begin;
-        std::vector<uint32_t> seq_len;
-        reference_blob(blob, seq_begin, seq_len);
+        const auto [blob, seq_begin, seq_len] = reference_blob();
         Tryptic ts;
         chk(ctx, v2p_tryptic_create(ctx.raw(), opt.tryptic_missed, opt.tryptic_min, opt.tryptic_max, ~0ull, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(),
                                     seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ts)));
@@ -918,16 +923,10 @@ struct UniqueSink {
         const uint64_t n = inf.n_peptides;
         std::vector<uint8_t> text(inf.text_bytes + 1);
         std::vector<uint64_t> begin(n + 2), occ(n + 1);
-        std::vector<uint32_t> fc(n + 1), fo(n + 1), order(n);
+        std::vector<uint32_t> fc(n + 1), fo(n + 1);
         chk(ctx, v2p_tryptic_download(ts.get(), text.data(), begin.data(), occ.data(), fc.data(), fo.data(), n, inf.text_bytes));
-        for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
-        auto peptide = [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[begin[i]]), size_t(begin[i + 1] - begin[i])); };
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return peptide(a) < peptide(b); });   // (char_traits<char>::compare orders as bytes)
-        std::string tsv = "#peptide\toccurrences\tfirst_protein\tposition\n";
-        for (const uint32_t i : order) {
-            tsv.append(peptide(i));
-            tsv += "\t" + std::to_string(occ[i]) + "\t" + class_name[fc[i]] + "\t" + std::to_string(fo[i] + 1u) + "\n";
-        }
+        const std::string tsv = peptide_tsv(n, [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[begin[i]]), size_t(begin[i + 1] - begin[i])); },
+                                            occ, fc, fo, class_name);
         write_tsv(std::string(opt.outdir) + "/tryptic_peptides.tsv", tsv);
         char buf[800];
         std::snprintf(buf, sizeof buf, "\"missed\": %llu, \"min_len\": %llu, \"max_len\": %llu, \"n_ref_products\": %llu, \"n_ref_peptides\": %llu, \"ref_table_slots\": %llu, "

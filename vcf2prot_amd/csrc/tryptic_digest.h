@@ -24,12 +24,9 @@
 // ALIGNED 8-byte loads; the one aligned word that reaches beyond the buffer's last byte is read byte by byte, so no byte outside the
 // buffer is read.  `hash_mask` is ANDed onto the hash before anything is taken from it (tests force shared starts and tags).
 //
-// Both tables (the BACKGROUND of reference products, built once per set; the PEPTIDE table of one scan): open addressing, linear probing
-// from the hash's low bits, 64-bit slots, TRY_EMPTY or [18 bits of the hash | 6 bits: length - 1 | 40 bits: position of a representative
-// in its text].  A slot is claimed by CAS and never becomes empty; a lane that meets a taken slot compares tag and length, then the
-// representative's bytes, and moves on if they differ -- so equal texts always meet in one slot, and texts that agree in every bit of the
-// hash stay apart.  atomicMin lowers the position (tag and length of equal texts are equal, so the whole word orders by position).  occ
-// is an integer atomicAdd of the class's count into a counter beside the slot.
+// Both tables (the BACKGROUND of reference products, built once per set; the PEPTIDE table of one scan) are set_table.hpp's slot tables,
+// probed from the hash; a slot word is [18 bits of the hash | 6 bits: length - 1 | 40 bits: position of a representative in its text],
+// and "the same text" is equality of the representative's bytes (texts_equal).
 //
 // One scan: mark -> scan -> one look at the number of starts -> list -> filter (every product of a start probed in the background; a byte
 // per start says which of its products are novel, a count per tile of starts how many) -> scan -> one look -> compact (the novel products
@@ -39,19 +36,18 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "set_table.hpp"
+
 namespace v2p {
 
-constexpr unsigned long long TRY_EMPTY = ~0ull;
 constexpr uint32_t TRY_POS_BITS = 40, TRY_LEN_BITS = 6, TRY_TAG_SHIFT = TRY_POS_BITS + TRY_LEN_BITS;
 constexpr unsigned long long TRY_POS_MASK = (1ull << TRY_POS_BITS) - 1u;
-constexpr unsigned long long TRY_MAX_BYTES = TRY_POS_MASK;   // a text stays below this: a position fits its field, and no [tag | length | position] equals TRY_EMPTY
+constexpr unsigned long long TRY_MAX_BYTES = TRY_POS_MASK;   // a text stays below this: a position fits its field, and no [tag | length | position] equals SLOT_EMPTY
 constexpr uint32_t TRY_MAX_MISSED = 4, TRY_MAX_LEN = 64;
 constexpr uint32_t TRY_THREADS = 256;
 constexpr uint32_t TRY_STEPS = 4;
 constexpr uint32_t TRY_TILE = TRY_THREADS * TRY_STEPS;       // positions (or list entries) per workgroup
 enum { TRY_ST_BOUNDARIES = 0, TRY_ST_PRODUCTS = 1, TRY_ST_NOVEL = 2, TRY_ST_CLAIMED = 3, TRY_ST_PEPTIDES = 4, TRY_ST_TEXT = 5, TRY_ST_FULL = 6, TRY_ST_WORDS = 7 };
-
-struct TryTable { unsigned long long* slots; uint64_t slot_mask; };
 
 struct TryText {                       // a buffer and its sequences
     const uint8_t* bytes; uint64_t n_bytes;        // bytes is 16-byte aligned
@@ -65,7 +61,7 @@ struct TryParams { uint32_t missed, min_len, max_len; uint64_t hash_mask; };
 struct TryScanArgs {
     TryParams par;
     TryText text;                      // the text that is digested: the reference (count, build) or the store
-    TryText ref; TryTable ref_table;   // the background (filter)
+    TryText ref; SlotTable ref_table;   // the background (filter)
     unsigned long long* marks_out; unsigned long long* start_pos_out; uint32_t* start_seq_out;   // (mark, list) text.marks, text.start_*, writable
     uint8_t* novel;                    // [text.n_starts] bit j: the product that ends at the (j + 1)-th next boundary of this start is novel
     uint32_t* tile_count;              // [tiles of the bytes] starts of a tile; [tiles of the starts] novel products; [tiles of the list] first occurrences
@@ -74,7 +70,7 @@ struct TryScanArgs {
     const unsigned long long* tile_text;    // [list tiles + 1] ... of tile_bytes
     unsigned long long* item; uint32_t* cls; unsigned long long* slot_of; uint64_t n_novel;   // the novel products, ascending: (length - 1) << 40 | position
     const unsigned long long* cls_count;
-    TryTable table; unsigned long long* occ;                                                  // the table under construction, a counter per slot
+    SlotTable table; unsigned long long* occ;                                                  // the table under construction, a counter per slot
     uint8_t* out_text; unsigned long long* out_text_begin; unsigned long long* out_occ; uint32_t* out_class; uint32_t* out_offset;
     unsigned long long* status;        // [TRY_ST_WORDS]
 };

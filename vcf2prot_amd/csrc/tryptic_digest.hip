@@ -20,13 +20,6 @@
 namespace v2p {
 namespace {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ uint64_t word_mult(uint32_t k) { return splitmix64(k) | 1u; }
 __device__ __forceinline__ uint64_t hash_final(uint64_t h, uint32_t len, uint64_t hash_mask) { return splitmix64(h ^ (len * 0x9E3779B97F4A7C15ull)) & hash_mask; }
 // the low r bytes of a word, 1 <= r <= 8
@@ -51,26 +44,6 @@ __device__ __forceinline__ uint64_t load_word(const uint8_t* base, uint64_t limi
     if (sh == 0u) return lo;
     const uint64_t hi = a + 8u < limit ? load_aligned(base, a + 8u, limit) : 0ull;
     return (lo >> (8u * sh)) | (hi << (64u - 8u * sh));
-}
-
-// the last entry of begin[lo .. hi] that is <= p (begin ascends, begin[lo] <= p)
-__device__ __forceinline__ uint64_t last_at_or_before(const unsigned long long* begin, uint64_t lo, uint64_t hi, uint64_t p)
-{
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1u) >> 1;
-        if (begin[mid] <= p) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
-
-// the sequences of a tile's first and last byte, found by thread 0 for every lane to search between
-__device__ __forceinline__ void tile_classes(const TryText& t, uint64_t tile0, uint64_t* s_range)
-{
-    if (threadIdx.x == 0) {
-        const uint64_t last = (tile0 + TRY_TILE < t.n_bytes ? tile0 + TRY_TILE : t.n_bytes) - 1u;
-        s_range[0] = last_at_or_before(t.begin, 0, t.n_seq - 1u, tile0);
-        s_range[1] = last_at_or_before(t.begin, s_range[0], t.n_seq - 1u, last);
-    }
 }
 
 __device__ __forceinline__ bool is_start(const TryText& t, uint64_t p) { return p < t.n_bytes && ((t.marks[p >> 6] >> (p & 63u)) & 1u); }
@@ -140,37 +113,15 @@ __device__ __forceinline__ unsigned long long slot_word(uint64_t h, uint32_t len
 
 // the slot of the product t[p, p + len) with hash h: claimed, or found taken by an equal text (whose position is lowered to p if p is
 // smaller).  *claimed: this call took an empty slot.  ~0: no slot (a table more than full: never, with half the slots free).
-__device__ __forceinline__ uint64_t table_insert(const TryTable tb, const TryText& t, uint64_t p, uint32_t len, uint64_t h, bool* claimed)
+__device__ __forceinline__ uint64_t table_insert(const SlotTable tb, const TryText& t, uint64_t p, uint32_t len, uint64_t h, bool* claimed)
 {
-    const unsigned long long mine = slot_word(h, len, p);
-    uint64_t i = h & tb.slot_mask;
-    for (uint64_t probe = 0; probe <= tb.slot_mask; ++probe, i = (i + 1u) & tb.slot_mask) {
-        unsigned long long v = __hip_atomic_load(&tb.slots[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v == TRY_EMPTY) {
-            v = atomicCAS(&tb.slots[i], TRY_EMPTY, mine);
-            if (v == TRY_EMPTY) { *claimed = true; return i; }
-        }
-        if ((v ^ mine) >> TRY_POS_BITS) continue;                    // another tag or length: another text
-        if (texts_equal(t, p, t, v & TRY_POS_MASK, len)) {           // (any representative a slot ever had holds the slot's text)
-            if (mine < v) atomicMin(&tb.slots[i], mine);
-            return i;
-        }
-    }
-    return ~0ull;
+    return slot_insert<TRY_POS_BITS>(tb, h, slot_word(h, len, p), [&](uint64_t at) { return texts_equal(t, p, t, at, len); }, claimed);
 }
 
 // read-only, behind a launch boundary: is the product t[p, p + len) with hash h a text of the table over `ref`?
-__device__ __forceinline__ bool table_holds(const TryTable tb, const TryText& ref, const TryText& t, uint64_t p, uint32_t len, uint64_t h)
+__device__ __forceinline__ bool table_holds(const SlotTable tb, const TryText& ref, const TryText& t, uint64_t p, uint32_t len, uint64_t h)
 {
-    const unsigned long long mine = slot_word(h, len, 0);
-    uint64_t i = h & tb.slot_mask;
-    for (uint64_t probe = 0; probe <= tb.slot_mask; ++probe, i = (i + 1u) & tb.slot_mask) {
-        const unsigned long long v = tb.slots[i];
-        if (v == TRY_EMPTY) return false;
-        if ((v ^ mine) >> TRY_POS_BITS) continue;
-        if (texts_equal(t, p, ref, v & TRY_POS_MASK, len)) return true;
-    }
-    return false;
+    return slot_holds<TRY_POS_BITS>(tb, h, slot_word(h, len, 0), [&](uint64_t at) { return texts_equal(t, p, ref, at, len); });
 }
 
 __global__ __launch_bounds__(TRY_THREADS) void try_mark_kernel(TryScanArgs a)
@@ -180,7 +131,7 @@ __global__ __launch_bounds__(TRY_THREADS) void try_mark_kernel(TryScanArgs a)
     const TryText& t = a.text;
     const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;          // (the grid has a block per tile that begins inside the text)
     if (threadIdx.x == 0) s_n = 0;
-    tile_classes(t, tile0, s_range);
+    tile_range(t.begin, t.n_seq, t.n_bytes, tile0, TRY_TILE, s_range);
     __syncthreads();
     const uint64_t c_lo = s_range[0], c_hi = s_range[1];
 #pragma unroll 1
@@ -217,7 +168,7 @@ __global__ __launch_bounds__(TRY_THREADS) void try_list_kernel(TryScanArgs a)
     const uint64_t tile0 = uint64_t(blockIdx.x) * TRY_TILE;
     uint64_t at = a.tile_begin[blockIdx.x];
     if (a.tile_begin[blockIdx.x + 1] == at) return;                  // (the whole workgroup)
-    tile_classes(t, tile0, s_range);
+    tile_range(t.begin, t.n_seq, t.n_bytes, tile0, TRY_TILE, s_range);
     __syncthreads();
     const uint64_t c_lo = s_range[0], c_hi = s_range[1];
 #pragma unroll 1
@@ -370,20 +321,17 @@ __global__ __launch_bounds__(TRY_THREADS) void try_emit_kernel(TryScanArgs a)
     }
 }
 
-inline dim3 grid_of(uint64_t blocks) { return dim3(uint32_t(blocks)); }
-
 }  // namespace
 
-#define TRY_LAUNCH(kernel, blocks, a) do { if (blocks) kernel<<<grid_of(blocks), TRY_THREADS, 0, st>>>(a); return hipGetLastError(); } while (0)
-hipError_t launch_try_mark(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_mark_kernel, try_tiles(a.text.n_bytes), a); }
-hipError_t launch_try_list(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_list_kernel, try_tiles(a.text.n_bytes), a); }
-hipError_t launch_try_count(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_COUNT>, try_tiles(a.text.n_starts), a); }
-hipError_t launch_try_build(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_BUILD>, try_tiles(a.text.n_starts), a); }
-hipError_t launch_try_filter(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_products_kernel<MODE_FILTER>, try_tiles(a.text.n_starts), a); }
-hipError_t launch_try_compact(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_compact_kernel, try_tiles(a.text.n_starts), a); }
-hipError_t launch_try_insert(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_insert_kernel, (a.n_novel + TRY_THREADS - 1) / TRY_THREADS, a); }
-hipError_t launch_try_firsts(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_firsts_kernel, try_tiles(a.n_novel), a); }
-hipError_t launch_try_emit(const TryScanArgs& a, hipStream_t st) { TRY_LAUNCH(try_emit_kernel, try_tiles(a.n_novel), a); }
+hipError_t launch_try_mark(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_mark_kernel, TRY_THREADS, try_tiles(a.text.n_bytes), a); }
+hipError_t launch_try_list(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_list_kernel, TRY_THREADS, try_tiles(a.text.n_bytes), a); }
+hipError_t launch_try_count(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_products_kernel<MODE_COUNT>, TRY_THREADS, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_build(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_products_kernel<MODE_BUILD>, TRY_THREADS, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_filter(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_products_kernel<MODE_FILTER>, TRY_THREADS, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_compact(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_compact_kernel, TRY_THREADS, try_tiles(a.text.n_starts), a); }
+hipError_t launch_try_insert(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_insert_kernel, TRY_THREADS, (a.n_novel + TRY_THREADS - 1) / TRY_THREADS, a); }
+hipError_t launch_try_firsts(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_firsts_kernel, TRY_THREADS, try_tiles(a.n_novel), a); }
+hipError_t launch_try_emit(const TryScanArgs& a, hipStream_t st) { SET_LAUNCH(try_emit_kernel, TRY_THREADS, try_tiles(a.n_novel), a); }
 
 }  // namespace v2p
 
@@ -405,23 +353,6 @@ struct v2p_tryptic {
 
 namespace {
 
-struct CtxLock {
-    v2p_ctx* c;
-    explicit CtxLock(v2p_ctx* ctx) : c(ctx) { ctx_lock(c); }
-    ~CtxLock() { ctx_unlock(c); }
-};
-
-int hip_fail(v2p_ctx* c, hipError_t e, const char* what) { return ctx_fail(c, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), -1); }
-#define T_TRY(expr, what) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return hip_fail(c, e__, what); } while (0)
-
-// a power of two, at least twice n and at least 64
-uint64_t slots_for(uint64_t n)
-{
-    uint64_t s = 64;
-    while (s < 2 * n) s *= 2;
-    return s;
-}
-size_t some(uint64_t bytes) { return size_t(bytes ? bytes : 16); }   // (no allocation of nothing)
 uint64_t mark_words(uint64_t n_bytes) { return 16 * try_tiles(n_bytes) + 1; }
 
 // what list_starts makes for a text
@@ -431,22 +362,22 @@ struct Starts { DevMem marks, tile_count, tile_begin, pos, seq; uint64_t n = 0; 
 int list_starts(v2p_ctx* c, TryScanArgs& a, Starts& s, hipStream_t st)
 {
     const uint64_t tiles = try_tiles(a.text.n_bytes);
-    T_TRY(s.marks.alloc(8 * mark_words(a.text.n_bytes)), "hipMalloc(tryptic boundaries)");
-    T_TRY(s.tile_count.alloc(some(4 * tiles)), "hipMalloc(tryptic tiles)");
-    T_TRY(s.tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(s.marks.alloc(8 * mark_words(a.text.n_bytes)), "hipMalloc(tryptic boundaries)");
+    V2P_TRY(s.tile_count.alloc(some(4 * tiles)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(s.tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(tryptic tiles)");
     a.text.marks = a.marks_out = s.marks.get<unsigned long long>();
     a.tile_count = s.tile_count.get<uint32_t>(); a.tile_begin = s.tile_begin.get<unsigned long long>();
-    T_TRY(hipMemsetAsync(a.marks_out, 0, 8 * mark_words(a.text.n_bytes), st), "hipMemset(tryptic boundaries)");
-    T_TRY(launch_try_mark(a, st), "launch(tryptic mark)");
-    T_TRY(launch_device_scan(a.tile_count, uint32_t(tiles), s.tile_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_BOUNDARIES, st), "launch(scan)");
+    V2P_TRY(hipMemsetAsync(a.marks_out, 0, 8 * mark_words(a.text.n_bytes), st), "hipMemset(tryptic boundaries)");
+    V2P_TRY(launch_try_mark(a, st), "launch(tryptic mark)");
+    V2P_TRY(launch_device_scan(a.tile_count, uint32_t(tiles), s.tile_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_BOUNDARIES, st), "launch(scan)");
     unsigned long long n = 0;
-    T_TRY(hipMemcpyAsync(&n, a.status + TRY_ST_BOUNDARIES, 8, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(hipMemcpyAsync(&n, a.status + TRY_ST_BOUNDARIES, 8, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     s.n = n;
-    T_TRY(s.pos.alloc(some(8 * s.n)), "hipMalloc(tryptic starts)");
-    T_TRY(s.seq.alloc(some(4 * s.n)), "hipMalloc(tryptic starts)");
+    V2P_TRY(s.pos.alloc(some(8 * s.n)), "hipMalloc(tryptic starts)");
+    V2P_TRY(s.seq.alloc(some(4 * s.n)), "hipMalloc(tryptic starts)");
     a.text.start_pos = a.start_pos_out = s.pos.get<unsigned long long>(); a.text.start_seq = a.start_seq_out = s.seq.get<uint32_t>(); a.text.n_starts = s.n;
-    if (s.n) T_TRY(launch_try_list(a, st), "launch(tryptic list)");
+    if (s.n) V2P_TRY(launch_try_list(a, st), "launch(tryptic list)");
     return V2P_OK;
 }
 
@@ -458,18 +389,18 @@ int build_background(v2p_tryptic* t, const std::vector<uint8_t>& packed, const s
     const uint64_t n_seq = t->n_seq;
     DevMem d_begin, d_len;                                   // the sequence table and the list of starts: for the build alone
     Starts starts;
-    T_TRY(t->ev.create(), "hipEventCreate");
-    T_TRY(t->status.alloc(8 * TRY_ST_WORDS), "hipMalloc(tryptic status)");
-    T_TRY(t->ref.alloc(some(t->ref_bytes)), "hipMalloc(tryptic reference)");
-    T_TRY(d_begin.alloc(some(8 * n_seq)), "hipMalloc(tryptic sequences)");
-    T_TRY(d_len.alloc(some(4 * n_seq)), "hipMalloc(tryptic sequences)");
-    T_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
-    if (t->ref_bytes) T_TRY(hipMemcpyAsync(t->ref.get<void>(), packed.data(), t->ref_bytes, hipMemcpyHostToDevice, st), "H2D(reference)");
+    V2P_TRY(t->ev.create(), "hipEventCreate");
+    V2P_TRY(t->status.alloc(8 * TRY_ST_WORDS), "hipMalloc(tryptic status)");
+    V2P_TRY(t->ref.alloc(some(t->ref_bytes)), "hipMalloc(tryptic reference)");
+    V2P_TRY(d_begin.alloc(some(8 * n_seq)), "hipMalloc(tryptic sequences)");
+    V2P_TRY(d_len.alloc(some(4 * n_seq)), "hipMalloc(tryptic sequences)");
+    V2P_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
+    if (t->ref_bytes) V2P_TRY(hipMemcpyAsync(t->ref.get<void>(), packed.data(), t->ref_bytes, hipMemcpyHostToDevice, st), "H2D(reference)");
     if (n_seq) {
-        T_TRY(hipMemcpyAsync(d_begin.get<void>(), begin.data(), 8 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
-        T_TRY(hipMemcpyAsync(d_len.get<void>(), seq_len, 4 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
+        V2P_TRY(hipMemcpyAsync(d_begin.get<void>(), begin.data(), 8 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
+        V2P_TRY(hipMemcpyAsync(d_len.get<void>(), seq_len, 4 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
     }
-    T_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    V2P_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
     TryScanArgs a{};
     a.par = t->par;
     a.text = TryText{t->ref.get<uint8_t>(), t->ref_bytes, d_begin.get<unsigned long long>(), d_len.get<uint32_t>(), n_seq, nullptr, nullptr, nullptr, 0};
@@ -477,19 +408,19 @@ int build_background(v2p_tryptic* t, const std::vector<uint8_t>& packed, const s
     const int rc = list_starts(c, a, starts, st);
     if (rc != V2P_OK) return rc;
     unsigned long long h_status[TRY_ST_WORDS];
-    T_TRY(launch_try_count(a, st), "launch(tryptic count)");
-    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_try_count(a, st), "launch(tryptic count)");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     t->n_ref_products = h_status[TRY_ST_PRODUCTS];
     t->ref_table_slots = slots_for(t->n_ref_products);
-    T_TRY(t->ref_slots.alloc(8 * t->ref_table_slots), "hipMalloc(tryptic background)");
-    T_TRY(hipMemsetAsync(t->ref_slots.get<void>(), 0xFF, 8 * t->ref_table_slots, st), "hipMemset(tryptic background)");
-    T_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
-    a.table = TryTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
-    T_TRY(launch_try_build(a, st), "launch(tryptic build)");
-    T_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
-    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(t->ref_slots.alloc(8 * t->ref_table_slots), "hipMalloc(tryptic background)");
+    V2P_TRY(hipMemsetAsync(t->ref_slots.get<void>(), 0xFF, 8 * t->ref_table_slots, st), "hipMemset(tryptic background)");
+    V2P_TRY(hipMemsetAsync(t->status.get<void>(), 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    a.table = SlotTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
+    V2P_TRY(launch_try_build(a, st), "launch(tryptic build)");
+    V2P_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (h_status[TRY_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the background table is full (internal)", -1);
     t->n_ref_peptides = h_status[TRY_ST_CLAIMED];
     (void)hipEventElapsedTime(&t->ms_ref_build, t->ev[0], t->ev[1]);
@@ -528,7 +459,7 @@ int v2p_tryptic_create(v2p_ctx* c, uint32_t missed, uint32_t min_len, uint32_t m
         if (seq_len[j]) std::memcpy(packed.data() + total, ref + seq_begin[j], seq_len[j]);
         total += seq_len[j];
     }
-    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     v2p_tryptic* t = new (std::nothrow) v2p_tryptic();
     if (!t) return ctx_fail(c, V2P_ERR_HIP, "out of host memory", -1);
     t->ctx = c; t->par = TryParams{missed, min_len, max_len, hash_mask}; t->ref_bytes = total; t->n_seq = n_seq;
@@ -556,7 +487,7 @@ int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
     unique_store_view(u, &uv);
     if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_scan: the tryptic set and the record set belong to different contexts", -1);
     if (uv.store_bytes >= TRY_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: a store of 2^40 bytes", -1);
-    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
     // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
     Starts starts;
@@ -565,70 +496,70 @@ int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
     a.par = t->par;
     a.text = TryText{uv.store, uv.store_bytes, uv.cls.store_begin, uv.cls.len, uv.n_classes, nullptr, nullptr, nullptr, 0};
     a.ref = TryText{t->ref.get<uint8_t>(), t->ref_bytes, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0};   // (a probe compares bytes: it needs no sequence)
-    a.ref_table = TryTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
+    a.ref_table = SlotTable{t->ref_slots.get<unsigned long long>(), t->ref_table_slots - 1};
     a.cls_count = uv.cls.count;
     a.status = t->status.get<unsigned long long>();
     unsigned long long h_status[TRY_ST_WORDS];
-    T_TRY(hipMemsetAsync(a.status, 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
-    T_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
+    V2P_TRY(hipMemsetAsync(a.status, 0, 8 * TRY_ST_WORDS, st), "hipMemset(tryptic status)");
+    V2P_TRY(hipEventRecord(t->ev[0], st), "hipEventRecord");
     // the start boundaries: bitmap, count, list
     const int rc = list_starts(c, a, starts, st);
     if (rc != V2P_OK) return rc;
-    T_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
+    V2P_TRY(hipEventRecord(t->ev[1], st), "hipEventRecord");
     // filter: every product of every start probed in the background; the novel ones counted per tile of starts, listed in (position, length) order
     const uint64_t start_tiles = try_tiles(starts.n);
-    T_TRY(novel.alloc(some(starts.n)), "hipMalloc(tryptic flags)");
-    T_TRY(start_count.alloc(some(4 * start_tiles)), "hipMalloc(tryptic tiles)");
-    T_TRY(start_begin.alloc(8 * (start_tiles + 1)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(novel.alloc(some(starts.n)), "hipMalloc(tryptic flags)");
+    V2P_TRY(start_count.alloc(some(4 * start_tiles)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(start_begin.alloc(8 * (start_tiles + 1)), "hipMalloc(tryptic tiles)");
     a.novel = novel.get<uint8_t>(); a.tile_count = start_count.get<uint32_t>(); a.tile_begin = start_begin.get<unsigned long long>();
-    T_TRY(launch_try_filter(a, st), "launch(tryptic filter)");
-    T_TRY(launch_device_scan(a.tile_count, uint32_t(start_tiles), start_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_NOVEL, st), "launch(scan)");
-    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_try_filter(a, st), "launch(tryptic filter)");
+    V2P_TRY(launch_device_scan(a.tile_count, uint32_t(start_tiles), start_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_NOVEL, st), "launch(scan)");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     const uint64_t n_boundaries = h_status[TRY_ST_BOUNDARIES], n_products = h_status[TRY_ST_PRODUCTS], n_novel = h_status[TRY_ST_NOVEL];
     a.n_novel = n_novel;
     const uint64_t table_slots = slots_for(n_novel), list_tiles = try_tiles(n_novel);
     if (list_tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: 2^42 novel products", -1);
-    T_TRY(item.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
-    T_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(tryptic list)");
-    T_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
-    T_TRY(list_count.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");      // (a start has up to five products: the list may have more tiles than the starts)
-    T_TRY(list_begin.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
-    T_TRY(tile_bytes.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");
-    T_TRY(tile_text.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
-    T_TRY(slots.alloc(8 * table_slots), "hipMalloc(tryptic table)");
-    T_TRY(occ.alloc(8 * table_slots), "hipMalloc(tryptic table)");
+    V2P_TRY(item.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
+    V2P_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(tryptic list)");
+    V2P_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
+    V2P_TRY(list_count.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");      // (a start has up to five products: the list may have more tiles than the starts)
+    V2P_TRY(list_begin.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(tile_bytes.alloc(some(4 * list_tiles)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(tile_text.alloc(8 * (list_tiles + 1)), "hipMalloc(tryptic tiles)");
+    V2P_TRY(slots.alloc(8 * table_slots), "hipMalloc(tryptic table)");
+    V2P_TRY(occ.alloc(8 * table_slots), "hipMalloc(tryptic table)");
     a.item = item.get<unsigned long long>(); a.cls = cls.get<uint32_t>(); a.slot_of = slot_of.get<unsigned long long>();
     a.tile_bytes = tile_bytes.get<uint32_t>(); a.tile_text = tile_text.get<unsigned long long>();
-    a.table = TryTable{slots.get<unsigned long long>(), table_slots - 1}; a.occ = occ.get<unsigned long long>();
-    if (n_novel) T_TRY(launch_try_compact(a, st), "launch(tryptic compact)");
-    T_TRY(hipEventRecord(t->ev[2], st), "hipEventRecord");
+    a.table = SlotTable{slots.get<unsigned long long>(), table_slots - 1}; a.occ = occ.get<unsigned long long>();
+    if (n_novel) V2P_TRY(launch_try_compact(a, st), "launch(tryptic compact)");
+    V2P_TRY(hipEventRecord(t->ev[2], st), "hipEventRecord");
     // insert: the smallest position and the summed class counts per distinct text
-    T_TRY(hipMemsetAsync(a.table.slots, 0xFF, 8 * table_slots, st), "hipMemset(tryptic table)");
-    T_TRY(hipMemsetAsync(a.occ, 0, 8 * table_slots, st), "hipMemset(tryptic table)");
-    T_TRY(launch_try_insert(a, st), "launch(tryptic insert)");
-    T_TRY(hipEventRecord(t->ev[3], st), "hipEventRecord");
+    V2P_TRY(hipMemsetAsync(a.table.slots, 0xFF, 8 * table_slots, st), "hipMemset(tryptic table)");
+    V2P_TRY(hipMemsetAsync(a.occ, 0, 8 * table_slots, st), "hipMemset(tryptic table)");
+    V2P_TRY(launch_try_insert(a, st), "launch(tryptic insert)");
+    V2P_TRY(hipEventRecord(t->ev[3], st), "hipEventRecord");
     // collect: the list entries that are their peptide's first occurrence, in list order; peptide ids and text offsets from two scans
     a.tile_count = list_count.get<uint32_t>(); a.tile_begin = list_begin.get<unsigned long long>();
-    T_TRY(launch_try_firsts(a, st), "launch(tryptic firsts)");
-    T_TRY(launch_device_scan(a.tile_count, uint32_t(list_tiles), list_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_PEPTIDES, st), "launch(scan)");
-    T_TRY(launch_device_scan(a.tile_bytes, uint32_t(list_tiles), tile_text.get<unsigned long long>(), nullptr, a.status + TRY_ST_TEXT, st), "launch(scan)");
-    T_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_try_firsts(a, st), "launch(tryptic firsts)");
+    V2P_TRY(launch_device_scan(a.tile_count, uint32_t(list_tiles), list_begin.get<unsigned long long>(), nullptr, a.status + TRY_ST_PEPTIDES, st), "launch(scan)");
+    V2P_TRY(launch_device_scan(a.tile_bytes, uint32_t(list_tiles), tile_text.get<unsigned long long>(), nullptr, a.status + TRY_ST_TEXT, st), "launch(scan)");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(tryptic status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (h_status[TRY_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the peptide table is full (internal)", -1);
     const uint64_t n_peptides = h_status[TRY_ST_PEPTIDES], text_bytes = h_status[TRY_ST_TEXT];
-    T_TRY(text.alloc(some(text_bytes)), "hipMalloc(tryptic result)");
-    T_TRY(text_begin.alloc(8 * (n_peptides + 1)), "hipMalloc(tryptic result)");
-    T_TRY(out_occ.alloc(some(8 * n_peptides)), "hipMalloc(tryptic result)");
-    T_TRY(out_class.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
-    T_TRY(out_offset.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
+    V2P_TRY(text.alloc(some(text_bytes)), "hipMalloc(tryptic result)");
+    V2P_TRY(text_begin.alloc(8 * (n_peptides + 1)), "hipMalloc(tryptic result)");
+    V2P_TRY(out_occ.alloc(some(8 * n_peptides)), "hipMalloc(tryptic result)");
+    V2P_TRY(out_class.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
+    V2P_TRY(out_offset.alloc(some(4 * n_peptides)), "hipMalloc(tryptic result)");
     a.out_text = text.get<uint8_t>(); a.out_text_begin = text_begin.get<unsigned long long>(); a.out_occ = out_occ.get<unsigned long long>();
     a.out_class = out_class.get<uint32_t>(); a.out_offset = out_offset.get<uint32_t>();
-    if (n_peptides) T_TRY(launch_try_emit(a, st), "launch(tryptic emit)");
+    if (n_peptides) V2P_TRY(launch_try_emit(a, st), "launch(tryptic emit)");
     const unsigned long long h_end = text_bytes;
-    T_TRY(hipMemcpyAsync(a.out_text_begin + n_peptides, &h_end, 8, hipMemcpyHostToDevice, st), "H2D(tryptic result)");
-    T_TRY(hipEventRecord(t->ev[4], st), "hipEventRecord");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(hipMemcpyAsync(a.out_text_begin + n_peptides, &h_end, 8, hipMemcpyHostToDevice, st), "H2D(tryptic result)");
+    V2P_TRY(hipEventRecord(t->ev[4], st), "hipEventRecord");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     t->text = std::move(text); t->text_begin = std::move(text_begin); t->occ = std::move(out_occ);
     t->first_class = std::move(out_class); t->first_offset = std::move(out_offset);
     t->n_peptides = n_peptides; t->text_bytes = text_bytes; t->scanned = true;
@@ -660,14 +591,14 @@ int v2p_tryptic_download(v2p_tryptic* t, uint8_t* text, uint64_t* text_begin, ui
     if (!t->scanned) return ctx_fail(c, V2P_ERR_STATE, "v2p_tryptic_download: no scan yet", -1);
     if (n != t->n_peptides || text_bytes != t->text_bytes)
         return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_download: n or text_bytes is not what v2p_tryptic_count gives", -1);
-    T_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
-    if (text && text_bytes) T_TRY(hipMemcpyAsync(text, t->text.get<void>(), text_bytes, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
-    if (text_begin) T_TRY(hipMemcpyAsync(text_begin, t->text_begin.get<void>(), 8 * (n + 1), hipMemcpyDeviceToHost, st), "D2H(tryptic)");
-    if (occ && n) T_TRY(hipMemcpyAsync(occ, t->occ.get<void>(), 8 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
-    if (first_class && n) T_TRY(hipMemcpyAsync(first_class, t->first_class.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
-    if (first_offset && n) T_TRY(hipMemcpyAsync(first_offset, t->first_offset.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
-    T_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (text && text_bytes) V2P_TRY(hipMemcpyAsync(text, t->text.get<void>(), text_bytes, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (text_begin) V2P_TRY(hipMemcpyAsync(text_begin, t->text_begin.get<void>(), 8 * (n + 1), hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (occ && n) V2P_TRY(hipMemcpyAsync(occ, t->occ.get<void>(), 8 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (first_class && n) V2P_TRY(hipMemcpyAsync(first_class, t->first_class.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    if (first_offset && n) V2P_TRY(hipMemcpyAsync(first_offset, t->first_offset.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(tryptic)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return V2P_OK;
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/vcf2prot_hip.h"
 #include "device_scan.h"
+#include "set_table.hpp"
 #include "unique_records.h"
 #include "v2p_ctx_internal.h"
 
@@ -20,13 +21,6 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint64_t ONES = 0x0101010101010101ull;
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ uint64_t mul0(uint64_t k) { return splitmix64(k) | 1ull; }
 __device__ __forceinline__ uint64_t mul1(uint64_t k) { return splitmix64(k ^ UNIQUE_MUL1_XOR) | 1ull; }
 // Where a record's probe begins.  Not D_0's low bits: a product carries upwards only, so they see the first bytes of the words alone, and
@@ -301,15 +295,6 @@ void unique_store_view(const ::v2p_unique* u, UniqueStoreView* v)
 
 namespace {
 
-struct CtxLock {
-    v2p_ctx* c;
-    explicit CtxLock(v2p_ctx* ctx) : c(ctx) { ctx_lock(c); }
-    ~CtxLock() { ctx_unlock(c); }
-};
-
-int hip_fail(v2p_ctx* c, hipError_t e, const char* what) { return ctx_fail(c, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), -1); }
-#define U_TRY(expr, what) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return hip_fail(c, e__, what); } while (0)
-
 uint64_t up16(uint64_t x) { return (x + 15u) & ~uint64_t(15); }
 struct ScratchLayout {
     uint64_t rec_begin, rec_key, dig, slot_of, id_scan, store_scan, rec_len, rep_flag, rep_bytes, class_of, total;
@@ -327,7 +312,7 @@ int ensure_scratch(v2p_unique* u, uint64_t n)
     if (n <= u->scratch_n && u->scratch) return V2P_OK;
     u->scratch_n = 0; u->last_ranges = false;
     const uint64_t cap = n + n / 4 + 64;
-    U_TRY(u->scratch.alloc(ScratchLayout(cap).total), "hipMalloc(unique scratch)");
+    V2P_TRY(u->scratch.alloc(ScratchLayout(cap).total), "hipMalloc(unique scratch)");
     u->scratch_n = cap;
     return V2P_OK;
 }
@@ -336,9 +321,9 @@ int ensure_scratch(v2p_unique* u, uint64_t n)
 int grow(v2p_ctx* c, DevMem& m, uint64_t used, uint64_t bytes, hipStream_t st, const char* what)
 {
     DevMem n;
-    U_TRY(n.alloc(bytes), what);
-    if (used) U_TRY(hipMemcpyAsync(n.get<void>(), m.get<void>(), used, hipMemcpyDeviceToDevice, st), what);
-    U_TRY(hipStreamSynchronize(st), what);
+    V2P_TRY(n.alloc(bytes), what);
+    if (used) V2P_TRY(hipMemcpyAsync(n.get<void>(), m.get<void>(), used, hipMemcpyDeviceToDevice, st), what);
+    V2P_TRY(hipStreamSynchronize(st), what);
     m = std::move(n);
     return V2P_OK;
 }
@@ -378,10 +363,10 @@ int ensure_table(v2p_unique* u, uint64_t n_add, hipStream_t st)
     uint64_t slots = u->table_slots ? u->table_slots : 64;
     while (slots < need) slots *= 2;
     DevMem t;
-    U_TRY(t.alloc(slots * 8), "hipMalloc(unique table)");
-    U_TRY(hipMemsetAsync(t.get<void>(), 0xFF, slots * 8, st), "hipMemset(unique table)");
-    U_TRY(launch_unique_rebuild(u->classes(), u->n_classes, t.get<unsigned long long>(), slots - 1, st), "launch(unique rebuild)");
-    U_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(t.alloc(slots * 8), "hipMalloc(unique table)");
+    V2P_TRY(hipMemsetAsync(t.get<void>(), 0xFF, slots * 8, st), "hipMemset(unique table)");
+    V2P_TRY(launch_unique_rebuild(u->classes(), u->n_classes, t.get<unsigned long long>(), slots - 1, st), "launch(unique rebuild)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     u->slots = std::move(t);
     u->table_slots = slots;
     return V2P_OK;
@@ -414,10 +399,10 @@ int add_core(v2p_unique* u, UniqueArgs a, const uint64_t* d_digest, uint32_t* cl
     a.cls = u->classes(); a.n_classes = u->n_classes; a.store = u->store.get<uint8_t>(); a.store_bytes = u->store_bytes; a.records_before = u->n_records;
     a.class_of = reinterpret_cast<uint32_t*>(sc + L.class_of);
     a.status = u->status.get<unsigned long long>();
-    U_TRY(hipMemsetAsync(a.status, 0xFF, 8 * UNIQUE_ST_WORDS, st), "hipMemset(unique status)");
-    if (d_digest) U_TRY(hipMemcpyAsync(a.dig, d_digest, 16 * n, hipMemcpyDeviceToDevice, st), "D2D(digests)");
-    else U_TRY(launch_unique_digest(a, st), "launch(unique digest)");
-    U_TRY(hipEventRecord(u->ev[1], st), "hipEventRecord");
+    V2P_TRY(hipMemsetAsync(a.status, 0xFF, 8 * UNIQUE_ST_WORDS, st), "hipMemset(unique status)");
+    if (d_digest) V2P_TRY(hipMemcpyAsync(a.dig, d_digest, 16 * n, hipMemcpyDeviceToDevice, st), "D2D(digests)");
+    else V2P_TRY(launch_unique_digest(a, st), "launch(unique digest)");
+    V2P_TRY(hipEventRecord(u->ev[1], st), "hipEventRecord");
     // from here on the table holds provisional slots: every way out rolls them back
     auto fail = [&](int code) {
         (void)launch_unique_rollback(a, st);
@@ -449,11 +434,11 @@ int add_core(v2p_unique* u, UniqueArgs a, const uint64_t* d_digest, uint32_t* cl
     e = launch_unique_commit(a, st);
     if (e != hipSuccess) return fail(hip_fail(c, e, "launch(unique commit)"));
     // (behind the commit the slots hold class ids: nothing is left to roll back, and a failure below can only be the device's)
-    U_TRY(launch_unique_resolve(a, st), "launch(unique resolve)");
-    U_TRY(hipEventRecord(u->ev[4], st), "hipEventRecord");
-    if (class_of) U_TRY(hipMemcpyAsync(class_of, a.class_of, 4 * n, hipMemcpyDeviceToHost, st), "D2H(class_of)");
-    if (n_new) U_TRY(hipMemcpyAsync(new_len.data(), a.cls.len + u->n_classes, 4 * n_new, hipMemcpyDeviceToHost, st), "D2H(class lengths)");
-    U_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_unique_resolve(a, st), "launch(unique resolve)");
+    V2P_TRY(hipEventRecord(u->ev[4], st), "hipEventRecord");
+    if (class_of) V2P_TRY(hipMemcpyAsync(class_of, a.class_of, 4 * n, hipMemcpyDeviceToHost, st), "D2H(class_of)");
+    if (n_new) V2P_TRY(hipMemcpyAsync(new_len.data(), a.cls.len + u->n_classes, 4 * n_new, hipMemcpyDeviceToHost, st), "D2H(class lengths)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     u->h_len.insert(u->h_len.end(), new_len.begin(), new_len.end());
     u->n_classes += n_new; u->store_bytes += new_bytes; u->n_records += n;
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
@@ -472,7 +457,7 @@ int v2p_unique_create(v2p_ctx* c, uint64_t expected_classes, v2p_unique** out)
     *out = nullptr;
     CtxLock lk(c);
     if (expected_classes > (1ull << 40)) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_create: expected_classes", -1);
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     v2p_unique* u = new (std::nothrow) v2p_unique();
     if (!u) return ctx_fail(c, V2P_ERR_HIP, "out of host memory", -1);
     u->ctx = c;
@@ -507,11 +492,11 @@ int v2p_unique_add_records(v2p_unique* u, const uint8_t* d_arena, uint64_t arena
     if (n >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_add_records: too many records", -1);
     if (n && (!d_rec_begin || !d_rec_len || !d_rec_key || (arena_bytes && !d_arena))) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_add_records: null argument", -1);
     if (n == 0) { fill_info(u, info, 0, 0, nullptr); return V2P_OK; }
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     const int rc = ensure_scratch(u, n);
     if (rc != V2P_OK) return rc;
     u->last_ranges = false;
-    U_TRY(hipEventRecord(u->ev[0], ctx_stream(c)), "hipEventRecord");
+    V2P_TRY(hipEventRecord(u->ev[0], ctx_stream(c)), "hipEventRecord");
     UniqueArgs a{};
     a.arena = d_arena; a.arena_bytes = arena_bytes;
     a.rec_begin = reinterpret_cast<const unsigned long long*>(d_rec_begin); a.rec_len = d_rec_len;
@@ -532,21 +517,21 @@ int v2p_unique_add(v2p_unique* u, v2p_batch* b, const v2p_stream* s, uint32_t* c
     const uint64_t n = sv.n_tx;
     if (n >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_add: too many records", -1);
     if (n == 0) { fill_info(u, info, 0, 0, nullptr); return V2P_OK; }
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     const int rc = ensure_scratch(u, n);
     if (rc != V2P_OK) return rc;
     u->last_ranges = false;
     hipStream_t st = ctx_stream(c);
     uint8_t* const sc = u->scratch.get<uint8_t>();
     const ScratchLayout L(u->scratch_n);
-    U_TRY(hipEventRecord(u->ev[0], st), "hipEventRecord");
+    V2P_TRY(hipEventRecord(u->ev[0], st), "hipEventRecord");
     // (arena bytes per transcript and their sums borrow two arrays the add fills later)
     UniqueRangeArgs ra{sv.n_haps, n, sv.hap_tx_begin, bv.hap_out_begin, sv.tx_proteome_off, sv.tx_ref_len, sv.tx_res_len, sv.tx_header_len,
                        reinterpret_cast<uint32_t*>(sc + L.rep_flag), reinterpret_cast<unsigned long long*>(sc + L.id_scan),
                        reinterpret_cast<unsigned long long*>(sc + L.rec_begin), reinterpret_cast<uint32_t*>(sc + L.rec_len), reinterpret_cast<unsigned long long*>(sc + L.rec_key)};
-    U_TRY(launch_unique_arena_len(ra, st), "launch(unique arena_len)");
-    U_TRY(launch_device_scan(ra.arena_len, uint32_t(n), reinterpret_cast<unsigned long long*>(sc + L.id_scan), nullptr, u->status.get<unsigned long long>() + UNIQUE_ST_NEW, st), "launch(scan)");
-    U_TRY(launch_unique_ranges(ra, st), "launch(unique ranges)");
+    V2P_TRY(launch_unique_arena_len(ra, st), "launch(unique arena_len)");
+    V2P_TRY(launch_device_scan(ra.arena_len, uint32_t(n), reinterpret_cast<unsigned long long*>(sc + L.id_scan), nullptr, u->status.get<unsigned long long>() + UNIQUE_ST_NEW, st), "launch(scan)");
+    V2P_TRY(launch_unique_ranges(ra, st), "launch(unique ranges)");
     UniqueArgs a{};
     a.arena = bv.arena; a.arena_bytes = bv.out_bytes;
     a.rec_begin = ra.rec_begin; a.rec_len = ra.rec_len; a.rec_key = ra.rec_key; a.n = n;
@@ -562,12 +547,12 @@ int v2p_unique_last_ranges(v2p_unique* u, uint64_t* rec_begin, uint32_t* rec_len
     CtxLock lk(c);
     if (!u->last_ranges) return ctx_fail(c, V2P_ERR_STATE, "v2p_unique_last_ranges: the last call was not a successful v2p_unique_add", -1);
     if (n != u->last_n) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_last_ranges: n is not the last add's", -1);
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     const ScratchLayout L(u->scratch_n);
     const uint8_t* sc = u->scratch.get<uint8_t>();
-    if (rec_begin) U_TRY(hipMemcpyAsync(rec_begin, sc + L.rec_begin, 8 * n, hipMemcpyDeviceToHost, ctx_stream(c)), "D2H(ranges)");
-    if (rec_len) U_TRY(hipMemcpyAsync(rec_len, sc + L.rec_len, 4 * n, hipMemcpyDeviceToHost, ctx_stream(c)), "D2H(ranges)");
-    U_TRY(hipStreamSynchronize(ctx_stream(c)), "hipStreamSynchronize");
+    if (rec_begin) V2P_TRY(hipMemcpyAsync(rec_begin, sc + L.rec_begin, 8 * n, hipMemcpyDeviceToHost, ctx_stream(c)), "D2H(ranges)");
+    if (rec_len) V2P_TRY(hipMemcpyAsync(rec_len, sc + L.rec_len, 4 * n, hipMemcpyDeviceToHost, ctx_stream(c)), "D2H(ranges)");
+    V2P_TRY(hipStreamSynchronize(ctx_stream(c)), "hipStreamSynchronize");
     return V2P_OK;
 }
 
@@ -588,13 +573,13 @@ int v2p_unique_classes(v2p_unique* u, uint64_t* key, uint32_t* len, uint64_t* co
     CtxLock lk(c);
     const uint64_t k = u->n_classes;
     if (k == 0) return V2P_OK;
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
-    if (key) U_TRY(hipMemcpyAsync(key, u->key.get<void>(), 16 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
-    if (len) U_TRY(hipMemcpyAsync(len, u->len.get<void>(), 4 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
-    if (count) U_TRY(hipMemcpyAsync(count, u->count.get<void>(), 8 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
-    if (first_record) U_TRY(hipMemcpyAsync(first_record, u->first_record.get<void>(), 8 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
-    U_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (key) V2P_TRY(hipMemcpyAsync(key, u->key.get<void>(), 16 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
+    if (len) V2P_TRY(hipMemcpyAsync(len, u->len.get<void>(), 4 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
+    if (count) V2P_TRY(hipMemcpyAsync(count, u->count.get<void>(), 8 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
+    if (first_record) V2P_TRY(hipMemcpyAsync(first_record, u->first_record.get<void>(), 8 * k, hipMemcpyDeviceToHost, st), "D2H(classes)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return V2P_OK;
 }
 
@@ -621,17 +606,17 @@ int v2p_unique_emit(v2p_unique* u, const uint32_t* order, uint64_t n, const uint
     if (!out) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_emit: null argument", -1);
     const uint64_t h0 = header_begin[0], hbytes = header_begin[n] - h0;
     if (hbytes && !headers) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_unique_emit: null argument", -1);
-    U_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
     // [order | header_begin | out_begin | headers | out]: one allocation for the call
     const uint64_t o_order = 0, o_hb = o_order + up16(4 * n), o_ob = o_hb + up16(8 * (n + 1)), o_hd = o_ob + up16(8 * (n + 1)), o_out = o_hd + up16(hbytes);
     DevMem m;
-    U_TRY(m.alloc(o_out + total), "hipMalloc(unique emit)");
+    V2P_TRY(m.alloc(o_out + total), "hipMalloc(unique emit)");
     uint8_t* const d = m.get<uint8_t>();
-    U_TRY(hipMemcpyAsync(d + o_order, order, 4 * n, hipMemcpyHostToDevice, st), "H2D(emit)");
-    U_TRY(hipMemcpyAsync(d + o_hb, hb_rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), "H2D(emit)");
-    U_TRY(hipMemcpyAsync(d + o_ob, out_begin.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), "H2D(emit)");
-    if (hbytes) U_TRY(hipMemcpyAsync(d + o_hd, headers + h0, hbytes, hipMemcpyHostToDevice, st), "H2D(emit)");
+    V2P_TRY(hipMemcpyAsync(d + o_order, order, 4 * n, hipMemcpyHostToDevice, st), "H2D(emit)");
+    V2P_TRY(hipMemcpyAsync(d + o_hb, hb_rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), "H2D(emit)");
+    V2P_TRY(hipMemcpyAsync(d + o_ob, out_begin.data(), 8 * (n + 1), hipMemcpyHostToDevice, st), "H2D(emit)");
+    if (hbytes) V2P_TRY(hipMemcpyAsync(d + o_hd, headers + h0, hbytes, hipMemcpyHostToDevice, st), "H2D(emit)");
     UniqueEmitArgs a{reinterpret_cast<const uint32_t*>(d + o_order), n, d + o_hd, reinterpret_cast<const unsigned long long*>(d + o_hb),
                      reinterpret_cast<const unsigned long long*>(d + o_ob), u->classes(), u->store.get<uint8_t>(), d + o_out};
     hipError_t e = launch_unique_emit(a, st);

@@ -7,13 +7,9 @@
 // key is cut from the one or two ALIGNED 16-byte blocks that hold it (one vector load each; a block that reaches beyond the buffer's last
 // byte -- there is at most one -- is read byte by byte up to that byte), so no byte outside the buffer is read.
 //
-// Both tables (the BACKGROUND of reference windows, built once per set; the PEPTIDE table of one scan) are unique_records.h's: open
-// addressing, linear probing from splitmix64(k0 ^ splitmix64(k1)), 64-bit slots, PEP_EMPTY or [16 bits of the hash | 48 bits: the
-// position of a representative window in the reference copy / in the store].  A slot is claimed by CAS and never becomes empty; a lane
-// that meets a taken slot compares the tag, then the representative's K bytes, and moves on if they differ -- so equal keys always meet
-// in one slot.  atomicMin lowers the position (the tag of equal keys is equal, so the whole word orders by position): the
-// representative is the smallest position whatever the order of arrival.  The store is in class order, so in the peptide table that is
-// the smallest (class, offset).  occ is an integer atomicAdd of the class's count into a counter beside the slot.
+// Both tables (the BACKGROUND of reference windows, built once per set; the PEPTIDE table of one scan) are set_table.hpp's slot tables,
+// probed from splitmix64(k0 ^ splitmix64(k1)); a slot word is [16 bits of the hash | 48 bits: the position of a representative window in
+// the reference copy / in the store], and "the same text" is equality of the representative's key.
 //
 // Work split: a LANE PER STORE POSITION in the filter.  The cost of a position is one probe -- a dependent 8-byte read at a random slot,
 // for most windows followed by a 16-byte read of the reference -- and no stage in front of it is worth sharing among lanes; consecutive
@@ -28,20 +24,18 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "set_table.hpp"
 #include "unique_records.h"
 
 namespace v2p {
 
-constexpr unsigned long long PEP_EMPTY = ~0ull;
 constexpr uint32_t PEP_POS_BITS = 48;
 constexpr unsigned long long PEP_POS_MASK = (1ull << PEP_POS_BITS) - 1u;
-constexpr unsigned long long PEP_MAX_BYTES = 1ull << 47;     // positions stay below this, so no [tag | position] equals PEP_EMPTY
+constexpr unsigned long long PEP_MAX_BYTES = 1ull << 47;     // positions stay below this, so no [tag | position] equals SLOT_EMPTY
 constexpr uint32_t PEP_THREADS = 256;
 constexpr uint32_t PEP_STEPS = 4;
 constexpr uint32_t PEP_TILE = PEP_THREADS * PEP_STEPS;       // positions (or list entries) per workgroup
 enum { PEP_ST_KMERS = 0, PEP_ST_WINDOWS = 1, PEP_ST_NOVEL = 2, PEP_ST_PEPTIDES = 3, PEP_ST_FULL = 4, PEP_ST_WORDS = 5 };
-
-struct PepTable { unsigned long long* slots; uint64_t slot_mask; };
 
 struct PepBuildArgs {                  // the background
     uint32_t k;
@@ -49,20 +43,20 @@ struct PepBuildArgs {                  // the background
     const unsigned long long* seq_begin;   // [n_seq]
     const unsigned long long* win_begin;   // [n_seq + 1] exclusive sums of the sequences' window counts
     uint64_t n_seq, n_windows;
-    PepTable table;
+    SlotTable table;
     unsigned long long* status;        // [PEP_ST_WORDS]
 };
 
 struct PepScanArgs {                   // one scan of a distinct-record set
     uint32_t k;
-    const uint8_t* ref; uint64_t ref_bytes; PepTable ref_table;
+    const uint8_t* ref; uint64_t ref_bytes; SlotTable ref_table;
     const uint8_t* store; uint64_t store_bytes;
     const unsigned long long* store_begin; const uint32_t* cls_len; const unsigned long long* cls_count; uint64_t n_classes;
     unsigned long long* flags;         // [16 per tile of the store] bit p & 63 of word p >> 6: the window at p is novel
     uint32_t* tile_count;              // [store tiles] novel windows of a tile; [list tiles] first occurrences of a tile
     const unsigned long long* tile_begin;  // [tiles + 1] their exclusive sums
     unsigned long long* pos; uint32_t* cls; unsigned long long* slot_of; uint64_t n_novel;   // the list of novel windows, ascending position
-    PepTable table; unsigned long long* occ;                                                  // the peptide table, a counter per slot
+    SlotTable table; unsigned long long* occ;                                                  // the peptide table, a counter per slot
     uint8_t* out_text; unsigned long long* out_occ; uint32_t* out_class; uint32_t* out_offset;
     unsigned long long* status;
 };

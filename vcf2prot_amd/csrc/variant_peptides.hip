@@ -20,13 +20,6 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ uint64_t key_hash(uint64_t k0, uint64_t k1) { return splitmix64(k0 ^ splitmix64(k1)); }
 
 // the aligned 16-byte block at offset `off` (a multiple of 16; base is 16-byte aligned) of a buffer of `limit` bytes, off < limit: one
@@ -64,59 +57,19 @@ __device__ __forceinline__ void window_key(const uint8_t* base, uint64_t limit, 
 
 // the slot of key (k0, k1), whose window sits at base[p, p + k): claimed, or found taken by an equal key (whose position is lowered to p if
 // p is smaller).  *claimed: this call took an empty slot.  ~0: no slot (a table more than full: never, with half the slots free).
-__device__ __forceinline__ uint64_t table_insert(const PepTable t, const uint8_t* base, uint64_t limit, uint32_t k, uint64_t p, uint64_t k0, uint64_t k1, bool* claimed)
+__device__ __forceinline__ uint64_t table_insert(const SlotTable t, const uint8_t* base, uint64_t limit, uint32_t k, uint64_t p, uint64_t k0, uint64_t k1, bool* claimed)
 {
     const uint64_t h = key_hash(k0, k1);
-    const unsigned long long mine = ((h >> PEP_POS_BITS) << PEP_POS_BITS) | p;
-    uint64_t i = h & t.slot_mask;
-    for (uint64_t probe = 0; probe <= t.slot_mask; ++probe, i = (i + 1u) & t.slot_mask) {
-        unsigned long long v = __hip_atomic_load(&t.slots[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v == PEP_EMPTY) {
-            v = atomicCAS(&t.slots[i], PEP_EMPTY, mine);
-            if (v == PEP_EMPTY) { *claimed = true; return i; }
-        }
-        if ((v ^ mine) >> PEP_POS_BITS) continue;                    // another tag: another key
-        uint64_t r0, r1;
-        window_key(base, limit, v & PEP_POS_MASK, k, r0, r1);         // (any representative a slot ever had holds the slot's key)
-        if (r0 == k0 && r1 == k1) {
-            if (mine < v) atomicMin(&t.slots[i], mine);
-            return i;
-        }
-    }
-    return ~0ull;
+    const auto same = [&](uint64_t at) { uint64_t r0, r1; window_key(base, limit, at, k, r0, r1); return r0 == k0 && r1 == k1; };
+    return slot_insert<PEP_POS_BITS>(t, h, ((h >> PEP_POS_BITS) << PEP_POS_BITS) | p, same, claimed);
 }
 
 // read-only, behind a launch boundary: is key (k0, k1) in the table?
-__device__ __forceinline__ bool table_holds(const PepTable t, const uint8_t* base, uint64_t limit, uint32_t k, uint64_t k0, uint64_t k1)
+__device__ __forceinline__ bool table_holds(const SlotTable t, const uint8_t* base, uint64_t limit, uint32_t k, uint64_t k0, uint64_t k1)
 {
     const uint64_t h = key_hash(k0, k1);
-    uint64_t i = h & t.slot_mask;
-    for (uint64_t probe = 0; probe <= t.slot_mask; ++probe, i = (i + 1u) & t.slot_mask) {
-        const unsigned long long v = t.slots[i];
-        if (v == PEP_EMPTY) return false;
-        if ((v >> PEP_POS_BITS) != (h >> PEP_POS_BITS)) continue;
-        uint64_t r0, r1;
-        window_key(base, limit, v & PEP_POS_MASK, k, r0, r1);
-        if (r0 == k0 && r1 == k1) return true;
-    }
-    return false;
-}
-
-// the last entry of begin[lo .. hi] that is <= p (begin ascends, begin[lo] <= p)
-__device__ __forceinline__ uint64_t last_at_or_before(const unsigned long long* begin, uint64_t lo, uint64_t hi, uint64_t p)
-{
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1u) >> 1;
-        if (begin[mid] <= p) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
-
-// a wave's lanes with `pred` set, added to an LDS counter by its first lane; every lane of the wave must reach the call
-__device__ __forceinline__ void wave_count(bool pred, uint32_t* counter)
-{
-    const unsigned long long m = __ballot(pred);
-    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(counter, uint32_t(__popcll(m)));
+    const auto same = [&](uint64_t at) { uint64_t r0, r1; window_key(base, limit, at, k, r0, r1); return r0 == k0 && r1 == k1; };
+    return slot_holds<PEP_POS_BITS>(t, h, (h >> PEP_POS_BITS) << PEP_POS_BITS, same);
 }
 
 __global__ __launch_bounds__(PEP_THREADS) void pep_build_kernel(PepBuildArgs a)
@@ -139,23 +92,13 @@ __global__ __launch_bounds__(PEP_THREADS) void pep_build_kernel(PepBuildArgs a)
     if (threadIdx.x == 0 && s_new) atomicAdd(&a.status[PEP_ST_KMERS], (unsigned long long)s_new);
 }
 
-// the classes of a tile's first and last byte, found by thread 0 for every lane to search between
-__device__ __forceinline__ void tile_classes(const PepScanArgs& a, uint64_t tile0, uint64_t* s_range)
-{
-    if (threadIdx.x == 0) {
-        const uint64_t last = (tile0 + PEP_TILE < a.store_bytes ? tile0 + PEP_TILE : a.store_bytes) - 1u;
-        s_range[0] = last_at_or_before(a.store_begin, 0, a.n_classes - 1u, tile0);
-        s_range[1] = last_at_or_before(a.store_begin, s_range[0], a.n_classes - 1u, last);
-    }
-}
-
 __global__ __launch_bounds__(PEP_THREADS) void pep_filter_kernel(PepScanArgs a)
 {
     __shared__ uint64_t s_range[2];
     __shared__ uint32_t s_novel, s_valid;
     const uint64_t tile0 = uint64_t(blockIdx.x) * PEP_TILE;          // (the grid has a block per tile that begins inside the store)
     if (threadIdx.x == 0) s_novel = s_valid = 0;
-    tile_classes(a, tile0, s_range);
+    tile_range(a.store_begin, a.n_classes, a.store_bytes, tile0, PEP_TILE, s_range);
     __syncthreads();
     const uint64_t c_lo = s_range[0], c_hi = s_range[1];
 #pragma unroll 1
@@ -193,7 +136,7 @@ __global__ __launch_bounds__(PEP_THREADS) void pep_compact_kernel(PepScanArgs a)
     const uint64_t tile0 = uint64_t(blockIdx.x) * PEP_TILE;
     uint64_t at = a.tile_begin[blockIdx.x];
     if (a.tile_begin[blockIdx.x + 1] == at) return;                  // (the whole workgroup)
-    tile_classes(a, tile0, s_range);
+    tile_range(a.store_begin, a.n_classes, a.store_bytes, tile0, PEP_TILE, s_range);
     __syncthreads();
     const uint64_t c_lo = s_range[0], c_hi = s_range[1];
 #pragma unroll 1
@@ -270,17 +213,14 @@ __global__ __launch_bounds__(PEP_THREADS) void pep_emit_kernel(PepScanArgs a)
     }
 }
 
-inline dim3 grid_of(uint64_t blocks) { return dim3(uint32_t(blocks)); }
-
 }  // namespace
 
-#define PEP_LAUNCH(kernel, blocks, a) do { if (blocks) kernel<<<grid_of(blocks), PEP_THREADS, 0, st>>>(a); return hipGetLastError(); } while (0)
-hipError_t launch_pep_build(const PepBuildArgs& a, hipStream_t st) { PEP_LAUNCH(pep_build_kernel, (a.n_windows + PEP_THREADS - 1) / PEP_THREADS, a); }
-hipError_t launch_pep_filter(const PepScanArgs& a, hipStream_t st) { PEP_LAUNCH(pep_filter_kernel, pep_tiles(a.store_bytes), a); }
-hipError_t launch_pep_compact(const PepScanArgs& a, hipStream_t st) { PEP_LAUNCH(pep_compact_kernel, pep_tiles(a.store_bytes), a); }
-hipError_t launch_pep_insert(const PepScanArgs& a, hipStream_t st) { PEP_LAUNCH(pep_insert_kernel, (a.n_novel + PEP_THREADS - 1) / PEP_THREADS, a); }
-hipError_t launch_pep_firsts(const PepScanArgs& a, hipStream_t st) { PEP_LAUNCH(pep_firsts_kernel, pep_tiles(a.n_novel), a); }
-hipError_t launch_pep_emit(const PepScanArgs& a, hipStream_t st) { PEP_LAUNCH(pep_emit_kernel, pep_tiles(a.n_novel), a); }
+hipError_t launch_pep_build(const PepBuildArgs& a, hipStream_t st) { SET_LAUNCH(pep_build_kernel, PEP_THREADS, (a.n_windows + PEP_THREADS - 1) / PEP_THREADS, a); }
+hipError_t launch_pep_filter(const PepScanArgs& a, hipStream_t st) { SET_LAUNCH(pep_filter_kernel, PEP_THREADS, pep_tiles(a.store_bytes), a); }
+hipError_t launch_pep_compact(const PepScanArgs& a, hipStream_t st) { SET_LAUNCH(pep_compact_kernel, PEP_THREADS, pep_tiles(a.store_bytes), a); }
+hipError_t launch_pep_insert(const PepScanArgs& a, hipStream_t st) { SET_LAUNCH(pep_insert_kernel, PEP_THREADS, (a.n_novel + PEP_THREADS - 1) / PEP_THREADS, a); }
+hipError_t launch_pep_firsts(const PepScanArgs& a, hipStream_t st) { SET_LAUNCH(pep_firsts_kernel, PEP_THREADS, pep_tiles(a.n_novel), a); }
+hipError_t launch_pep_emit(const PepScanArgs& a, hipStream_t st) { SET_LAUNCH(pep_emit_kernel, PEP_THREADS, pep_tiles(a.n_novel), a); }
 
 }  // namespace v2p
 
@@ -302,52 +242,34 @@ struct v2p_peptides {
 
 namespace {
 
-struct CtxLock {
-    v2p_ctx* c;
-    explicit CtxLock(v2p_ctx* ctx) : c(ctx) { ctx_lock(c); }
-    ~CtxLock() { ctx_unlock(c); }
-};
-
-int hip_fail(v2p_ctx* c, hipError_t e, const char* what) { return ctx_fail(c, V2P_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), -1); }
-#define P_TRY(expr, what) do { const hipError_t e__ = (expr); if (e__ != hipSuccess) return hip_fail(c, e__, what); } while (0)
-
-// a power of two, at least twice n and at least 64
-uint64_t slots_for(uint64_t n)
-{
-    uint64_t s = 64;
-    while (s < 2 * n) s *= 2;
-    return s;
-}
-size_t some(uint64_t bytes) { return size_t(bytes ? bytes : 16); }   // (no allocation of nothing)
-
 int build_background(v2p_peptides* p, const uint8_t* ref, const uint64_t* seq_begin, const std::vector<unsigned long long>& win_begin, uint64_t n_seq)
 {
     v2p_ctx* c = p->ctx;
     hipStream_t st = ctx_stream(c);
-    P_TRY(p->ev.create(), "hipEventCreate");
-    P_TRY(p->status.alloc(8 * PEP_ST_WORDS), "hipMalloc(peptides status)");
-    P_TRY(p->ref.alloc(some(p->ref_bytes)), "hipMalloc(peptides reference)");
+    V2P_TRY(p->ev.create(), "hipEventCreate");
+    V2P_TRY(p->status.alloc(8 * PEP_ST_WORDS), "hipMalloc(peptides status)");
+    V2P_TRY(p->ref.alloc(some(p->ref_bytes)), "hipMalloc(peptides reference)");
     p->ref_table_slots = slots_for(p->n_ref_windows);
-    P_TRY(p->ref_slots.alloc(8 * p->ref_table_slots), "hipMalloc(peptides background)");
+    V2P_TRY(p->ref_slots.alloc(8 * p->ref_table_slots), "hipMalloc(peptides background)");
     DevMem tables;                                           // [seq_begin | win_begin], for the build alone
     const uint64_t o_win = (8 * n_seq + 15u) & ~uint64_t(15);
-    P_TRY(tables.alloc(some(o_win + 8 * (n_seq + 1))), "hipMalloc(peptides sequences)");
-    P_TRY(hipEventRecord(p->ev[0], st), "hipEventRecord");
-    if (p->ref_bytes) P_TRY(hipMemcpyAsync(p->ref.get<void>(), ref, p->ref_bytes, hipMemcpyHostToDevice, st), "H2D(reference)");
+    V2P_TRY(tables.alloc(some(o_win + 8 * (n_seq + 1))), "hipMalloc(peptides sequences)");
+    V2P_TRY(hipEventRecord(p->ev[0], st), "hipEventRecord");
+    if (p->ref_bytes) V2P_TRY(hipMemcpyAsync(p->ref.get<void>(), ref, p->ref_bytes, hipMemcpyHostToDevice, st), "H2D(reference)");
     if (n_seq) {
-        P_TRY(hipMemcpyAsync(tables.get<void>(), seq_begin, 8 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
-        P_TRY(hipMemcpyAsync(tables.get<uint8_t>() + o_win, win_begin.data(), 8 * (n_seq + 1), hipMemcpyHostToDevice, st), "H2D(sequences)");
+        V2P_TRY(hipMemcpyAsync(tables.get<void>(), seq_begin, 8 * n_seq, hipMemcpyHostToDevice, st), "H2D(sequences)");
+        V2P_TRY(hipMemcpyAsync(tables.get<uint8_t>() + o_win, win_begin.data(), 8 * (n_seq + 1), hipMemcpyHostToDevice, st), "H2D(sequences)");
     }
-    P_TRY(hipMemsetAsync(p->ref_slots.get<void>(), 0xFF, 8 * p->ref_table_slots, st), "hipMemset(peptides background)");
-    P_TRY(hipMemsetAsync(p->status.get<void>(), 0, 8 * PEP_ST_WORDS, st), "hipMemset(peptides status)");
+    V2P_TRY(hipMemsetAsync(p->ref_slots.get<void>(), 0xFF, 8 * p->ref_table_slots, st), "hipMemset(peptides background)");
+    V2P_TRY(hipMemsetAsync(p->status.get<void>(), 0, 8 * PEP_ST_WORDS, st), "hipMemset(peptides status)");
     PepBuildArgs a{p->k, p->ref.get<uint8_t>(), p->ref_bytes, tables.get<unsigned long long>(),
                    reinterpret_cast<const unsigned long long*>(tables.get<uint8_t>() + o_win), n_seq, p->n_ref_windows,
-                   PepTable{p->ref_slots.get<unsigned long long>(), p->ref_table_slots - 1}, p->status.get<unsigned long long>()};
-    P_TRY(launch_pep_build(a, st), "launch(peptides build)");
-    P_TRY(hipEventRecord(p->ev[1], st), "hipEventRecord");
+                   SlotTable{p->ref_slots.get<unsigned long long>(), p->ref_table_slots - 1}, p->status.get<unsigned long long>()};
+    V2P_TRY(launch_pep_build(a, st), "launch(peptides build)");
+    V2P_TRY(hipEventRecord(p->ev[1], st), "hipEventRecord");
     unsigned long long h_status[PEP_ST_WORDS];
-    P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
-    P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (h_status[PEP_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the background table is full (internal)", -1);
     p->n_ref_kmers = h_status[PEP_ST_KMERS];
     (void)hipEventElapsedTime(&p->ms_ref_build, p->ev[0], p->ev[1]);
@@ -378,7 +300,7 @@ int v2p_peptides_create(v2p_ctx* c, uint32_t k, const uint8_t* ref, uint64_t ref
     }
     win_begin[n_seq] = n_windows;
     if (n_windows >= (1ull << 38)) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_peptides_create: 2^38 reference windows", -1);
-    P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     v2p_peptides* p = new (std::nothrow) v2p_peptides();
     if (!p) return ctx_fail(c, V2P_ERR_HIP, "out of host memory", -1);
     p->ctx = c; p->k = k; p->ref_bytes = ref_bytes; p->n_ref_windows = n_windows;
@@ -406,64 +328,64 @@ int v2p_peptides_scan(v2p_peptides* p, v2p_unique* u, v2p_peptides_info* info)
     unique_store_view(u, &uv);
     if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_peptides_scan: the peptide set and the record set belong to different contexts", -1);
     if (uv.store_bytes >= PEP_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_peptides_scan: a store of 2^47 bytes", -1);
-    P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
     const uint64_t tiles = pep_tiles(uv.store_bytes);
     if (tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_peptides_scan: 2^32 tiles", -1);
     // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
     DevMem flags, tile_count, tile_begin, pos, cls, slot_of, slots, occ, text, out_occ, out_class, out_offset;
-    P_TRY(flags.alloc(some(8 * 16 * tiles)), "hipMalloc(peptides flags)");
-    P_TRY(tile_count.alloc(some(4 * tiles)), "hipMalloc(peptides tiles)");
-    P_TRY(tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(peptides tiles)");
+    V2P_TRY(flags.alloc(some(8 * 16 * tiles)), "hipMalloc(peptides flags)");
+    V2P_TRY(tile_count.alloc(some(4 * tiles)), "hipMalloc(peptides tiles)");
+    V2P_TRY(tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(peptides tiles)");
     PepScanArgs a{};
     a.k = p->k;
-    a.ref = p->ref.get<uint8_t>(); a.ref_bytes = p->ref_bytes; a.ref_table = PepTable{p->ref_slots.get<unsigned long long>(), p->ref_table_slots - 1};
+    a.ref = p->ref.get<uint8_t>(); a.ref_bytes = p->ref_bytes; a.ref_table = SlotTable{p->ref_slots.get<unsigned long long>(), p->ref_table_slots - 1};
     a.store = uv.store; a.store_bytes = uv.store_bytes;
     a.store_begin = uv.cls.store_begin; a.cls_len = uv.cls.len; a.cls_count = uv.cls.count; a.n_classes = uv.n_classes;
     a.flags = flags.get<unsigned long long>(); a.tile_count = tile_count.get<uint32_t>(); a.tile_begin = tile_begin.get<unsigned long long>();
     a.status = p->status.get<unsigned long long>();
     unsigned long long* const d_tile_begin = tile_begin.get<unsigned long long>();
     unsigned long long h_status[PEP_ST_WORDS];
-    P_TRY(hipMemsetAsync(a.status, 0, 8 * PEP_ST_WORDS, st), "hipMemset(peptides status)");
-    P_TRY(hipEventRecord(p->ev[0], st), "hipEventRecord");
+    V2P_TRY(hipMemsetAsync(a.status, 0, 8 * PEP_ST_WORDS, st), "hipMemset(peptides status)");
+    V2P_TRY(hipEventRecord(p->ev[0], st), "hipEventRecord");
     // filter: one probe per store byte; the novel windows counted per tile, listed in position order
-    P_TRY(launch_pep_filter(a, st), "launch(peptides filter)");
-    P_TRY(launch_device_scan(a.tile_count, uint32_t(tiles), d_tile_begin, nullptr, a.status + PEP_ST_NOVEL, st), "launch(scan)");
-    P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
-    P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_pep_filter(a, st), "launch(peptides filter)");
+    V2P_TRY(launch_device_scan(a.tile_count, uint32_t(tiles), d_tile_begin, nullptr, a.status + PEP_ST_NOVEL, st), "launch(scan)");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     const uint64_t n_windows = h_status[PEP_ST_WINDOWS], n_novel = h_status[PEP_ST_NOVEL];
     a.n_novel = n_novel;
     const uint64_t table_slots = slots_for(n_novel);
-    P_TRY(pos.alloc(some(8 * n_novel)), "hipMalloc(peptides list)");
-    P_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(peptides list)");
-    P_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(peptides list)");
-    P_TRY(slots.alloc(8 * table_slots), "hipMalloc(peptides table)");
-    P_TRY(occ.alloc(8 * table_slots), "hipMalloc(peptides table)");
+    V2P_TRY(pos.alloc(some(8 * n_novel)), "hipMalloc(peptides list)");
+    V2P_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(peptides list)");
+    V2P_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(peptides list)");
+    V2P_TRY(slots.alloc(8 * table_slots), "hipMalloc(peptides table)");
+    V2P_TRY(occ.alloc(8 * table_slots), "hipMalloc(peptides table)");
     a.pos = pos.get<unsigned long long>(); a.cls = cls.get<uint32_t>(); a.slot_of = slot_of.get<unsigned long long>();
-    a.table = PepTable{slots.get<unsigned long long>(), table_slots - 1}; a.occ = occ.get<unsigned long long>();
-    if (n_novel) P_TRY(launch_pep_compact(a, st), "launch(peptides compact)");
-    P_TRY(hipEventRecord(p->ev[1], st), "hipEventRecord");
+    a.table = SlotTable{slots.get<unsigned long long>(), table_slots - 1}; a.occ = occ.get<unsigned long long>();
+    if (n_novel) V2P_TRY(launch_pep_compact(a, st), "launch(peptides compact)");
+    V2P_TRY(hipEventRecord(p->ev[1], st), "hipEventRecord");
     // insert: the smallest position and the summed class counts per distinct window
-    P_TRY(hipMemsetAsync(a.table.slots, 0xFF, 8 * table_slots, st), "hipMemset(peptides table)");
-    P_TRY(hipMemsetAsync(a.occ, 0, 8 * table_slots, st), "hipMemset(peptides table)");
-    P_TRY(launch_pep_insert(a, st), "launch(peptides insert)");
-    P_TRY(hipEventRecord(p->ev[2], st), "hipEventRecord");
+    V2P_TRY(hipMemsetAsync(a.table.slots, 0xFF, 8 * table_slots, st), "hipMemset(peptides table)");
+    V2P_TRY(hipMemsetAsync(a.occ, 0, 8 * table_slots, st), "hipMemset(peptides table)");
+    V2P_TRY(launch_pep_insert(a, st), "launch(peptides insert)");
+    V2P_TRY(hipEventRecord(p->ev[2], st), "hipEventRecord");
     // collect: the list entries that are their peptide's first occurrence, in list order
     const uint64_t list_tiles = pep_tiles(n_novel);
-    P_TRY(launch_pep_firsts(a, st), "launch(peptides firsts)");
-    P_TRY(launch_device_scan(a.tile_count, uint32_t(list_tiles), d_tile_begin, nullptr, a.status + PEP_ST_PEPTIDES, st), "launch(scan)");
-    P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
-    P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    V2P_TRY(launch_pep_firsts(a, st), "launch(peptides firsts)");
+    V2P_TRY(launch_device_scan(a.tile_count, uint32_t(list_tiles), d_tile_begin, nullptr, a.status + PEP_ST_PEPTIDES, st), "launch(scan)");
+    V2P_TRY(hipMemcpyAsync(h_status, a.status, sizeof h_status, hipMemcpyDeviceToHost, st), "D2H(peptides status)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (h_status[PEP_ST_FULL]) return ctx_fail(c, V2P_ERR_HIP, "the peptide table is full (internal)", -1);
     const uint64_t n_peptides = h_status[PEP_ST_PEPTIDES];
-    P_TRY(text.alloc(some(n_peptides * p->k)), "hipMalloc(peptides result)");
-    P_TRY(out_occ.alloc(some(8 * n_peptides)), "hipMalloc(peptides result)");
-    P_TRY(out_class.alloc(some(4 * n_peptides)), "hipMalloc(peptides result)");
-    P_TRY(out_offset.alloc(some(4 * n_peptides)), "hipMalloc(peptides result)");
+    V2P_TRY(text.alloc(some(n_peptides * p->k)), "hipMalloc(peptides result)");
+    V2P_TRY(out_occ.alloc(some(8 * n_peptides)), "hipMalloc(peptides result)");
+    V2P_TRY(out_class.alloc(some(4 * n_peptides)), "hipMalloc(peptides result)");
+    V2P_TRY(out_offset.alloc(some(4 * n_peptides)), "hipMalloc(peptides result)");
     a.out_text = text.get<uint8_t>(); a.out_occ = out_occ.get<unsigned long long>(); a.out_class = out_class.get<uint32_t>(); a.out_offset = out_offset.get<uint32_t>();
-    if (n_peptides) P_TRY(launch_pep_emit(a, st), "launch(peptides emit)");
-    P_TRY(hipEventRecord(p->ev[3], st), "hipEventRecord");
-    P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (n_peptides) V2P_TRY(launch_pep_emit(a, st), "launch(peptides emit)");
+    V2P_TRY(hipEventRecord(p->ev[3], st), "hipEventRecord");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     p->text = std::move(text); p->occ = std::move(out_occ); p->first_class = std::move(out_class); p->first_offset = std::move(out_offset);
     p->n_peptides = n_peptides; p->scanned = true;
     if (info) {
@@ -492,13 +414,13 @@ int v2p_peptides_download(v2p_peptides* p, uint8_t* text, uint64_t* occ, uint32_
     if (!p->scanned) return ctx_fail(c, V2P_ERR_STATE, "v2p_peptides_download: no scan yet", -1);
     if (n != p->n_peptides) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_peptides_download: n is not the peptide count", -1);
     if (n == 0) return V2P_OK;
-    P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
+    V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
-    if (text) P_TRY(hipMemcpyAsync(text, p->text.get<void>(), n * p->k, hipMemcpyDeviceToHost, st), "D2H(peptides)");
-    if (occ) P_TRY(hipMemcpyAsync(occ, p->occ.get<void>(), 8 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
-    if (first_class) P_TRY(hipMemcpyAsync(first_class, p->first_class.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
-    if (first_offset) P_TRY(hipMemcpyAsync(first_offset, p->first_offset.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
-    P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (text) V2P_TRY(hipMemcpyAsync(text, p->text.get<void>(), n * p->k, hipMemcpyDeviceToHost, st), "D2H(peptides)");
+    if (occ) V2P_TRY(hipMemcpyAsync(occ, p->occ.get<void>(), 8 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
+    if (first_class) V2P_TRY(hipMemcpyAsync(first_class, p->first_class.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
+    if (first_offset) V2P_TRY(hipMemcpyAsync(first_offset, p->first_offset.get<void>(), 4 * n, hipMemcpyDeviceToHost, st), "D2H(peptides)");
+    V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return V2P_OK;
 }
 

@@ -517,20 +517,13 @@ class Batch:
 _default_ctx: Optional[Context] = None
 
 
-class UniqueSet:
-    """One ``v2p_unique``: the distinct records (equal transcript key and residues) of every arena added to it, deduplicated on the device;
-    class ids follow first occurrence (the rule: tests/unique_rule.py)."""
-
-    def __init__(self, ctx: Context, expected_classes: int = 0):
-        self.ctx = ctx
-        self._lib = ctx._lib
-        h = ctypes.c_void_p()
-        ctx._check(self._lib.v2p_unique_create(ctx._h, expected_classes, ctypes.byref(h)))
-        self._h = h
+class _DeviceSet:
+    """close and __del__ of a handle ``_h`` made in ``ctx``; ``_destroy`` names the library's function that frees it"""
+    _destroy = ""
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._lib.v2p_unique_destroy(self._h)
+            getattr(self._lib, self._destroy)(self._h)
         self._h = None
 
     def __del__(self):
@@ -538,6 +531,36 @@ class UniqueSet:
             self.close()
         except Exception:
             pass
+
+
+def _packed(reference: Sequence[bytes]):
+    """sequences as bytes -> what ``_create`` takes: (blob, ref_bytes, begin, lens, n_seq), back to back, every array one element longer"""
+    reference = [bytes(s) for s in reference]
+    lens = np.asarray([len(s) for s in reference] + [0], np.uint32)
+    begin = np.zeros(len(reference) + 1, np.uint64)
+    begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return np.frombuffer(b"".join(reference) + b"\0", np.uint8), int(begin[-1]), begin, lens, len(reference)
+
+
+def _padded(blob, seq_begin, seq_len):
+    """one uint8 array and a sequence table -> the same tuple, every array copied with one element behind it"""
+    blob = np.ascontiguousarray(blob, np.uint8)
+    begin, lens = np.ascontiguousarray(seq_begin, np.uint64), np.ascontiguousarray(seq_len, np.uint32)
+    pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
+    return pad(blob), int(blob.size), pad(begin), pad(lens), int(begin.size)
+
+
+class UniqueSet(_DeviceSet):
+    """One ``v2p_unique``: the distinct records (equal transcript key and residues) of every arena added to it, deduplicated on the device;
+    class ids follow first occurrence (the rule: tests/unique_rule.py)."""
+    _destroy = "v2p_unique_destroy"
+
+    def __init__(self, ctx: Context, expected_classes: int = 0):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        ctx._check(self._lib.v2p_unique_create(ctx._h, expected_classes, ctypes.byref(h)))
+        self._h = h
 
     @staticmethod
     def _info(info: "N.UniqueInfo") -> dict:
@@ -592,19 +615,15 @@ class UniqueSet:
         return out[:out_len].tobytes()
 
 
-class PeptideSet:
+class PeptideSet(_DeviceSet):
     """One ``v2p_peptides``: the K-byte windows of a UniqueSet's classes that occur in no reference sequence, each once, filtered and
     deduplicated on the device (the rule: tests/peptides_rule.py).  ``reference``: the sequences as bytes."""
+    _destroy = "v2p_peptides_destroy"
 
     def __init__(self, ctx: Context, k: int, reference: Sequence[bytes] = ()):
         self.ctx, self.k = ctx, k
         self._lib = ctx._lib
-        reference = [bytes(s) for s in reference]
-        lens = np.asarray([len(s) for s in reference] + [0], np.uint32)
-        begin = np.zeros(len(reference) + 1, np.uint64)
-        begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(reference) + b"\0", np.uint8)
-        self._create(blob, int(begin[-1]), begin, lens, len(reference))
+        self._create(*_packed(reference))
 
     def _create(self, blob: np.ndarray, ref_bytes: int, begin: np.ndarray, lens: np.ndarray, n_seq: int):
         """v2p_peptides_create on the arrays as given (tests hand it ranges that leave the reference)"""
@@ -618,22 +637,8 @@ class PeptideSet:
         """the reference as one uint8 array and a sequence table (sequences may overlap)"""
         self = cls.__new__(cls)
         self.ctx, self.k, self._lib = ctx, k, ctx._lib
-        blob = np.ascontiguousarray(blob, np.uint8)
-        begin, lens = np.ascontiguousarray(seq_begin, np.uint64), np.ascontiguousarray(seq_len, np.uint32)
-        pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
-        self._create(pad(blob), int(blob.size), pad(begin), pad(lens), int(begin.size))
+        self._create(*_padded(blob, seq_begin, seq_len))
         return self
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._lib.v2p_peptides_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def scan(self, uset: "UniqueSet") -> dict:
         """v2p_peptides_scan: every window of every class the set holds now; returns the info."""
@@ -656,20 +661,16 @@ class PeptideSet:
         return {"text": text[:n], "occ": occ[:n], "first_class": cls[:n], "first_offset": off[:n]}
 
 
-class TrypticSet:
+class TrypticSet(_DeviceSet):
     """One ``v2p_tryptic``: the tryptic products (cleavage after K or R unless P follows, ``missed`` missed cleavages, ``min_len`` ..
     ``max_len`` bytes) of a UniqueSet's classes that are no product of any reference sequence, each once, digested, filtered and
     deduplicated on the device (the rule: tests/tryptic_rule.py).  ``reference``: the sequences as bytes.  ``hash_mask`` is for tests."""
+    _destroy = "v2p_tryptic_destroy"
 
     def __init__(self, ctx: Context, missed: int, min_len: int, max_len: int, reference: Sequence[bytes] = (), hash_mask: int = 2 ** 64 - 1):
         self.ctx, self.params, self.hash_mask = ctx, (missed, min_len, max_len), hash_mask
         self._lib = ctx._lib
-        reference = [bytes(s) for s in reference]
-        lens = np.asarray([len(s) for s in reference] + [0], np.uint32)
-        begin = np.zeros(len(reference) + 1, np.uint64)
-        begin[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(reference) + b"\0", np.uint8)
-        self._create(blob, int(begin[-1]), begin, lens, len(reference))
+        self._create(*_packed(reference))
 
     def _create(self, blob: np.ndarray, ref_bytes: int, begin: np.ndarray, lens: np.ndarray, n_seq: int):
         """v2p_tryptic_create on the arrays as given (tests hand it ranges that leave the reference)"""
@@ -684,22 +685,8 @@ class TrypticSet:
         """the reference as one uint8 array and a sequence table (sequences may overlap)"""
         self = cls.__new__(cls)
         self.ctx, self.params, self.hash_mask, self._lib = ctx, (missed, min_len, max_len), hash_mask, ctx._lib
-        blob = np.ascontiguousarray(blob, np.uint8)
-        begin, lens = np.ascontiguousarray(seq_begin, np.uint64), np.ascontiguousarray(seq_len, np.uint32)
-        pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
-        self._create(pad(blob), int(blob.size), pad(begin), pad(lens), int(begin.size))
+        self._create(*_padded(blob, seq_begin, seq_len))
         return self
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._lib.v2p_tryptic_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def scan(self, uset: "UniqueSet") -> dict:
         """v2p_tryptic_scan: every product of every class the set holds now; returns the info."""
