@@ -175,7 +175,10 @@ typedef struct v2p_mutation {
 
 /* Groups every haplotype's consequence ids by transcript the way vcf_tools.rs:82-96 does (sorted unique
  * transcript ids; a consequence joins every group whose id occurs anywhere in its text; Mutation::new failures
- * dropped), sorts each group by mut_aa_position and applies drop_replicate.  n_threads = 0 -> hardware threads. */
+ * dropped), sorts each group by mut_aa_position and applies drop_replicate.  n_threads = 0 -> hardware threads.
+ * hap_begin[n_haps + 1] must ascend: where it descends the call returns -1 with v2p_groups_error "hap_begin descends" and
+ * v2p_groups_error_haplotype = the list, and reads no id.  An id that is not below n_consequences, or one of a start_lost
+ * consequence with fewer than three fields, returns V2P_ERR_DUPLICATE_POS with the list and the reason. */
 int  v2p_groups_build(const v2p_vcf_index* x, const uint8_t* text,
                       const uint64_t* hap_begin, const uint32_t* ids, uint64_t n_haps, uint32_t n_threads,
                       v2p_groups** out);

@@ -277,6 +277,8 @@ void fill_from_tables(v2p_groups* g, const Table& T)
 int group_lists(v2p_groups* g, const Table& T, const uint64_t* hap_begin, const uint32_t* ids, uint64_t n_haps, uint32_t n_threads)
 {
     const uint64_t n_csq = T.rank.size();
+    for (uint64_t h = 0; h < n_haps; ++h)                                // a list's length is a difference of these: refuse, never read
+        if (hap_begin[h + 1] < hap_begin[h]) { g->error_hap = int64_t(h); g->error = "hap_begin descends"; return -1; }
     struct HapOut { std::vector<uint32_t> group_tx; std::vector<uint32_t> group_size; std::vector<uint32_t> members; };
     std::vector<HapOut> outs(n_haps);
     std::atomic<uint64_t> next{0};
@@ -412,8 +414,9 @@ int v2p_csq_tables_from_arrays(const uint8_t* text_u8, uint64_t n_text, uint64_t
         names[r] = std::string_view(text + tx_begin[r], tx_len[r]);
         if (r && !(names[r - 1] < names[r])) return -1;              // sorted and unique, as build_tables leaves them
     }
-    for (uint64_t i = 0; i < n_csq; ++i) {
+    for (uint64_t i = 0; i < n_csq; ++i)                              // every offset first: extra and aa end where the last one says
         if (extra_begin[i + 1] < extra_begin[i] || aa_begin[i + 1] < aa_begin[i]) return -1;
+    for (uint64_t i = 0; i < n_csq; ++i) {
         if (rank[i] != ~0u && rank[i] >= n_tx) return -1;
         if ((flags[i] & 1u) && (rank[i] == ~0u || (flags[i] >> 8 & 0xffu) >= 22)) return -1;
         if (aa_ref_len[i] > aa_begin[i + 1] - aa_begin[i]) return -1;
