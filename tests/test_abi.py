@@ -107,7 +107,8 @@ def test_product_library_exports_only_what_the_headers_declare(built):
     declared = set(_declared("vcf2prot_hip.h")) | {n for n in _declared("v2p_frontend.h") if n.startswith("v2p_decode_")}
     assert exported <= declared, sorted(exported - declared)
     assert declared <= exported, sorted(declared - exported)
-    for dev_only in ("v2p_batch_download_patch_image", "v2p_stitch_launch", "v2p_bench_set_variant", "v2p_scan_launch"):
+    for dev_only in ("v2p_batch_download_patch_image", "v2p_stitch_launch", "v2p_bench_set_variant", "v2p_scan_launch", "v2p_build_scan_launch",
+                     "v2p_build_scan_scratch_entries", "v2p_order_blocks_launch", "v2p_order_blocks_thread_blocks"):
         assert dev_only not in exported
     text = open(os.path.join(ROOT, "include", "vcf2prot_hip.h")).read()
     assert "variant" not in text.split("typedef struct {\n    uint32_t nontemporal;")[1].split("} v2p_launch_opts;")[0].replace("`variant`", "")

@@ -238,6 +238,12 @@ BENCH_API = {
     "v2p_bench_set_variant": (c_int, [c_void_p, c_uint32]),
     # the front end's prefix sums on caller-owned memory (tests/test_gpu_scan.py)
     "v2p_scan_launch": (c_int, [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p]),
+    # the builders' prefix sums and blocked chunk order on caller-owned memory (tests/test_gpu_build_scans.py, tests/test_gpu_order_rule.py)
+    "v2p_build_scan_launch": (c_int, [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64]),
+    "v2p_build_scan_scratch_entries": (c_uint64, [c_int, c_uint64]),
+    "v2p_order_blocks_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "v2p_order_blocks_thread_blocks": (c_uint64, [c_uint64, c_uint32]),
 }
 _bench = None
 

@@ -7,6 +7,8 @@
 #include "../stitch_device.hpp"
 #include "../device_scan.h"
 #include "../group_tasks.h"
+#include "../build_kernels.h"
+#include "../build_rows.h"
 #include "v2p_bench.h"
 
 namespace v2p {
@@ -372,5 +374,39 @@ int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, vo
     return launch_device_scan(static_cast<const uint32_t*>(d_in), uint32_t(n), kind == 0 ? static_cast<unsigned long long*>(d_out) : nullptr,
                               kind == 1 ? static_cast<uint32_t*>(d_out) : nullptr, static_cast<unsigned long long*>(d_scratch), st) == hipSuccess ? 0 : -2;
 }
+
+int v2p_build_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch, uint64_t first)
+{
+    using namespace v2p;
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (kind < 0 || kind > 3 || !d_out || (n && (!d_in || !d_scratch)) || (n + 1023) / 1024 > 0xFFFFFFFFull) return -1;
+    uint64_t* out = static_cast<uint64_t*>(d_out);
+    uint64_t* scratch = static_cast<uint64_t*>(d_scratch);
+    const uint32_t* in32 = static_cast<const uint32_t*>(d_in);
+    hipError_t e;
+    if (kind == 0) e = launch_scan_u32(in32, n, out, scratch, st);
+    else if (kind == 1) e = launch_scan_u32_from(in32, n, out, scratch, first, st);
+    else if (kind == 2) e = launch_scan_u32_chained(in32, n, out, scratch, st);
+    else e = launch_rows_scan_u64(static_cast<const uint64_t*>(d_in), n, scratch, out, st);
+    return e == hipSuccess ? 0 : -2;
+}
+
+uint64_t v2p_build_scan_scratch_entries(int kind, uint64_t n)
+{
+    return kind == 3 ? v2p::rows_scan_scratch_entries(n) : v2p::scan_tiles_for(n);
+}
+
+int v2p_order_blocks_launch(void* hip_stream, const void* d_chunks, const uint8_t* d_bucket, const uint8_t* d_sub, uint64_t n, uint32_t nb,
+                            uint32_t* d_subhist, uint64_t* d_substart, uint64_t* d_tiles, void* d_by_window, uint8_t* d_bucket2,
+                            uint32_t* d_hist8, uint32_t* d_tot, void* d_out)
+{
+    using namespace v2p;
+    if (n && nb && (!d_chunks || !d_bucket || !d_sub || !d_subhist || !d_substart || !d_tiles || !d_by_window || !d_bucket2 || !d_hist8 || !d_tot || !d_out)) return -1;
+    if (n && (nb > n || nb > 65535u)) return -1;                      // (a block without entries; blocks are the grid's y)
+    return launch_order_blocks(static_cast<const Chunk*>(d_chunks), d_bucket, d_sub, n, nb, d_subhist, d_substart, d_tiles, static_cast<Chunk*>(d_by_window),
+                               d_bucket2, d_hist8, d_tot, static_cast<Chunk*>(d_out), reinterpret_cast<hipStream_t>(hip_stream)) == hipSuccess ? 0 : -2;
+}
+
+uint64_t v2p_order_blocks_thread_blocks(uint64_t n, uint32_t nb) { return v2p::order_blocks_thread_blocks(n, nb); }
 
 }  // extern "C"

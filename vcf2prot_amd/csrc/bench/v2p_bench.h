@@ -102,6 +102,19 @@ int v2p_gather_bench_launch(void* hip_stream, const uint8_t* d_src, uint64_t win
 /* the front end's prefix sums through the product's launchers on caller-owned device memory (tests/test_gpu_scan.py): kind 0 / 1 = launch_device_scan,
  * uint32_t in[n], uint64_t / uint32_t out[n + 1], scratch = the 64-bit total; 2 = launch_tasks_tile_scan, TaskCount in[n], out[n + 1], scratch[ceil(n / TASKS_SCAN_TILE) + 1] */
 int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch);
+/* the builders' three-pass prefix sums on caller-owned device memory (tests/test_gpu_build_scans.py): kind 0 = launch_scan_u32, 1 = launch_scan_u32_from
+ * (out[i] = first + in[0] + .. + in[i - 1]), 2 = launch_scan_u32_chained (the caller has put the running total in d_out[0]; n = 0 launches nothing),
+ * 3 = launch_rows_scan_u64 (uint64_t in[n], sums modulo 2^64); kinds 0 .. 2: uint32_t in[n]; all: uint64_t out[n + 1], scratch of
+ * v2p_build_scan_scratch_entries(kind, n) uint64_t.  0, -1 for a bad argument, -2 for a HIP launch error */
+int v2p_build_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch, uint64_t first);
+uint64_t v2p_build_scan_scratch_entries(int kind, uint64_t n);
+/* launch_order_blocks (csrc/build_kernels.h) on caller-owned device memory (tests/test_gpu_order_rule.py): v2p_chunk chunks[n], by_window[n], out[n];
+ * bucket[n], sub[n], bucket2[n] bytes; with T = v2p_order_blocks_thread_blocks(n, nb): subhist[256 T] u32, substart[256 T + 1] u64,
+ * tiles[scratch of the u32 scan for 256 T entries], hist8[8 T] u32, tot[8 nb] u32.  n = 0 or nb = 0 launches nothing.  Return values as above */
+int v2p_order_blocks_launch(void* hip_stream, const void* d_chunks, const uint8_t* d_bucket, const uint8_t* d_sub, uint64_t n, uint32_t nb,
+                            uint32_t* d_subhist, uint64_t* d_substart, uint64_t* d_tiles, void* d_by_window, uint8_t* d_bucket2,
+                            uint32_t* d_hist8, uint32_t* d_tot, void* d_out);
+uint64_t v2p_order_blocks_thread_blocks(uint64_t n, uint32_t nb);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -78,6 +78,8 @@ inline void rows_ranges(const RowsArgs& a, uint64_t& t0, uint64_t& t1, uint64_t&
 // arena bytes per tile (+ u64 exclusive scan into tile_res_base, total behind the last tile)
 hipError_t launch_rows_tile_bytes(const RowsArgs& a, uint64_t* scan_scratch, hipStream_t stream);
 uint64_t rows_scan_scratch_entries(uint64_t n);
+// its scan on its own: out[i] = in[0] + .. + in[i - 1] (modulo 2^64) for i = 0 .. n, scratch of rows_scan_scratch_entries(n) entries
+hipError_t launch_rows_scan_u64(const uint64_t* in, uint64_t n, uint64_t* scratch, uint64_t* out, hipStream_t stream);
 constexpr uint32_t ROWS_CHUNK_PAD = 96;            // chunk slots per segment of 640 rows in the cutter's padded table, at least (64 ten-row chunks tile a segment)
 // ... and for a stream of these sizes: a chunk takes rows while its descriptors fit its kernel (64 / 1024), so a stream of b result bytes
 // per Task fills a chunk after about max_desc * b / 1024 rows -- 1.5 x the segment's chunks at that rate, between 96 and 640 (one row per

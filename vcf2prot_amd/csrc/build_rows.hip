@@ -803,6 +803,17 @@ __global__ __launch_bounds__(256) void rows_keys_kernel(RowsArgs a, uint64_t n_c
 
 uint64_t rows_scan_scratch_entries(uint64_t n) { return (n + RS_TILE - 1) / RS_TILE + 2; }
 
+// out[i] = in[0] + .. + in[i - 1] modulo 2^64 for i = 0 .. n; scratch holds rows_scan_scratch_entries(n) entries
+hipError_t launch_rows_scan_u64(const uint64_t* in, uint64_t n, uint64_t* scratch, uint64_t* out, hipStream_t stream)
+{
+    const uint64_t n_t = (n + RS_TILE - 1) / RS_TILE;
+    if (n == 0) return hipMemsetAsync(out, 0, 8, stream);            // (no tile, no grid: the total alone)
+    hipLaunchKernelGGL(rows_scan_sums, dim3(uint32_t(n_t)), dim3(256), 0, stream, in, n, scratch);
+    hipLaunchKernelGGL(rows_scan_tiles, dim3(1), dim3(1024), 0, stream, scratch, n_t);
+    hipLaunchKernelGGL(rows_scan_apply, dim3(uint32_t(n_t)), dim3(256), 0, stream, in, n, scratch, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_rows_tile_bytes(const RowsArgs& a, uint64_t* scan_scratch, hipStream_t stream)
 {
     if (a.K >= 32u) hipLaunchKernelGGL(rows_tile_bytes_wave_kernel, dim3(uint32_t((a.n_tiles + 3) / 4)), dim3(256), 0, stream, a);
@@ -811,11 +822,7 @@ hipError_t launch_rows_tile_bytes(const RowsArgs& a, uint64_t* scan_scratch, hip
         if (e != hipSuccess) return e;
         if (a.n_tx) hipLaunchKernelGGL(rows_tile_bytes_kernel, dim3(uint32_t((a.n_tx + 255) / 256)), dim3(256), 0, stream, a);
     }
-    const uint64_t n = a.n_tiles, n_t = (n + RS_TILE - 1) / RS_TILE;
-    hipLaunchKernelGGL(rows_scan_sums, dim3(uint32_t(n_t)), dim3(256), 0, stream, a.tile_bytes, n, scan_scratch);
-    hipLaunchKernelGGL(rows_scan_tiles, dim3(1), dim3(1024), 0, stream, scan_scratch, n_t);
-    hipLaunchKernelGGL(rows_scan_apply, dim3(uint32_t(n_t)), dim3(256), 0, stream, a.tile_bytes, n, scan_scratch, a.tile_res_base);
-    return hipGetLastError();
+    return launch_rows_scan_u64(a.tile_bytes, a.n_tiles, scan_scratch, a.tile_res_base, stream);
 }
 
 static_assert(ROWS_PAD == ROWS_PAD_SLOTS && ROWS_PAD == ROWS_TILE_SLOTS, "build_rows.h, sir_pack.hpp");
