@@ -517,6 +517,37 @@ int  v2p_tryptic_count(const v2p_tryptic*, uint64_t* n, uint64_t* text_bytes);
 int  v2p_tryptic_download(v2p_tryptic*, uint8_t* text, uint64_t* text_begin, uint64_t* occ,
                           uint32_t* first_class, uint32_t* first_offset, uint64_t n, uint64_t text_bytes);
 
+/* ---- carriers: which probands carry each variant peptide (vcf2prot_amd/csrc/peptide_carriers.hip) ----
+ * A set has P >= 1 probands, 0 .. P - 1, and every record an owner among them.  Proband q CARRIES CLASS c iff some record of class c is
+ * owned by q, and CARRIES PEPTIDE x iff it carries some class in whose residues x occurs -- as a K-byte window (v2p_peptides) or as a
+ * product under the set's (M, MIN, MAX) (v2p_tryptic), both exactly as above.  A ROW is W = ceil(P / 64) 64-bit words: bit q % 64 of word
+ * q / 64 is proband q, the bits at and above P are zero.  Per peptide, indexed as v2p_*_download delivers them: its row and n_carriers,
+ * the row's popcount; per proband: the number of peptides it carries.  OR and integer add commute: nothing depends on the order in which
+ * atomics arrive, and two runs give equal bytes.  The rule in Python: tests/carriers_rule.py. */
+typedef struct v2p_carriers v2p_carriers;
+typedef struct { uint64_t n_probands, words, n_class_rows,        /* of the carriers the scan used */
+                 n_entries, n_pairs, n_peptides;                   /* novel occurrences walked; the sum of n_carriers over the peptides; the peptides */
+                 float ms_carry, ms_count; } v2p_carriers_info;    /* HIP events on the context's stream: index + row ORs; popcounts + per-proband sums */
+int  v2p_carriers_create(v2p_ctx*, uint32_t n_probands, v2p_carriers** out);          /* n_probands == 0: V2P_ERR_INVALID_ARG */
+void v2p_carriers_destroy(v2p_carriers*);
+/* record i belongs to class class_of[i] (as v2p_unique_add / _add_records returned it) and to proband proband_of[i]; HOST arrays of n.
+ * Sets bit (class, proband) on the device; class rows grow by doubling with a device copy.  Idempotent.
+ * V2P_ERR_INVALID_ARG with the index: proband_of[i] >= n_probands.  A failed call leaves the set as it was. */
+int  v2p_carriers_add(v2p_carriers*, const uint32_t* class_of, const uint32_t* proband_of, uint64_t n);
+/* class rows now: *n_rows = 1 + the largest class id ever added (0 if none); bits [n_rows * W], n_carriers [n_rows]; pointers may be NULL.
+ * With bits or n_carriers given, n must be that number of rows (V2P_ERR_INVALID_ARG). */
+int  v2p_carriers_classes(v2p_carriers*, uint64_t* n_rows, uint64_t* bits, uint32_t* n_carriers, uint64_t n);
+/* Everything v2p_*_scan does -- the base result is byte for byte a plain scan's -- and the carrier rows of its peptides.  A class with no
+ * row (never added) has no carriers; a peptide may have none.  V2P_ERR_INVALID_ARG: the carriers or u belong to another context; the
+ * carriers hold a row for a class id >= u's current number of classes.  A failed call leaves the earlier result, base and carrier rows;
+ * a later plain v2p_*_scan replaces the base result and drops the carrier rows.  Either info may be NULL. */
+int  v2p_peptides_scan_carriers(v2p_peptides*, v2p_unique* u, v2p_carriers*, v2p_peptides_info*, v2p_carriers_info*);
+int  v2p_tryptic_scan_carriers (v2p_tryptic*,  v2p_unique* u, v2p_carriers*, v2p_tryptic_info*,  v2p_carriers_info*);
+/* n = the peptide count, words = W of the carriers the scan used (V2P_ERR_INVALID_ARG); bits [n * W], n_carriers [n], per_proband [P];
+ * any pointer may be NULL.  V2P_ERR_STATE unless the set's CURRENT result came from a *_scan_carriers call. */
+int  v2p_peptides_download_carriers(v2p_peptides*, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words);
+int  v2p_tryptic_download_carriers (v2p_tryptic*,  uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.

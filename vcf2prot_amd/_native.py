@@ -133,6 +133,14 @@ HIP_API = {
     "v2p_tryptic_scan": (c_int, [c_void_p, c_void_p, c_void_p]),
     "v2p_tryptic_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_tryptic_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64]),
+    "v2p_carriers_create": (c_int, [c_void_p, c_uint32, POINTER(c_void_p)]),
+    "v2p_carriers_destroy": (None, [c_void_p]),
+    "v2p_carriers_add": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
+    "v2p_carriers_classes": (c_int, [c_void_p, POINTER(c_uint64), c_void_p, c_void_p, c_uint64]),
+    "v2p_peptides_scan_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_tryptic_scan_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_peptides_download_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]),
+    "v2p_tryptic_download_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]),
 }
 
 _hip = None
@@ -162,6 +170,12 @@ class PeptidesInfo(ctypes.Structure):
     _fields_ = [("k", c_uint64), ("n_ref_windows", c_uint64), ("n_ref_kmers", c_uint64), ("ref_table_slots", c_uint64), ("n_windows", c_uint64),
                 ("n_novel_windows", c_uint64), ("n_peptides", c_uint64), ("table_slots", c_uint64),
                 ("ms_ref_build", ctypes.c_float), ("ms_filter", ctypes.c_float), ("ms_insert", ctypes.c_float), ("ms_collect", ctypes.c_float)]
+
+
+class CarriersInfo(ctypes.Structure):
+    """v2p_carriers_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("n_probands", c_uint64), ("words", c_uint64), ("n_class_rows", c_uint64), ("n_entries", c_uint64), ("n_pairs", c_uint64),
+                ("n_peptides", c_uint64), ("ms_carry", ctypes.c_float), ("ms_count", ctypes.c_float)]
 
 
 class TrypticInfo(ctypes.Structure):

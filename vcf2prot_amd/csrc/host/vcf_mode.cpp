@@ -53,6 +53,7 @@ using Pipeline = Owned<v2p_pipeline, v2p_pipeline_destroy>;
 using Unique = Owned<v2p_unique, v2p_unique_destroy>;
 using Peptides = Owned<v2p_peptides, v2p_peptides_destroy>;
 using Tryptic = Owned<v2p_tryptic, v2p_tryptic_destroy>;
+using Carriers = Owned<v2p_carriers, v2p_carriers_destroy>;
 using Stream = Owned<v2p_stream, v2p_stream_destroy>;
 
 // the end of a run that cannot go on: the line is thrown, main() prints it and exits with 101
@@ -281,11 +282,14 @@ bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
         o.int_map |= is(i, "-i", "--write_int_map");
         o.device_int_map |= is(i, "--device-int-map");
         o.unique |= is(i, "--unique");
+        o.carriers |= is(i, "--carriers");
     }
     const char* refusal = nullptr;
     if (o.bgzf && o.compressed) refusal = "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one";
     else if (o.unique && (o.compressed || o.bgzf || o.host_build))
         refusal = "usage: --unique writes unique_proteins.fasta and unique_proteins.tsv from the device's record set, no per-proband file: it cannot be combined with -c, --bgzf or --host-build";
+    else if (o.carriers && (!o.unique || (!peptides_arg && !tryptic_arg)))
+        refusal = "usage: --carriers writes {stem}.carriers.tsv beside every peptide file and peptide_carriers_summary.tsv: it needs --unique and at least one of --peptides and --tryptic";
     else if (peptides_arg && (!o.unique || !parse_peptide_ks(peptides_arg, o.peptide_ks)))
         refusal = "usage: --peptides K[,K...] writes variant_peptides_k{K}.tsv from the classes of --unique: it needs --unique and at most eight window lengths, each 1 .. 16";
     else if (tryptic_arg && (!o.unique || !parse_tryptic(tryptic_arg, o)))
@@ -307,7 +311,8 @@ struct Report {
     float ims[3] = {}, xms[5] = {}, kms[4] = {}, tms[7] = {}, sms[2] = {}, gms[5] = {}, jms[5] = {};
     v2p_tables_info tinf{}; v2p_stats_info sinfo{}; v2p_groups_info ginfo{}; v2p_unique_info u_sum{};
     bool tables_on_device = false, device_groups = false, tasks_on_device = false, int_map_on_device = false;
-    std::string pep_json, tryptic_json;
+    std::string pep_json, tryptic_json, carriers_json;
+    v2p_carriers_info k_last{};                                      // (of the last scan with carriers: the set's probands, words and class rows)
 
     void print(const VcfOptions& opt, const std::string& tasks_json) const      // tasks_json says where steps 4a / 4b ran
     {
@@ -346,6 +351,9 @@ struct Report {
                         (unsigned long long)u_fasta_bytes, (unsigned long long)u_tsv_bytes, u_sum.ms_digest, u_sum.ms_insert, u_sum.ms_verify, u_sum.ms_commit);
         if (!opt.peptide_ks.empty()) std::printf(", \"peptides\": {%s}", pep_json.c_str());
         if (opt.tryptic) std::printf(", \"tryptic\": {%s}", tryptic_json.c_str());
+        if (opt.carriers)
+            std::printf(", \"carriers\": {\"probands\": %llu, \"words\": %llu, \"class_rows\": %llu, \"files\": {%s}}", (unsigned long long)k_last.n_probands,
+                        (unsigned long long)k_last.words, (unsigned long long)k_last.n_class_rows, carriers_json.c_str());
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     }
 };
@@ -832,6 +840,7 @@ static Batch execute_or_host_build(GpuContext& ctx, v2p_batch* b, v2p_stream* rs
 // v2p_unique_emit) and the records' classes unique_proteins.tsv ----
 struct UniqueSink {
     GpuContext& ctx; v2p_unique* uq; const VcfOptions& opt; const std::vector<std::string>& samples; const Fasta& ref; const ResidentReference& rr; Report& rep;
+    v2p_carriers* kq;                                                // --carriers: a proband row per class, filled add by add; else null
     std::vector<uint32_t> u_class;                                   // the class of every record, slice after slice
     std::vector<uint64_t> u_hap_begin{0};                            // the first record of every haplotype
 
@@ -845,8 +854,15 @@ struct UniqueSink {
         v2p_unique_info inf{};
         chk(ctx, v2p_unique_add(uq, eb, rs, u_class.data() + at, &inf));
         u_class.resize(at + n_tx);
+        const uint64_t hap0 = u_hap_begin.size() - 1;
         for (uint64_t h = 0; h < n_haps; ++h) u_hap_begin.push_back(u_hap_begin.back() + hap_tx[h]);
         if (u_hap_begin.back() != u_class.size()) fail("panicked: a slice's stream holds another number of records than its haplotypes");
+        if (kq) {                                                    // a record's owner: the sample of its haplotype
+            std::vector<uint32_t> owner(n_tx + 1);
+            for (uint64_t h = 0; h < n_haps; ++h)
+                for (uint64_t r = u_hap_begin[hap0 + h]; r < u_hap_begin[hap0 + h + 1]; ++r) owner[r - at] = uint32_t((hap0 + h) / 2);
+            chk(ctx, v2p_carriers_add(kq, u_class.data() + at, owner.data(), n_tx));
+        }
         v2p_unique_info& sum = rep.u_sum;
         sum.n_records += inf.n_records; sum.n_classes = inf.n_classes; sum.store_bytes = inf.store_bytes; sum.table_slots = inf.table_slots;
         sum.ms_digest += inf.ms_digest; sum.ms_insert += inf.ms_insert; sum.ms_verify += inf.ms_verify; sum.ms_commit += inf.ms_commit;
@@ -885,6 +901,50 @@ struct UniqueSink {
         }
         return tsv;
     }
+    // ---- --carriers: beside a peptide file {stem}.tsv, {stem}.carriers.tsv -- per peptide, in the same order, the number of probands that carry
+    // it and their names in column order -- from the rows of a scan with carriers; the per-proband counts become a column of the summary ----
+    std::vector<std::pair<std::string, std::vector<uint64_t>>> carrier_columns;
+    template <class Peptide, class Download>
+    void write_carriers(const std::string& stem, uint64_t n, Peptide peptide, Download download, const v2p_carriers_info& kinf)
+    {
+        const uint32_t W = uint32_t(kinf.words);
+        std::vector<uint64_t> bits(n * W + 1), per(samples.size() + 1);
+        std::vector<uint32_t> count(n + 1);
+        download(bits.data(), count.data(), per.data(), n, W);
+        std::vector<uint32_t> order(n);
+        for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return peptide(a) < peptide(b); });
+        std::string tsv = "#peptide\tcarriers\tprobands\n";
+        for (const uint32_t i : order) {
+            tsv.append(peptide(i));
+            tsv += "\t" + std::to_string(count[i]) + "\t";
+            bool any = false;
+            for (uint64_t q = 0; q < samples.size(); ++q)
+                if ((bits[uint64_t(i) * W + (q >> 6)] >> (q & 63u)) & 1u) { if (any) tsv += ","; tsv += samples[q]; any = true; }
+            tsv += "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/" + stem + ".carriers.tsv", tsv);
+        per.resize(samples.size());
+        carrier_columns.emplace_back(stem, std::move(per));
+        char buf[320];
+        std::snprintf(buf, sizeof buf, "%s\"%s\": {\"n_peptides\": %llu, \"n_pairs\": %llu, \"ms_carry\": %.3f, \"ms_count\": %.3f, \"tsv_bytes\": %llu}",
+                      rep.carriers_json.empty() ? "" : ", ", stem.c_str(), (unsigned long long)kinf.n_peptides, (unsigned long long)kinf.n_pairs, kinf.ms_carry, kinf.ms_count,
+                      (unsigned long long)tsv.size());
+        rep.carriers_json += buf;
+        rep.k_last = kinf;
+    }
+    void write_carriers_summary()
+    {
+        std::string tsv = "#proband";
+        for (const auto& col : carrier_columns) tsv += "\t" + col.first;
+        tsv += "\n";
+        for (uint64_t q = 0; q < samples.size(); ++q) {
+            tsv += samples[q];
+            for (const auto& col : carrier_columns) tsv += "\t" + std::to_string(col.second[q]);
+            tsv += "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/peptide_carriers_summary.tsv", tsv);
+    }
     void write_peptides(const std::vector<std::string>& class_name)
     {
         const auto [blob, seq_begin, seq_len] = reference_blob();
@@ -892,14 +952,19 @@ struct UniqueSink {
             Peptides ps;
             chk(ctx, v2p_peptides_create(ctx.raw(), K, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ps)));
             v2p_peptides_info inf{};
-            chk(ctx, v2p_peptides_scan(ps.get(), uq, &inf));
+            v2p_carriers_info kinf{};
+            chk(ctx, kq ? v2p_peptides_scan_carriers(ps.get(), uq, kq, &inf, &kinf) : v2p_peptides_scan(ps.get(), uq, &inf));
             const uint64_t n = inf.n_peptides;
             std::vector<uint8_t> text(n * K + 1);
             std::vector<uint64_t> occ(n + 1);
             std::vector<uint32_t> fc(n + 1), fo(n + 1);
             chk(ctx, v2p_peptides_download(ps.get(), text.data(), occ.data(), fc.data(), fo.data(), n));
-            const std::string tsv = peptide_tsv(n, [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K); }, occ, fc, fo, class_name);
+            const auto peptide = [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[uint64_t(i) * K]), K); };
+            const std::string tsv = peptide_tsv(n, peptide, occ, fc, fo, class_name);
             write_tsv(std::string(opt.outdir) + "/variant_peptides_k" + std::to_string(K) + ".tsv", tsv);
+            if (kq)
+                write_carriers("variant_peptides_k" + std::to_string(K), n, peptide,
+                               [&](uint64_t* bits, uint32_t* count, uint64_t* per, uint64_t m, uint32_t W) { chk(ctx, v2p_peptides_download_carriers(ps.get(), bits, count, per, m, W)); }, kinf);
             char buf[640];
             std::snprintf(buf, sizeof buf, "%s\"%u\": {\"n_ref_windows\": %llu, \"n_ref_kmers\": %llu, \"ref_table_slots\": %llu, \"n_windows\": %llu, \"n_novel_windows\": %llu, "
                           "\"n_peptides\": %llu, \"table_slots\": %llu, \"tsv_bytes\": %llu, \"ms_ref_build\": %.3f, \"ms_filter\": %.3f, \"ms_insert\": %.3f, \"ms_collect\": %.3f}",
@@ -919,15 +984,19 @@ struct UniqueSink {
         chk(ctx, v2p_tryptic_create(ctx.raw(), opt.tryptic_missed, opt.tryptic_min, opt.tryptic_max, ~0ull, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(),
                                     seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ts)));
         v2p_tryptic_info inf{};
-        chk(ctx, v2p_tryptic_scan(ts.get(), uq, &inf));
+        v2p_carriers_info kinf{};
+        chk(ctx, kq ? v2p_tryptic_scan_carriers(ts.get(), uq, kq, &inf, &kinf) : v2p_tryptic_scan(ts.get(), uq, &inf));
         const uint64_t n = inf.n_peptides;
         std::vector<uint8_t> text(inf.text_bytes + 1);
         std::vector<uint64_t> begin(n + 2), occ(n + 1);
         std::vector<uint32_t> fc(n + 1), fo(n + 1);
         chk(ctx, v2p_tryptic_download(ts.get(), text.data(), begin.data(), occ.data(), fc.data(), fo.data(), n, inf.text_bytes));
-        const std::string tsv = peptide_tsv(n, [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[begin[i]]), size_t(begin[i + 1] - begin[i])); },
-                                            occ, fc, fo, class_name);
+        const auto peptide = [&](uint32_t i) { return std::string_view(reinterpret_cast<const char*>(&text[begin[i]]), size_t(begin[i + 1] - begin[i])); };
+        const std::string tsv = peptide_tsv(n, peptide, occ, fc, fo, class_name);
         write_tsv(std::string(opt.outdir) + "/tryptic_peptides.tsv", tsv);
+        if (kq)
+            write_carriers("tryptic_peptides", n, peptide,
+                           [&](uint64_t* bits, uint32_t* count, uint64_t* per, uint64_t m, uint32_t W) { chk(ctx, v2p_tryptic_download_carriers(ts.get(), bits, count, per, m, W)); }, kinf);
         char buf[800];
         std::snprintf(buf, sizeof buf, "\"missed\": %llu, \"min_len\": %llu, \"max_len\": %llu, \"n_ref_products\": %llu, \"n_ref_peptides\": %llu, \"ref_table_slots\": %llu, "
                       "\"n_boundaries\": %llu, \"n_products\": %llu, \"n_novel_products\": %llu, \"n_peptides\": %llu, \"text_bytes\": %llu, \"table_slots\": %llu, "
@@ -996,6 +1065,7 @@ struct UniqueSink {
             for (uint64_t c = 0; c < nc; ++c) class_name[c] = *cname[c] + "_v" + std::to_string(k_of[c]);
             if (!opt.peptide_ks.empty()) write_peptides(class_name);
             if (opt.tryptic) write_tryptic(class_name);
+            if (kq) write_carriers_summary();
         }
         rep.t_write_acc += sw.seconds();
     }
@@ -1236,13 +1306,13 @@ static void run_host_tasks(const Emit& e, const v2p_groups* g, Stopwatch& lap)
 }
 
 // The stages of a run.  The handles are declared so that what is left at the end goes in this order: the batch, the groups, the tables and
-// the decode (both long gone by then), the index, the distinct-record set, and last the context every one of them works on.
+// the decode (both long gone by then), the index, the distinct-record set, its carriers, and last the context every one of them works on.
 int vcf_mode(const VcfOptions& opt)
 {
     Report rep;
     Stopwatch lap;
     std::unique_ptr<GpuContext> ctx_box;
-    Unique uq; Index idx; Decode dec; Tables tb; Groups g; Batch b;
+    Carriers kq; Unique uq; Index idx; Decode dec; Tables tb; Groups g; Batch b;
     std::string vcf = slurp(opt.vcf_path);
     const Fasta ref = read_fasta(slurp(opt.fasta_path));
     rep.t_read = lap.lap();
@@ -1271,7 +1341,8 @@ int vcf_mode(const VcfOptions& opt)
     chk(ctx, v2p_batch_create(ctx.raw(), out_ptr(b)));
     if (opt.unique) chk(ctx, v2p_unique_create(ctx.raw(), 0, out_ptr(uq)));
     ProbandWriter writer{opt, samples, rep};
-    UniqueSink sink{ctx, uq.get(), opt, samples, ref, rr, rep};
+    if (opt.carriers) chk(ctx, v2p_carriers_create(ctx.raw(), uint32_t(samples.size()), out_ptr(kq)));
+    UniqueSink sink{ctx, uq.get(), opt, samples, ref, rr, rep, kq.get()};
     const Emit emit{ctx, opt, co, rr, b.get(), writer, sink, rep};
     std::string tasks_json = "{\"path\": \"host\"}";
     if (rep.tasks_on_device) tasks_json = run_device_tasks(emit, dec, tb);

@@ -11,6 +11,7 @@ struct VcfOptions {
     std::vector<uint32_t> peptide_ks;        // --peptides K[,K...]
     bool tryptic = false;                    // --tryptic M,MIN,MAX
     uint32_t tryptic_missed = 0, tryptic_min = 0, tryptic_max = 0;
+    bool carriers = false;                   // --carriers: {stem}.carriers.tsv beside every peptide file, and peptide_carriers_summary.tsv
 };
 
 // argv = {harness, "vcf", in.vcf, reference.fasta, outdir, flags...}; an argument that is no flag is ignored.  false: a combination that is

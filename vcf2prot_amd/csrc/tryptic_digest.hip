@@ -13,6 +13,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "block_scan.hpp"
 #include "device_scan.h"
+#include "peptide_carriers.h"
 #include "tryptic_digest.h"
 #include "unique_records.h"
 #include "v2p_ctx_internal.h"
@@ -348,6 +349,7 @@ struct v2p_tryptic {
     bool scanned = false;
     uint64_t n_peptides = 0, text_bytes = 0;
     DevMem text, text_begin, occ, first_class, first_offset;
+    CarrierRows carriers;                  // ... if it came from v2p_tryptic_scan_carriers
     Events<5> ev;
 };
 
@@ -478,20 +480,26 @@ void v2p_tryptic_destroy(v2p_tryptic* t)
     delete t;
 }
 
-int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
+}  // extern "C"
+
+namespace {
+
+// one scan; k: the carriers whose rows the peptides get as well, or null (a plain scan: no further kernel, no further allocation)
+int scan_set(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* info, v2p_carriers_info* kinfo, const std::string& who)
 {
-    if (!t || !u) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = t->ctx;
     CtxLock lk(c);
     UniqueStoreView uv;
     unique_store_view(u, &uv);
-    if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_tryptic_scan: the tryptic set and the record set belong to different contexts", -1);
-    if (uv.store_bytes >= TRY_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: a store of 2^40 bytes", -1);
+    if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, who + ": the tryptic set and the record set belong to different contexts", -1);
+    if (uv.store_bytes >= TRY_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, who + ": a store of 2^40 bytes", -1);
+    if (k) { const int rc = carriers_check(c, k, uv.n_classes, who.c_str()); if (rc != V2P_OK) return rc; }
     V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
     // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
     Starts starts;
-    DevMem novel, start_count, start_begin, list_count, list_begin, tile_bytes, tile_text, item, cls, slot_of, slots, occ, text, text_begin, out_occ, out_class, out_offset;
+    DevMem novel, start_count, start_begin, list_count, list_begin, tile_bytes, tile_text, item, cls, slot_of, slots, occ, text, text_begin, out_occ, out_class, out_offset, index_of_slot;
+    CarrierRows rows;
     TryScanArgs a{};
     a.par = t->par;
     a.text = TryText{uv.store, uv.store_bytes, uv.cls.store_begin, uv.cls.len, uv.n_classes, nullptr, nullptr, nullptr, 0};
@@ -519,7 +527,7 @@ int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
     const uint64_t n_boundaries = h_status[TRY_ST_BOUNDARIES], n_products = h_status[TRY_ST_PRODUCTS], n_novel = h_status[TRY_ST_NOVEL];
     a.n_novel = n_novel;
     const uint64_t table_slots = slots_for(n_novel), list_tiles = try_tiles(n_novel);
-    if (list_tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_tryptic_scan: 2^42 novel products", -1);
+    if (list_tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, who + ": 2^42 novel products", -1);
     V2P_TRY(item.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
     V2P_TRY(cls.alloc(some(4 * n_novel)), "hipMalloc(tryptic list)");
     V2P_TRY(slot_of.alloc(some(8 * n_novel)), "hipMalloc(tryptic list)");
@@ -559,7 +567,15 @@ int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
     const unsigned long long h_end = text_bytes;
     V2P_TRY(hipMemcpyAsync(a.out_text_begin + n_peptides, &h_end, 8, hipMemcpyHostToDevice, st), "H2D(tryptic result)");
     V2P_TRY(hipEventRecord(t->ev[4], st), "hipEventRecord");
+    if (k) {                                                 // the peptides' indices beside their slots, then the class rows ORed into the peptides'
+        V2P_TRY(index_of_slot.alloc(8 * table_slots), "hipMalloc(carriers index)");
+        V2P_TRY(carriers_begin(k, st), "hipEventRecord");
+        V2P_TRY(launch_try_index(a, index_of_slot.get<unsigned long long>(), st), "launch(tryptic index)");
+        const int rc2 = carriers_pass(c, k, a.cls, a.slot_of, n_novel, index_of_slot.get<unsigned long long>(), n_peptides, &rows, kinfo);
+        if (rc2 != V2P_OK) return rc2;
+    }
     V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (k) t->carriers = std::move(rows); else t->carriers.drop();
     t->text = std::move(text); t->text_begin = std::move(text_begin); t->occ = std::move(out_occ);
     t->first_class = std::move(out_class); t->first_offset = std::move(out_offset);
     t->n_peptides = n_peptides; t->text_bytes = text_bytes; t->scanned = true;
@@ -570,6 +586,29 @@ int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
                                  n_boundaries, n_products, n_novel, n_peptides, text_bytes, table_slots, t->ms_ref_build, ms[0], ms[1], ms[2], ms[3]};
     }
     return V2P_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2p_tryptic_scan(v2p_tryptic* t, v2p_unique* u, v2p_tryptic_info* info)
+{
+    if (!t || !u) return V2P_ERR_INVALID_ARG;
+    return scan_set(t, u, nullptr, info, nullptr, "v2p_tryptic_scan");
+}
+
+int v2p_tryptic_scan_carriers(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* info, v2p_carriers_info* kinfo)
+{
+    if (!t || !u || !k) return V2P_ERR_INVALID_ARG;
+    return scan_set(t, u, k, info, kinfo, "v2p_tryptic_scan_carriers");
+}
+
+int v2p_tryptic_download_carriers(v2p_tryptic* t, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words)
+{
+    if (!t) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(t->ctx);
+    return carriers_download(t->ctx, t->carriers, t->n_peptides, bits, n_carriers, per_proband, n, words, "v2p_tryptic_download_carriers");
 }
 
 int v2p_tryptic_count(const v2p_tryptic* t, uint64_t* n, uint64_t* text_bytes)

@@ -11,6 +11,7 @@
 #include "../../include/vcf2prot_hip.h"
 #include "block_scan.hpp"
 #include "device_scan.h"
+#include "peptide_carriers.h"
 #include "unique_records.h"
 #include "v2p_ctx_internal.h"
 #include "variant_peptides.h"
@@ -237,6 +238,7 @@ struct v2p_peptides {
     bool scanned = false;
     uint64_t n_peptides = 0;
     DevMem text, occ, first_class, first_offset;
+    CarrierRows carriers;                  // ... if it came from v2p_peptides_scan_carriers
     Events<4> ev;
 };
 
@@ -319,21 +321,27 @@ void v2p_peptides_destroy(v2p_peptides* p)
     delete p;
 }
 
-int v2p_peptides_scan(v2p_peptides* p, v2p_unique* u, v2p_peptides_info* info)
+}  // extern "C"
+
+namespace {
+
+// one scan; k: the carriers whose rows the peptides get as well, or null (a plain scan: no further kernel, no further allocation)
+int scan_set(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info* info, v2p_carriers_info* kinfo, const std::string& who)
 {
-    if (!p || !u) return V2P_ERR_INVALID_ARG;
     v2p_ctx* c = p->ctx;
     CtxLock lk(c);
     UniqueStoreView uv;
     unique_store_view(u, &uv);
-    if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, "v2p_peptides_scan: the peptide set and the record set belong to different contexts", -1);
-    if (uv.store_bytes >= PEP_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_peptides_scan: a store of 2^47 bytes", -1);
+    if (uv.ctx != c) return ctx_fail(c, V2P_ERR_INVALID_ARG, who + ": the peptide set and the record set belong to different contexts", -1);
+    if (uv.store_bytes >= PEP_MAX_BYTES) return ctx_fail(c, V2P_ERR_UNSUPPORTED, who + ": a store of 2^47 bytes", -1);
+    if (k) { const int rc = carriers_check(c, k, uv.n_classes, who.c_str()); if (rc != V2P_OK) return rc; }
     V2P_TRY(hipSetDevice(ctx_device(c)), "hipSetDevice");
     hipStream_t st = ctx_stream(c);
     const uint64_t tiles = pep_tiles(uv.store_bytes);
-    if (tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, "v2p_peptides_scan: 2^32 tiles", -1);
+    if (tiles >= 0xFFFFFFFFull) return ctx_fail(c, V2P_ERR_UNSUPPORTED, who + ": 2^32 tiles", -1);
     // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
-    DevMem flags, tile_count, tile_begin, pos, cls, slot_of, slots, occ, text, out_occ, out_class, out_offset;
+    DevMem flags, tile_count, tile_begin, pos, cls, slot_of, slots, occ, text, out_occ, out_class, out_offset, index_of_slot;
+    CarrierRows rows;
     V2P_TRY(flags.alloc(some(8 * 16 * tiles)), "hipMalloc(peptides flags)");
     V2P_TRY(tile_count.alloc(some(4 * tiles)), "hipMalloc(peptides tiles)");
     V2P_TRY(tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(peptides tiles)");
@@ -385,7 +393,15 @@ int v2p_peptides_scan(v2p_peptides* p, v2p_unique* u, v2p_peptides_info* info)
     a.out_text = text.get<uint8_t>(); a.out_occ = out_occ.get<unsigned long long>(); a.out_class = out_class.get<uint32_t>(); a.out_offset = out_offset.get<uint32_t>();
     if (n_peptides) V2P_TRY(launch_pep_emit(a, st), "launch(peptides emit)");
     V2P_TRY(hipEventRecord(p->ev[3], st), "hipEventRecord");
+    if (k) {                                                 // the peptides' indices beside their slots, then the class rows ORed into the peptides'
+        V2P_TRY(index_of_slot.alloc(8 * table_slots), "hipMalloc(carriers index)");
+        V2P_TRY(carriers_begin(k, st), "hipEventRecord");
+        V2P_TRY(launch_pep_index(a, index_of_slot.get<unsigned long long>(), st), "launch(peptides index)");
+        const int rc = carriers_pass(c, k, a.cls, a.slot_of, n_novel, index_of_slot.get<unsigned long long>(), n_peptides, &rows, kinfo);
+        if (rc != V2P_OK) return rc;
+    }
     V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (k) p->carriers = std::move(rows); else p->carriers.drop();
     p->text = std::move(text); p->occ = std::move(out_occ); p->first_class = std::move(out_class); p->first_offset = std::move(out_offset);
     p->n_peptides = n_peptides; p->scanned = true;
     if (info) {
@@ -395,6 +411,29 @@ int v2p_peptides_scan(v2p_peptides* p, v2p_unique* u, v2p_peptides_info* info)
                                   p->ms_ref_build, ms[0], ms[1], ms[2]};
     }
     return V2P_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2p_peptides_scan(v2p_peptides* p, v2p_unique* u, v2p_peptides_info* info)
+{
+    if (!p || !u) return V2P_ERR_INVALID_ARG;
+    return scan_set(p, u, nullptr, info, nullptr, "v2p_peptides_scan");
+}
+
+int v2p_peptides_scan_carriers(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info* info, v2p_carriers_info* kinfo)
+{
+    if (!p || !u || !k) return V2P_ERR_INVALID_ARG;
+    return scan_set(p, u, k, info, kinfo, "v2p_peptides_scan_carriers");
+}
+
+int v2p_peptides_download_carriers(v2p_peptides* p, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words)
+{
+    if (!p) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(p->ctx);
+    return carriers_download(p->ctx, p->carriers, p->n_peptides, bits, n_carriers, per_proband, n, words, "v2p_peptides_download_carriers");
 }
 
 int v2p_peptides_count(const v2p_peptides* p, uint64_t* n)

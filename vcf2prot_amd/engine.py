@@ -615,6 +615,53 @@ class UniqueSet(_DeviceSet):
         return out[:out_len].tobytes()
 
 
+class CarrierSet(_DeviceSet):
+    """One ``v2p_carriers``: a bitmap row of ``n_probands`` bits per class of a UniqueSet -- which probands own a record of the class -- kept
+    on the device for ``PeptideSet.scan`` / ``TrypticSet.scan`` (the rule: tests/carriers_rule.py)."""
+    _destroy = "v2p_carriers_destroy"
+
+    def __init__(self, ctx: Context, n_probands: int):
+        self.ctx, self.n_probands, self.words = ctx, n_probands, (n_probands + 63) // 64
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        self._h = None
+        ctx._check(self._lib.v2p_carriers_create(ctx._h, n_probands, ctypes.byref(h)))
+        self._h = h
+
+    def add(self, class_of, proband_of):
+        """v2p_carriers_add: record i belongs to class class_of[i] and to proband proband_of[i]."""
+        class_of, proband_of = np.ascontiguousarray(class_of, np.uint32), np.ascontiguousarray(proband_of, np.uint32)
+        if class_of.shape != proband_of.shape or class_of.ndim != 1:
+            raise ValueError("class_of and proband_of: two flat arrays of one length")
+        pad = lambda x: np.concatenate([x, np.zeros(1, x.dtype)])
+        a, b = pad(class_of), pad(proband_of)
+        self.ctx._check(self._lib.v2p_carriers_add(self._h, a.ctypes.data, b.ctypes.data, int(class_of.size)))
+
+    def n_rows(self) -> int:
+        n = ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_carriers_classes(self._h, ctypes.byref(n), None, None, 0))
+        return int(n.value)
+
+    def classes(self, n: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_carriers_classes: bits [n_rows, words] and n_carriers [n_rows] of the class rows as they are now."""
+        if n is None:
+            n = self.n_rows()
+        bits, count = np.zeros((n + 1, self.words), np.uint64), np.zeros(n + 1, np.uint32)
+        have = ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_carriers_classes(self._h, ctypes.byref(have), bits.ctypes.data, count.ctypes.data, n))
+        return {"bits": bits[:n], "n_carriers": count[:n]}
+
+
+def _carriers_info(info: "N.CarriersInfo") -> dict:
+    return {k: getattr(info, k) for k, _ in N.CarriersInfo._fields_}
+
+
+def _download_carriers(fn, s, n: int, words: int, n_probands: int) -> Dict[str, np.ndarray]:
+    bits, count, per = np.zeros((n + 1, words), np.uint64), np.zeros(n + 1, np.uint32), np.zeros(n_probands + 1, np.uint64)
+    s.ctx._check(fn(s._h, bits.ctypes.data, count.ctypes.data, per.ctypes.data, n, words))
+    return {"bits": bits[:n], "n_carriers": count[:n], "per_proband": per[:n_probands]}
+
+
 class PeptideSet(_DeviceSet):
     """One ``v2p_peptides``: the K-byte windows of a UniqueSet's classes that occur in no reference sequence, each once, filtered and
     deduplicated on the device (the rule: tests/peptides_rule.py).  ``reference``: the sequences as bytes."""
@@ -640,11 +687,23 @@ class PeptideSet(_DeviceSet):
         self._create(*_padded(blob, seq_begin, seq_len))
         return self
 
-    def scan(self, uset: "UniqueSet") -> dict:
-        """v2p_peptides_scan: every window of every class the set holds now; returns the info."""
+    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None) -> dict:
+        """v2p_peptides_scan: every window of every class the set holds now; returns the info.  With ``carriers``
+        (v2p_peptides_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry."""
         info = N.PeptidesInfo()
-        self.ctx._check(self._lib.v2p_peptides_scan(self._h, uset._h, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in N.PeptidesInfo._fields_}
+        if carriers is None:
+            self.ctx._check(self._lib.v2p_peptides_scan(self._h, uset._h, ctypes.byref(info)))
+            return {k: getattr(info, k) for k, _ in N.PeptidesInfo._fields_}
+        kinfo = N.CarriersInfo()
+        self.ctx._check(self._lib.v2p_peptides_scan_carriers(self._h, uset._h, carriers._h, ctypes.byref(info), ctypes.byref(kinfo)))
+        self._carriers = (carriers.words, carriers.n_probands)
+        return dict({k: getattr(info, k) for k, _ in N.PeptidesInfo._fields_}, carriers=_carriers_info(kinfo))
+
+    def download_carriers(self, n: Optional[int] = None, words: Optional[int] = None, n_probands: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_peptides_download_carriers: bits [n, words], n_carriers [n], per_proband [P] of the last scan with carriers."""
+        have = getattr(self, "_carriers", (1, 1))
+        return _download_carriers(self._lib.v2p_peptides_download_carriers, self, self.count() if n is None else n,
+                                  have[0] if words is None else words, have[1] if n_probands is None else n_probands)
 
     def count(self) -> int:
         n = ctypes.c_uint64()
@@ -688,11 +747,23 @@ class TrypticSet(_DeviceSet):
         self._create(*_padded(blob, seq_begin, seq_len))
         return self
 
-    def scan(self, uset: "UniqueSet") -> dict:
-        """v2p_tryptic_scan: every product of every class the set holds now; returns the info."""
+    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None) -> dict:
+        """v2p_tryptic_scan: every product of every class the set holds now; returns the info.  With ``carriers``
+        (v2p_tryptic_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry."""
         info = N.TrypticInfo()
-        self.ctx._check(self._lib.v2p_tryptic_scan(self._h, uset._h, ctypes.byref(info)))
-        return {k: getattr(info, k) for k, _ in N.TrypticInfo._fields_}
+        if carriers is None:
+            self.ctx._check(self._lib.v2p_tryptic_scan(self._h, uset._h, ctypes.byref(info)))
+            return {k: getattr(info, k) for k, _ in N.TrypticInfo._fields_}
+        kinfo = N.CarriersInfo()
+        self.ctx._check(self._lib.v2p_tryptic_scan_carriers(self._h, uset._h, carriers._h, ctypes.byref(info), ctypes.byref(kinfo)))
+        self._carriers = (carriers.words, carriers.n_probands)
+        return dict({k: getattr(info, k) for k, _ in N.TrypticInfo._fields_}, carriers=_carriers_info(kinfo))
+
+    def download_carriers(self, n: Optional[int] = None, words: Optional[int] = None, n_probands: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_tryptic_download_carriers: bits [n, words], n_carriers [n], per_proband [P] of the last scan with carriers."""
+        have = getattr(self, "_carriers", (1, 1))
+        return _download_carriers(self._lib.v2p_tryptic_download_carriers, self, self.count()[0] if n is None else n,
+                                  have[0] if words is None else words, have[1] if n_probands is None else n_probands)
 
     def count(self) -> Tuple[int, int]:
         """(peptides, bytes of their texts)"""
