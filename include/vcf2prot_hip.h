@@ -548,6 +548,34 @@ int  v2p_tryptic_scan_carriers (v2p_tryptic*,  v2p_unique* u, v2p_carriers*, v2p
 int  v2p_peptides_download_carriers(v2p_peptides*, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words);
 int  v2p_tryptic_download_carriers (v2p_tryptic*,  uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words);
 
+/* ---- sources: every class a variant peptide occurs in (vcf2prot_amd/csrc/peptide_sources.hip, device_sort.hip) ----
+ * Class c is a SOURCE of peptide x iff x occurs in c's residues -- as a K-byte window (v2p_peptides) or as a product under the set's
+ * (M, MIN, MAX) (v2p_tryptic), both exactly as above; two occurrences in one class make one source.  Per peptide, indexed as
+ * v2p_*_download delivers them: its sources source_class[source_begin[i] .. source_begin[i + 1]) in ascending class id, and beside each
+ * the smallest offset at which the peptide occurs in that class (the first source and offset are first_class / first_offset).  Per
+ * class: total, the number of peptides it is a source of, and only, the number of those whose single source it is.  Every position comes
+ * from a stable sort and scans, the counters from integer adds: nothing depends on the order in which atomics arrive, and two runs give
+ * equal bytes.  The rule in Python: tests/sources_rule.py. */
+typedef struct { uint64_t n_entries, n_pairs, n_peptides, n_classes;   /* novel occurrences sorted; (peptide, source) pairs; the peptides; the record set's classes at the scan */
+                 uint64_t max_sources;                                 /* the largest number of sources of one peptide */
+                 uint32_t sort_passes;                                 /* 8-bit digits of the peptide index the sort went through */
+                 float ms_sort, ms_group; } v2p_sources_info;          /* HIP events on the context's stream: key + sort; heads + emit + only */
+/* Everything v2p_*_scan does -- the base result is byte for byte a plain scan's -- and the source lists of its peptides; with carriers
+ * given (may be NULL) also what v2p_*_scan_carriers adds, checked as there.  V2P_ERR_UNSUPPORTED: 2^32 novel occurrences or peptides.
+ * A failed call leaves the earlier result whole; a later plain v2p_*_scan or v2p_*_scan_carriers replaces the result and drops the
+ * source lists.  Any info may be NULL. */
+int  v2p_peptides_scan_sources(v2p_peptides*, v2p_unique* u, v2p_carriers*, v2p_peptides_info*, v2p_carriers_info*, v2p_sources_info*);
+int  v2p_tryptic_scan_sources (v2p_tryptic*,  v2p_unique* u, v2p_carriers*, v2p_tryptic_info*,  v2p_carriers_info*, v2p_sources_info*);
+/* the sizes of the download's arrays; either pointer may be NULL.  V2P_ERR_STATE unless the set's CURRENT result came from a *_scan_sources call. */
+int  v2p_peptides_sources_count(const v2p_peptides*, uint64_t* n_pairs, uint64_t* n_classes);
+int  v2p_tryptic_sources_count (const v2p_tryptic*,  uint64_t* n_pairs, uint64_t* n_classes);
+/* n = the peptide count, n_pairs and n_classes what *_sources_count gives (V2P_ERR_INVALID_ARG); source_begin [n + 1], source_class /
+ * source_offset [n_pairs], per_class_total / per_class_only [n_classes]; any pointer may be NULL.  V2P_ERR_STATE as above. */
+int  v2p_peptides_download_sources(v2p_peptides*, uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset,
+                                   uint64_t* per_class_total, uint64_t* per_class_only, uint64_t n, uint64_t n_pairs, uint64_t n_classes);
+int  v2p_tryptic_download_sources (v2p_tryptic*,  uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset,
+                                   uint64_t* per_class_total, uint64_t* per_class_only, uint64_t n, uint64_t n_pairs, uint64_t n_classes);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.

@@ -1,4 +1,4 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]] [--write_tryptic M,MIN,MAX] [--write_carriers]] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]] [--write_tryptic M,MIN,MAX] [--write_carriers] [--write_sources]] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
@@ -22,7 +22,13 @@ products of a tryptic digest of those distinct proteins (cleavage after K or R u
 --write_carriers (with --write_unique and at least one of --write_peptides / --write_tryptic) adds, beside every peptide file {stem}.tsv,
 {stem}.carriers.tsv (`peptide, number of probands that carry it, their names in VCF column order`, same row order) and
 <outdir>/peptide_carriers_summary.tsv: per proband, the number of peptides of every file it carries.  A proband carries a peptide if one of
-its two haplotypes holds a protein the peptide occurs in; the proband rows are ORed together on the GPU (v2p_carriers_*)."""
+its two haplotypes holds a protein the peptide occurs in; the proband rows are ORed together on the GPU (v2p_carriers_*).
+
+--write_sources (with --write_unique and at least one of --write_peptides / --write_tryptic) adds, beside every peptide file {stem}.tsv,
+{stem}.sources.tsv (`peptide, number of distinct proteins that have it, number of transcripts among them, every such protein as
+{transcript}_v{k}:{1-based position}`, same row order) and <outdir>/peptide_sources_summary.tsv: per distinct protein, the number of
+peptides of every file it is a source of, and of those that no other protein has.  The occurrences are grouped by peptide with a stable
+radix sort on the GPU (v2p_*_scan_sources)."""
 import argparse
 import os
 import subprocess
@@ -57,6 +63,9 @@ def main() -> int:
     ap.add_argument("--write_carriers", action="store_true",
                     help="with --write_unique and --write_peptides / --write_tryptic: also write {stem}.carriers.tsv beside every peptide file (which probands carry "
                          "each peptide, ORed together on the GPU) and peptide_carriers_summary.tsv")
+    ap.add_argument("--write_sources", action="store_true",
+                    help="with --write_unique and --write_peptides / --write_tryptic: also write {stem}.sources.tsv beside every peptide file (every distinct protein "
+                         "each peptide occurs in, grouped on the GPU) and peptide_sources_summary.tsv")
     ap.add_argument("--slice-kb", type=int, default=0, help="cut the cohort into slices of about this many KiB of FASTA text (default: 256 MiB; for tests)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
@@ -76,6 +85,8 @@ def main() -> int:
             ap.error("--write_tryptic takes M,MIN,MAX: missed cleavages 0-4 and peptide lengths 1 <= MIN <= MAX <= 64")
     if a.write_carriers and not (a.write_unique and (a.write_peptides is not None or a.write_tryptic is not None)):
         ap.error("--write_carriers says which probands carry the peptides of --write_peptides / --write_tryptic: give --write_unique and at least one of the two")
+    if a.write_sources and not (a.write_unique and (a.write_peptides is not None or a.write_tryptic is not None)):
+        ap.error("--write_sources says which proteins have the peptides of --write_peptides / --write_tryptic: give --write_unique and at least one of the two")
     from .engine import Engine
     if Engine.from_str(a.engine) is not Engine.GPU:                      # engines.rs:17-29
         sys.exit("only -g gpu is implemented here; st / mt are the reference's CPU engines")
@@ -113,6 +124,8 @@ def main() -> int:
         cmd += ["--tryptic", a.write_tryptic]
     if a.write_carriers:
         cmd.append("--carriers")
+    if a.write_sources:
+        cmd.append("--sources")
     if a.slice_kb > 0:
         cmd += ["--slice-kb", str(a.slice_kb)]
     return subprocess.run(cmd).returncode

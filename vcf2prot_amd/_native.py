@@ -141,6 +141,12 @@ HIP_API = {
     "v2p_tryptic_scan_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "v2p_peptides_download_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]),
     "v2p_tryptic_download_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]),
+    "v2p_peptides_scan_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_tryptic_scan_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_peptides_sources_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_tryptic_sources_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_peptides_download_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64]),
+    "v2p_tryptic_download_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64]),
 }
 
 _hip = None
@@ -176,6 +182,12 @@ class CarriersInfo(ctypes.Structure):
     """v2p_carriers_info (include/vcf2prot_hip.h)"""
     _fields_ = [("n_probands", c_uint64), ("words", c_uint64), ("n_class_rows", c_uint64), ("n_entries", c_uint64), ("n_pairs", c_uint64),
                 ("n_peptides", c_uint64), ("ms_carry", ctypes.c_float), ("ms_count", ctypes.c_float)]
+
+
+class SourcesInfo(ctypes.Structure):
+    """v2p_sources_info (include/vcf2prot_hip.h)"""
+    _fields_ = [("n_entries", c_uint64), ("n_pairs", c_uint64), ("n_peptides", c_uint64), ("n_classes", c_uint64), ("max_sources", c_uint64),
+                ("sort_passes", ctypes.c_uint32), ("ms_sort", ctypes.c_float), ("ms_group", ctypes.c_float)]
 
 
 class TrypticInfo(ctypes.Structure):
@@ -252,6 +264,9 @@ BENCH_API = {
     "v2p_bench_set_variant": (c_int, [c_void_p, c_uint32]),
     # the front end's prefix sums on caller-owned memory (tests/test_gpu_scan.py)
     "v2p_scan_launch": (c_int, [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p]),
+    # the array sort on caller-owned memory (tests/test_gpu_sort.py)
+    "v2p_sort_launch": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, POINTER(c_int)]),
+    "v2p_sort_scratch_entries": (c_uint64, [c_uint64]),
     # the builders' prefix sums and blocked chunk order on caller-owned memory (tests/test_gpu_build_scans.py, tests/test_gpu_order_rule.py)
     "v2p_build_scan_launch": (c_int, [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64]),
     "v2p_build_scan_scratch_entries": (c_uint64, [c_int, c_uint64]),

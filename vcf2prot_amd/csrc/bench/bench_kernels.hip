@@ -6,6 +6,7 @@
 #include "../stitch_kernels.h"
 #include "../stitch_device.hpp"
 #include "../device_scan.h"
+#include "../device_sort.h"
 #include "../group_tasks.h"
 #include "../build_kernels.h"
 #include "../build_rows.h"
@@ -374,6 +375,15 @@ int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, vo
     return launch_device_scan(static_cast<const uint32_t*>(d_in), uint32_t(n), kind == 0 ? static_cast<unsigned long long*>(d_out) : nullptr,
                               kind == 1 ? static_cast<uint32_t*>(d_out) : nullptr, static_cast<unsigned long long*>(d_scratch), st) == hipSuccess ? 0 : -2;
 }
+
+int v2p_sort_launch(void* hip_stream, void* d_words, void* d_tmp, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, void* d_scratch, int* result_in)
+{
+    const hipError_t e = v2p::launch_device_sort(static_cast<uint64_t*>(d_words), static_cast<uint64_t*>(d_tmp), n, bit_lo, bit_hi, static_cast<uint64_t*>(d_scratch),
+                                                 reinterpret_cast<hipStream_t>(hip_stream), result_in);
+    return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -1 : -2;
+}
+
+uint64_t v2p_sort_scratch_entries(uint64_t n) { return v2p::device_sort_scratch_entries(n); }
 
 int v2p_build_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch, uint64_t first)
 {

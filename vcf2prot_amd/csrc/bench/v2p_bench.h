@@ -102,6 +102,12 @@ int v2p_gather_bench_launch(void* hip_stream, const uint8_t* d_src, uint64_t win
 /* the front end's prefix sums through the product's launchers on caller-owned device memory (tests/test_gpu_scan.py): kind 0 / 1 = launch_device_scan,
  * uint32_t in[n], uint64_t / uint32_t out[n + 1], scratch = the 64-bit total; 2 = launch_tasks_tile_scan, TaskCount in[n], out[n + 1], scratch[ceil(n / TASKS_SCAN_TILE) + 1] */
 int v2p_scan_launch(void* hip_stream, int kind, const void* d_in, uint64_t n, void* d_out, void* d_scratch);
+/* launch_device_sort (csrc/device_sort.h) on caller-owned device memory (tests/test_gpu_sort.py): uint64_t words[n] and tmp[n] reordered, stable, by
+ * bits [bit_lo, bit_hi) of each word; *result_in = 0 / 1: the result lies in d_words / d_tmp; scratch of v2p_sort_scratch_entries(n) uint64_t.
+ * n = 0 or an empty bit range launches nothing.  0, -1 for a bad argument (a bit range outside the word, more tiles than the scan counts), -2 for
+ * a HIP launch error */
+int v2p_sort_launch(void* hip_stream, void* d_words, void* d_tmp, uint64_t n, uint32_t bit_lo, uint32_t bit_hi, void* d_scratch, int* result_in);
+uint64_t v2p_sort_scratch_entries(uint64_t n);
 /* the builders' three-pass prefix sums on caller-owned device memory (tests/test_gpu_build_scans.py): kind 0 = launch_scan_u32, 1 = launch_scan_u32_from
  * (out[i] = first + in[0] + .. + in[i - 1]), 2 = launch_scan_u32_chained (the caller has put the running total in d_out[0]; n = 0 launches nothing),
  * 3 = launch_rows_scan_u64 (uint64_t in[n], sums modulo 2^64); kinds 0 .. 2: uint32_t in[n]; all: uint64_t out[n + 1], scratch of

@@ -283,6 +283,7 @@ bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
         o.device_int_map |= is(i, "--device-int-map");
         o.unique |= is(i, "--unique");
         o.carriers |= is(i, "--carriers");
+        o.sources |= is(i, "--sources");
     }
     const char* refusal = nullptr;
     if (o.bgzf && o.compressed) refusal = "--bgzf and -c both ask for a .fasta.gz: -c writes single-member gzip (zlib -9 on the host), --bgzf BGZF compressed on the GPU; pick one";
@@ -290,6 +291,8 @@ bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
         refusal = "usage: --unique writes unique_proteins.fasta and unique_proteins.tsv from the device's record set, no per-proband file: it cannot be combined with -c, --bgzf or --host-build";
     else if (o.carriers && (!o.unique || (!peptides_arg && !tryptic_arg)))
         refusal = "usage: --carriers writes {stem}.carriers.tsv beside every peptide file and peptide_carriers_summary.tsv: it needs --unique and at least one of --peptides and --tryptic";
+    else if (o.sources && (!o.unique || (!peptides_arg && !tryptic_arg)))
+        refusal = "usage: --sources writes {stem}.sources.tsv beside every peptide file and peptide_sources_summary.tsv: it needs --unique and at least one of --peptides and --tryptic";
     else if (peptides_arg && (!o.unique || !parse_peptide_ks(peptides_arg, o.peptide_ks)))
         refusal = "usage: --peptides K[,K...] writes variant_peptides_k{K}.tsv from the classes of --unique: it needs --unique and at most eight window lengths, each 1 .. 16";
     else if (tryptic_arg && (!o.unique || !parse_tryptic(tryptic_arg, o)))
@@ -311,7 +314,8 @@ struct Report {
     float ims[3] = {}, xms[5] = {}, kms[4] = {}, tms[7] = {}, sms[2] = {}, gms[5] = {}, jms[5] = {};
     v2p_tables_info tinf{}; v2p_stats_info sinfo{}; v2p_groups_info ginfo{}; v2p_unique_info u_sum{};
     bool tables_on_device = false, device_groups = false, tasks_on_device = false, int_map_on_device = false;
-    std::string pep_json, tryptic_json, carriers_json;
+    std::string pep_json, tryptic_json, carriers_json, sources_json;
+    uint64_t sources_classes = 0;                                    // (of the last scan with sources)
     v2p_carriers_info k_last{};                                      // (of the last scan with carriers: the set's probands, words and class rows)
 
     void print(const VcfOptions& opt, const std::string& tasks_json) const      // tasks_json says where steps 4a / 4b ran
@@ -354,6 +358,7 @@ struct Report {
         if (opt.carriers)
             std::printf(", \"carriers\": {\"probands\": %llu, \"words\": %llu, \"class_rows\": %llu, \"files\": {%s}}", (unsigned long long)k_last.n_probands,
                         (unsigned long long)k_last.words, (unsigned long long)k_last.n_class_rows, carriers_json.c_str());
+        if (opt.sources) std::printf(", \"sources\": {\"classes\": %llu, \"files\": {%s}}", (unsigned long long)sources_classes, sources_json.c_str());
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     }
 };
@@ -945,6 +950,58 @@ struct UniqueSink {
         }
         write_tsv(std::string(opt.outdir) + "/peptide_carriers_summary.tsv", tsv);
     }
+    // ---- --sources: beside a peptide file {stem}.tsv, {stem}.sources.tsv -- per peptide, in the same order, the number of classes it occurs
+    // in, the number of distinct transcripts among them, and `{class name}:{1-based position}` of every one in ascending class id -- from the
+    // lists of a scan with sources; the per-class counts become two columns of the summary ----
+    struct SourceColumn { std::string stem; std::vector<uint64_t> total, only; };
+    std::vector<SourceColumn> source_columns;
+    template <class Peptide, class Download>
+    void write_sources(const std::string& stem, uint64_t n, Peptide peptide, Download download, const v2p_sources_info& sinf, const std::vector<std::string>& class_name)
+    {
+        std::vector<uint64_t> begin(n + 2), total(sinf.n_classes + 1), only(sinf.n_classes + 1);
+        std::vector<uint32_t> cls(sinf.n_pairs + 1), off(sinf.n_pairs + 1);
+        download(begin.data(), cls.data(), off.data(), total.data(), only.data(), n, sinf.n_pairs, sinf.n_classes);
+        std::vector<uint32_t> order(n);
+        for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return peptide(a) < peptide(b); });
+        const auto transcript = [&](uint32_t c) { return std::string_view(class_name[c]).substr(0, class_name[c].rfind("_v")); };
+        std::string tsv = "#peptide\tproteins\ttranscripts\tsources\n", list;
+        std::vector<std::string_view> seen;
+        for (const uint32_t i : order) {
+            list.clear(); seen.clear();
+            for (uint64_t r = begin[i]; r < begin[i + 1]; ++r) {
+                if (r > begin[i]) list += ",";
+                list += class_name[cls[r]] + ":" + std::to_string(off[r] + 1u);
+                seen.push_back(transcript(cls[r]));
+            }
+            std::sort(seen.begin(), seen.end());
+            const size_t n_tx = size_t(std::unique(seen.begin(), seen.end()) - seen.begin());
+            tsv.append(peptide(i));
+            tsv += "\t" + std::to_string(begin[i + 1] - begin[i]) + "\t" + std::to_string(n_tx) + "\t" + list + "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/" + stem + ".sources.tsv", tsv);
+        total.resize(sinf.n_classes); only.resize(sinf.n_classes);
+        source_columns.push_back(SourceColumn{stem, std::move(total), std::move(only)});
+        char buf[400];
+        std::snprintf(buf, sizeof buf, "%s\"%s\": {\"n_entries\": %llu, \"n_peptides\": %llu, \"n_pairs\": %llu, \"max_sources\": %llu, \"sort_passes\": %u, "
+                      "\"ms_sort\": %.3f, \"ms_group\": %.3f, \"tsv_bytes\": %llu}", rep.sources_json.empty() ? "" : ", ", stem.c_str(),
+                      (unsigned long long)sinf.n_entries, (unsigned long long)sinf.n_peptides, (unsigned long long)sinf.n_pairs, (unsigned long long)sinf.max_sources,
+                      sinf.sort_passes, sinf.ms_sort, sinf.ms_group, (unsigned long long)tsv.size());
+        rep.sources_json += buf;
+        rep.sources_classes = sinf.n_classes;
+    }
+    void write_sources_summary(const std::vector<std::string>& class_name)
+    {
+        std::string tsv = "#protein";
+        for (const auto& col : source_columns) tsv += "\t" + col.stem + "\t" + col.stem + ".only";
+        tsv += "\n";
+        for (uint64_t c = 0; c < class_name.size(); ++c) {
+            tsv += class_name[c];
+            for (const auto& col : source_columns) tsv += "\t" + std::to_string(c < col.total.size() ? col.total[c] : 0) + "\t" + std::to_string(c < col.only.size() ? col.only[c] : 0);
+            tsv += "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/peptide_sources_summary.tsv", tsv);
+    }
     void write_peptides(const std::vector<std::string>& class_name)
     {
         const auto [blob, seq_begin, seq_len] = reference_blob();
@@ -953,7 +1010,9 @@ struct UniqueSink {
             chk(ctx, v2p_peptides_create(ctx.raw(), K, reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ps)));
             v2p_peptides_info inf{};
             v2p_carriers_info kinf{};
-            chk(ctx, kq ? v2p_peptides_scan_carriers(ps.get(), uq, kq, &inf, &kinf) : v2p_peptides_scan(ps.get(), uq, &inf));
+            v2p_sources_info sinf{};
+            chk(ctx, opt.sources ? v2p_peptides_scan_sources(ps.get(), uq, kq, &inf, &kinf, &sinf)
+                     : kq ? v2p_peptides_scan_carriers(ps.get(), uq, kq, &inf, &kinf) : v2p_peptides_scan(ps.get(), uq, &inf));
             const uint64_t n = inf.n_peptides;
             std::vector<uint8_t> text(n * K + 1);
             std::vector<uint64_t> occ(n + 1);
@@ -965,6 +1024,10 @@ struct UniqueSink {
             if (kq)
                 write_carriers("variant_peptides_k" + std::to_string(K), n, peptide,
                                [&](uint64_t* bits, uint32_t* count, uint64_t* per, uint64_t m, uint32_t W) { chk(ctx, v2p_peptides_download_carriers(ps.get(), bits, count, per, m, W)); }, kinf);
+            if (opt.sources)
+                write_sources("variant_peptides_k" + std::to_string(K), n, peptide,
+                              [&](uint64_t* begin, uint32_t* cls, uint32_t* off, uint64_t* total, uint64_t* only, uint64_t m, uint64_t np, uint64_t nc) {
+                                  chk(ctx, v2p_peptides_download_sources(ps.get(), begin, cls, off, total, only, m, np, nc)); }, sinf, class_name);
             char buf[640];
             std::snprintf(buf, sizeof buf, "%s\"%u\": {\"n_ref_windows\": %llu, \"n_ref_kmers\": %llu, \"ref_table_slots\": %llu, \"n_windows\": %llu, \"n_novel_windows\": %llu, "
                           "\"n_peptides\": %llu, \"table_slots\": %llu, \"tsv_bytes\": %llu, \"ms_ref_build\": %.3f, \"ms_filter\": %.3f, \"ms_insert\": %.3f, \"ms_collect\": %.3f}",
@@ -985,7 +1048,9 @@ struct UniqueSink {
                                     seq_begin.data(), seq_len.data(), ref.size(), out_ptr(ts)));
         v2p_tryptic_info inf{};
         v2p_carriers_info kinf{};
-        chk(ctx, kq ? v2p_tryptic_scan_carriers(ts.get(), uq, kq, &inf, &kinf) : v2p_tryptic_scan(ts.get(), uq, &inf));
+        v2p_sources_info sinf{};
+        chk(ctx, opt.sources ? v2p_tryptic_scan_sources(ts.get(), uq, kq, &inf, &kinf, &sinf)
+                 : kq ? v2p_tryptic_scan_carriers(ts.get(), uq, kq, &inf, &kinf) : v2p_tryptic_scan(ts.get(), uq, &inf));
         const uint64_t n = inf.n_peptides;
         std::vector<uint8_t> text(inf.text_bytes + 1);
         std::vector<uint64_t> begin(n + 2), occ(n + 1);
@@ -997,6 +1062,10 @@ struct UniqueSink {
         if (kq)
             write_carriers("tryptic_peptides", n, peptide,
                            [&](uint64_t* bits, uint32_t* count, uint64_t* per, uint64_t m, uint32_t W) { chk(ctx, v2p_tryptic_download_carriers(ts.get(), bits, count, per, m, W)); }, kinf);
+        if (opt.sources)
+            write_sources("tryptic_peptides", n, peptide,
+                          [&](uint64_t* begin, uint32_t* cls, uint32_t* off, uint64_t* total, uint64_t* only, uint64_t m, uint64_t np, uint64_t nc) {
+                              chk(ctx, v2p_tryptic_download_sources(ts.get(), begin, cls, off, total, only, m, np, nc)); }, sinf, class_name);
         char buf[800];
         std::snprintf(buf, sizeof buf, "\"missed\": %llu, \"min_len\": %llu, \"max_len\": %llu, \"n_ref_products\": %llu, \"n_ref_peptides\": %llu, \"ref_table_slots\": %llu, "
                       "\"n_boundaries\": %llu, \"n_products\": %llu, \"n_novel_products\": %llu, \"n_peptides\": %llu, \"text_bytes\": %llu, \"table_slots\": %llu, "
@@ -1066,6 +1135,7 @@ struct UniqueSink {
             if (!opt.peptide_ks.empty()) write_peptides(class_name);
             if (opt.tryptic) write_tryptic(class_name);
             if (kq) write_carriers_summary();
+            if (opt.sources) write_sources_summary(class_name);
         }
         rep.t_write_acc += sw.seconds();
     }

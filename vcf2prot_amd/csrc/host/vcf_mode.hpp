@@ -12,6 +12,7 @@ struct VcfOptions {
     bool tryptic = false;                    // --tryptic M,MIN,MAX
     uint32_t tryptic_missed = 0, tryptic_min = 0, tryptic_max = 0;
     bool carriers = false;                   // --carriers: {stem}.carriers.tsv beside every peptide file, and peptide_carriers_summary.tsv
+    bool sources = false;                    // --sources: {stem}.sources.tsv beside every peptide file, and peptide_sources_summary.tsv
 };
 
 // argv = {harness, "vcf", in.vcf, reference.fasta, outdir, flags...}; an argument that is no flag is ignored.  false: a combination that is

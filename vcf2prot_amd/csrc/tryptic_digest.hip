@@ -14,6 +14,7 @@
 #include "block_scan.hpp"
 #include "device_scan.h"
 #include "peptide_carriers.h"
+#include "peptide_sources.h"
 #include "tryptic_digest.h"
 #include "unique_records.h"
 #include "v2p_ctx_internal.h"
@@ -349,7 +350,8 @@ struct v2p_tryptic {
     bool scanned = false;
     uint64_t n_peptides = 0, text_bytes = 0;
     DevMem text, text_begin, occ, first_class, first_offset;
-    CarrierRows carriers;                  // ... if it came from v2p_tryptic_scan_carriers
+    CarrierRows carriers;                  // ... if it came from v2p_tryptic_scan_carriers, or _scan_sources with carriers
+    SourceLists sources;                   // ... if it came from v2p_tryptic_scan_sources
     Events<5> ev;
 };
 
@@ -484,8 +486,10 @@ void v2p_tryptic_destroy(v2p_tryptic* t)
 
 namespace {
 
-// one scan; k: the carriers whose rows the peptides get as well, or null (a plain scan: no further kernel, no further allocation)
-int scan_set(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* info, v2p_carriers_info* kinfo, const std::string& who)
+// one scan; k: the carriers whose rows the peptides get as well, or null; want_sources: the source lists as well (neither: a plain scan --
+// no further kernel, no further allocation)
+int scan_set(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* info, v2p_carriers_info* kinfo, const std::string& who,
+             bool want_sources = false, v2p_sources_info* sinfo = nullptr)
 {
     v2p_ctx* c = t->ctx;
     CtxLock lk(c);
@@ -500,6 +504,7 @@ int scan_set(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* i
     Starts starts;
     DevMem novel, start_count, start_begin, list_count, list_begin, tile_bytes, tile_text, item, cls, slot_of, slots, occ, text, text_begin, out_occ, out_class, out_offset, index_of_slot;
     CarrierRows rows;
+    SourceLists lists;
     TryScanArgs a{};
     a.par = t->par;
     a.text = TryText{uv.store, uv.store_bytes, uv.cls.store_begin, uv.cls.len, uv.n_classes, nullptr, nullptr, nullptr, 0};
@@ -574,8 +579,20 @@ int scan_set(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* i
         const int rc2 = carriers_pass(c, k, a.cls, a.slot_of, n_novel, index_of_slot.get<unsigned long long>(), n_peptides, &rows, kinfo);
         if (rc2 != V2P_OK) return rc2;
     }
+    if (want_sources) {                                      // the same indices; the list sorted by them, one head per (peptide, class)
+        if (!k) {
+            V2P_TRY(index_of_slot.alloc(8 * table_slots), "hipMalloc(sources index)");
+            V2P_TRY(launch_try_index(a, index_of_slot.get<unsigned long long>(), st), "launch(tryptic index)");
+        }
+        SourceArgs s{};
+        s.cls = a.cls; s.slot_of = a.slot_of; s.key = a.item; s.pos_mask = TRY_POS_MASK; s.n_novel = n_novel;
+        s.index_of_slot = index_of_slot.get<unsigned long long>(); s.store_begin = a.text.begin; s.n_classes = a.text.n_seq; s.n_peptides = n_peptides;
+        const int rc3 = sources_pass(c, s, &lists, sinfo, who.c_str());
+        if (rc3 != V2P_OK) return rc3;
+    }
     V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (k) t->carriers = std::move(rows); else t->carriers.drop();
+    if (want_sources) t->sources = std::move(lists); else t->sources.drop();
     t->text = std::move(text); t->text_begin = std::move(text_begin); t->occ = std::move(out_occ);
     t->first_class = std::move(out_class); t->first_offset = std::move(out_offset);
     t->n_peptides = n_peptides; t->text_bytes = text_bytes; t->scanned = true;
@@ -602,6 +619,28 @@ int v2p_tryptic_scan_carriers(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2
 {
     if (!t || !u || !k) return V2P_ERR_INVALID_ARG;
     return scan_set(t, u, k, info, kinfo, "v2p_tryptic_scan_carriers");
+}
+
+int v2p_tryptic_scan_sources(v2p_tryptic* t, v2p_unique* u, v2p_carriers* k, v2p_tryptic_info* info, v2p_carriers_info* kinfo, v2p_sources_info* sinfo)
+{
+    if (!t || !u) return V2P_ERR_INVALID_ARG;
+    return scan_set(t, u, k, info, kinfo, "v2p_tryptic_scan_sources", true, sinfo);
+}
+
+int v2p_tryptic_sources_count(const v2p_tryptic* t, uint64_t* n_pairs, uint64_t* n_classes)
+{
+    if (!t) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(t->ctx);
+    return sources_count(t->ctx, t->sources, n_pairs, n_classes, "v2p_tryptic_sources_count");
+}
+
+int v2p_tryptic_download_sources(v2p_tryptic* t, uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset,
+                                 uint64_t* per_class_total, uint64_t* per_class_only, uint64_t n, uint64_t n_pairs, uint64_t n_classes)
+{
+    if (!t) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(t->ctx);
+    return sources_download(t->ctx, t->sources, source_begin, source_class, source_offset, per_class_total, per_class_only, n, n_pairs, n_classes,
+                            "v2p_tryptic_download_sources");
 }
 
 int v2p_tryptic_download_carriers(v2p_tryptic* t, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words)

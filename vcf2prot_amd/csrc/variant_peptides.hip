@@ -12,6 +12,7 @@
 #include "block_scan.hpp"
 #include "device_scan.h"
 #include "peptide_carriers.h"
+#include "peptide_sources.h"
 #include "unique_records.h"
 #include "v2p_ctx_internal.h"
 #include "variant_peptides.h"
@@ -238,7 +239,8 @@ struct v2p_peptides {
     bool scanned = false;
     uint64_t n_peptides = 0;
     DevMem text, occ, first_class, first_offset;
-    CarrierRows carriers;                  // ... if it came from v2p_peptides_scan_carriers
+    CarrierRows carriers;                  // ... if it came from v2p_peptides_scan_carriers, or _scan_sources with carriers
+    SourceLists sources;                   // ... if it came from v2p_peptides_scan_sources
     Events<4> ev;
 };
 
@@ -325,8 +327,10 @@ void v2p_peptides_destroy(v2p_peptides* p)
 
 namespace {
 
-// one scan; k: the carriers whose rows the peptides get as well, or null (a plain scan: no further kernel, no further allocation)
-int scan_set(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info* info, v2p_carriers_info* kinfo, const std::string& who)
+// one scan; k: the carriers whose rows the peptides get as well, or null; want_sources: the source lists as well (neither: a plain scan --
+// no further kernel, no further allocation)
+int scan_set(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info* info, v2p_carriers_info* kinfo, const std::string& who,
+             bool want_sources = false, v2p_sources_info* sinfo = nullptr)
 {
     v2p_ctx* c = p->ctx;
     CtxLock lk(c);
@@ -342,6 +346,7 @@ int scan_set(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info*
     // everything a scan makes lives in locals until it has succeeded: a failed scan leaves the earlier result
     DevMem flags, tile_count, tile_begin, pos, cls, slot_of, slots, occ, text, out_occ, out_class, out_offset, index_of_slot;
     CarrierRows rows;
+    SourceLists lists;
     V2P_TRY(flags.alloc(some(8 * 16 * tiles)), "hipMalloc(peptides flags)");
     V2P_TRY(tile_count.alloc(some(4 * tiles)), "hipMalloc(peptides tiles)");
     V2P_TRY(tile_begin.alloc(8 * (tiles + 1)), "hipMalloc(peptides tiles)");
@@ -400,8 +405,20 @@ int scan_set(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info*
         const int rc = carriers_pass(c, k, a.cls, a.slot_of, n_novel, index_of_slot.get<unsigned long long>(), n_peptides, &rows, kinfo);
         if (rc != V2P_OK) return rc;
     }
+    if (want_sources) {                                      // the same indices; the list sorted by them, one head per (peptide, class)
+        if (!k) {
+            V2P_TRY(index_of_slot.alloc(8 * table_slots), "hipMalloc(sources index)");
+            V2P_TRY(launch_pep_index(a, index_of_slot.get<unsigned long long>(), st), "launch(peptides index)");
+        }
+        SourceArgs s{};
+        s.cls = a.cls; s.slot_of = a.slot_of; s.key = a.pos; s.pos_mask = PEP_POS_MASK; s.n_novel = n_novel;
+        s.index_of_slot = index_of_slot.get<unsigned long long>(); s.store_begin = a.store_begin; s.n_classes = a.n_classes; s.n_peptides = n_peptides;
+        const int rc = sources_pass(c, s, &lists, sinfo, who.c_str());
+        if (rc != V2P_OK) return rc;
+    }
     V2P_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (k) p->carriers = std::move(rows); else p->carriers.drop();
+    if (want_sources) p->sources = std::move(lists); else p->sources.drop();
     p->text = std::move(text); p->occ = std::move(out_occ); p->first_class = std::move(out_class); p->first_offset = std::move(out_offset);
     p->n_peptides = n_peptides; p->scanned = true;
     if (info) {
@@ -427,6 +444,28 @@ int v2p_peptides_scan_carriers(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, 
 {
     if (!p || !u || !k) return V2P_ERR_INVALID_ARG;
     return scan_set(p, u, k, info, kinfo, "v2p_peptides_scan_carriers");
+}
+
+int v2p_peptides_scan_sources(v2p_peptides* p, v2p_unique* u, v2p_carriers* k, v2p_peptides_info* info, v2p_carriers_info* kinfo, v2p_sources_info* sinfo)
+{
+    if (!p || !u) return V2P_ERR_INVALID_ARG;
+    return scan_set(p, u, k, info, kinfo, "v2p_peptides_scan_sources", true, sinfo);
+}
+
+int v2p_peptides_sources_count(const v2p_peptides* p, uint64_t* n_pairs, uint64_t* n_classes)
+{
+    if (!p) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(p->ctx);
+    return sources_count(p->ctx, p->sources, n_pairs, n_classes, "v2p_peptides_sources_count");
+}
+
+int v2p_peptides_download_sources(v2p_peptides* p, uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset,
+                                  uint64_t* per_class_total, uint64_t* per_class_only, uint64_t n, uint64_t n_pairs, uint64_t n_classes)
+{
+    if (!p) return V2P_ERR_INVALID_ARG;
+    CtxLock lk(p->ctx);
+    return sources_download(p->ctx, p->sources, source_begin, source_class, source_offset, per_class_total, per_class_only, n, n_pairs, n_classes,
+                            "v2p_peptides_download_sources");
 }
 
 int v2p_peptides_download_carriers(v2p_peptides* p, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n, uint32_t words)

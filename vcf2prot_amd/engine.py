@@ -662,6 +662,29 @@ def _download_carriers(fn, s, n: int, words: int, n_probands: int) -> Dict[str, 
     return {"bits": bits[:n], "n_carriers": count[:n], "per_proband": per[:n_probands]}
 
 
+def _scan_more(s, fn, info, uset, carriers, fields) -> dict:
+    """v2p_*_scan_sources: the base info plus a ``"sources"`` entry, and a ``"carriers"`` entry if carriers were given"""
+    kinfo, sinfo = N.CarriersInfo(), N.SourcesInfo()
+    s.ctx._check(fn(s._h, uset._h, carriers._h if carriers is not None else None, ctypes.byref(info), ctypes.byref(kinfo), ctypes.byref(sinfo)))
+    out = dict({k: getattr(info, k) for k, _ in fields}, sources={k: getattr(sinfo, k) for k, _ in N.SourcesInfo._fields_})
+    if carriers is not None:
+        s._carriers = (carriers.words, carriers.n_probands)
+        out["carriers"] = _carriers_info(kinfo)
+    return out
+
+
+def _download_sources(count_fn, fn, s, n: int, n_pairs: Optional[int], n_classes: Optional[int]) -> Dict[str, np.ndarray]:
+    if n_pairs is None or n_classes is None:
+        have_pairs, have_classes = ctypes.c_uint64(), ctypes.c_uint64()
+        s.ctx._check(count_fn(s._h, ctypes.byref(have_pairs), ctypes.byref(have_classes)))
+        n_pairs = int(have_pairs.value) if n_pairs is None else n_pairs
+        n_classes = int(have_classes.value) if n_classes is None else n_classes
+    begin, cls, off = np.zeros(n + 2, np.uint64), np.zeros(n_pairs + 1, np.uint32), np.zeros(n_pairs + 1, np.uint32)
+    total, only = np.zeros(n_classes + 1, np.uint64), np.zeros(n_classes + 1, np.uint64)
+    s.ctx._check(fn(s._h, begin.ctypes.data, cls.ctypes.data, off.ctypes.data, total.ctypes.data, only.ctypes.data, n, n_pairs, n_classes))
+    return {"source_begin": begin[:n + 1], "source_class": cls[:n_pairs], "source_offset": off[:n_pairs], "total": total[:n_classes], "only": only[:n_classes]}
+
+
 class PeptideSet(_DeviceSet):
     """One ``v2p_peptides``: the K-byte windows of a UniqueSet's classes that occur in no reference sequence, each once, filtered and
     deduplicated on the device (the rule: tests/peptides_rule.py).  ``reference``: the sequences as bytes."""
@@ -687,10 +710,13 @@ class PeptideSet(_DeviceSet):
         self._create(*_padded(blob, seq_begin, seq_len))
         return self
 
-    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None) -> dict:
+    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None, sources: bool = False) -> dict:
         """v2p_peptides_scan: every window of every class the set holds now; returns the info.  With ``carriers``
-        (v2p_peptides_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry."""
+        (v2p_peptides_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry; with ``sources``
+        (v2p_peptides_scan_sources) they get their source lists, and the info a ``"sources"`` entry."""
         info = N.PeptidesInfo()
+        if sources:
+            return _scan_more(self, self._lib.v2p_peptides_scan_sources, info, uset, carriers, N.PeptidesInfo._fields_)
         if carriers is None:
             self.ctx._check(self._lib.v2p_peptides_scan(self._h, uset._h, ctypes.byref(info)))
             return {k: getattr(info, k) for k, _ in N.PeptidesInfo._fields_}
@@ -704,6 +730,12 @@ class PeptideSet(_DeviceSet):
         have = getattr(self, "_carriers", (1, 1))
         return _download_carriers(self._lib.v2p_peptides_download_carriers, self, self.count() if n is None else n,
                                   have[0] if words is None else words, have[1] if n_probands is None else n_probands)
+
+    def sources(self, n: Optional[int] = None, n_pairs: Optional[int] = None, n_classes: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_peptides_download_sources: source_begin [n + 1], source_class / source_offset [n_pairs], total / only [n_classes] of the
+        last scan with sources (the rule: tests/sources_rule.py)."""
+        return _download_sources(self._lib.v2p_peptides_sources_count, self._lib.v2p_peptides_download_sources, self,
+                                 self.count() if n is None else n, n_pairs, n_classes)
 
     def count(self) -> int:
         n = ctypes.c_uint64()
@@ -747,10 +779,13 @@ class TrypticSet(_DeviceSet):
         self._create(*_padded(blob, seq_begin, seq_len))
         return self
 
-    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None) -> dict:
+    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None, sources: bool = False) -> dict:
         """v2p_tryptic_scan: every product of every class the set holds now; returns the info.  With ``carriers``
-        (v2p_tryptic_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry."""
+        (v2p_tryptic_scan_carriers) the peptides get carrier rows as well, and the info a ``"carriers"`` entry; with ``sources``
+        (v2p_tryptic_scan_sources) they get their source lists, and the info a ``"sources"`` entry."""
         info = N.TrypticInfo()
+        if sources:
+            return _scan_more(self, self._lib.v2p_tryptic_scan_sources, info, uset, carriers, N.TrypticInfo._fields_)
         if carriers is None:
             self.ctx._check(self._lib.v2p_tryptic_scan(self._h, uset._h, ctypes.byref(info)))
             return {k: getattr(info, k) for k, _ in N.TrypticInfo._fields_}
@@ -764,6 +799,12 @@ class TrypticSet(_DeviceSet):
         have = getattr(self, "_carriers", (1, 1))
         return _download_carriers(self._lib.v2p_tryptic_download_carriers, self, self.count()[0] if n is None else n,
                                   have[0] if words is None else words, have[1] if n_probands is None else n_probands)
+
+    def sources(self, n: Optional[int] = None, n_pairs: Optional[int] = None, n_classes: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_tryptic_download_sources: source_begin [n + 1], source_class / source_offset [n_pairs], total / only [n_classes] of the
+        last scan with sources (the rule: tests/sources_rule.py)."""
+        return _download_sources(self._lib.v2p_tryptic_sources_count, self._lib.v2p_tryptic_download_sources, self,
+                                 self.count()[0] if n is None else n, n_pairs, n_classes)
 
     def count(self) -> Tuple[int, int]:
         """(peptides, bytes of their texts)"""
