@@ -576,6 +576,52 @@ int  v2p_peptides_download_sources(v2p_peptides*, uint64_t* source_begin, uint32
 int  v2p_tryptic_download_sources (v2p_tryptic*,  uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset,
                                    uint64_t* per_class_total, uint64_t* per_class_only, uint64_t n, uint64_t n_pairs, uint64_t n_classes);
 
+/* ---- find: a given list of peptides looked up in the record set and in the reference (vcf2prot_amd/csrc/peptide_find.hip) ----
+ * A QUERY is a text of 1 .. 64 bytes; a list holds n_q of them (0 is legal), in any order, and equal queries get equal answers.  Bytes are
+ * bytes.  Query q OCCURS in a sequence s at offset i iff s[i, i + len(q)) == q and i + len(q) <= len(s): every offset counts (AAAA occurs
+ * twice in AAAAA), and an occurrence never spans two classes, two reference sequences or the store's line feed.  Per query against the
+ * record set as it is at the scan: occ, the sum of count[c] over every (class c, offset) at which it occurs; its SOURCES, the classes it
+ * occurs in, in ascending id, each with the smallest offset in that class; its carrier row, the OR of the proband rows of its sources (a
+ * class with no row has no carriers).  Per query against the reference given at create: ref_occ, the number of (sequence, offset)
+ * occurrences (a sequence passed twice counts twice), and first_ref, the smallest (sequence index, offset), (2^32 - 1, 2^32 - 1) if there
+ * is none.  Per class: total, the number of queries it is a source of; per proband: the number of queries it carries.  Every position
+ * comes from a stable sort and scans, the counters from integer adds, minima and ORs: nothing depends on the order in which atomics
+ * arrive, and two runs give equal bytes.  The rule in Python: tests/find_rule.py. */
+typedef struct v2p_find v2p_find;
+typedef struct { uint64_t n_queries, n_anchors, anchor_len,            /* the index: queries, distinct anchors, A = min(8, the shortest query) (8 with no query) */
+                 filter_bits, filter_bits_set, table_slots,            /* bits of the first test and how many are set; slots of the anchor table */
+                 n_positions, n_filter_pass, n_table_hits,             /* the scan: store positions with A bytes left in their class; those whose bit is set; those whose anchor is a query's */
+                 n_occurrences, n_pairs, n_classes, max_sources,       /* (query, class, offset) occurrences; (query, source) pairs; the record set's classes at the scan; the largest number of sources of one query */
+                 ref_positions, ref_filter_pass, ref_table_hits, ref_occurrences;   /* the same counters of the create's pass over the reference */
+                 float ms_ref, ms_match, ms_group, ms_carry; } v2p_find_info;   /* HIP events on the context's stream: the create's upload + match; count + scan + emit (with one look);
+                                                                                  * sort + heads + emit + per-query scan (with one look); row ORs + popcounts (0 without carriers) */
+/* text: HOST bytes; query q = text[q_begin[q], + q_len[q]); ref and its sequences as for v2p_tryptic_create (the device gets a copy in which
+ * they lie back to back).  Builds the index -- queries ordered by ANCHOR (their first A bytes), a slot table from anchor to the queries
+ * that share it, a bit array over a hash of the anchor -- and matches the list against the reference once.  hash_mask is ANDed onto the
+ * 64-bit hash of an anchor, from which the filter bit and the probe's start are taken (a slot holds the anchor itself, so there is no
+ * tag): pass ~0; tests pass small masks so that every anchor shares both and only the comparison of bytes keeps them apart.
+ * V2P_ERR_INVALID_ARG with the index: a query of length 0 or above 64 or whose range leaves text; a sequence whose range leaves ref.
+ * V2P_ERR_UNSUPPORTED: n_q >= 2^32; 2^32 - 1 sequences; sequences of 2^40 bytes in all. */
+int  v2p_find_create(v2p_ctx*, const uint8_t* text, const uint64_t* q_begin, const uint32_t* q_len, uint64_t n_q, uint64_t hash_mask,
+                     const uint8_t* ref, uint64_t ref_bytes, const uint64_t* seq_begin, const uint32_t* seq_len, uint64_t n_seq, v2p_find** out);
+void v2p_find_destroy(v2p_find*);
+/* every query against every class u holds NOW; replaces the result of an earlier scan.  carriers may be NULL: then the result has no
+ * carrier rows.  An empty set and n_q == 0 are legal.  V2P_ERR_INVALID_ARG: u or the carriers belong to another context; the carriers
+ * hold a row for a class id >= u's current number of classes.  V2P_ERR_UNSUPPORTED: 2^32 occurrences.  A failed scan leaves the earlier
+ * result whole.  info may be NULL. */
+int  v2p_find_scan(v2p_find*, v2p_unique* u, v2p_carriers* carriers, v2p_find_info* info);
+/* the sizes of the download's arrays; either pointer may be NULL.  V2P_ERR_STATE before the first scan. */
+int  v2p_find_count(const v2p_find*, uint64_t* n_pairs, uint64_t* n_classes);
+/* n_q the list's length, n_pairs and n_classes what v2p_find_count gives (V2P_ERR_INVALID_ARG); occ / ref_occ / first_ref_seq /
+ * first_ref_offset [n_q], source_begin [n_q + 1], source_class / source_offset [n_pairs], per_class_total [n_classes]; any pointer may be
+ * NULL.  V2P_ERR_STATE before the first scan. */
+int  v2p_find_download(v2p_find*, uint64_t* occ, uint64_t* ref_occ, uint32_t* first_ref_seq, uint32_t* first_ref_offset,
+                       uint64_t* source_begin, uint32_t* source_class, uint32_t* source_offset, uint64_t* per_class_total,
+                       uint64_t n_q, uint64_t n_pairs, uint64_t n_classes);
+/* n_q the list's length, words = W of the carriers the scan used (V2P_ERR_INVALID_ARG); bits [n_q * W], n_carriers [n_q], per_proband [P];
+ * any pointer may be NULL.  V2P_ERR_STATE before the first scan, and when the current result came from a scan without carriers. */
+int  v2p_find_download_carriers(v2p_find*, uint64_t* bits, uint32_t* n_carriers, uint64_t* per_proband, uint64_t n_q, uint32_t words);
+
 /* ---- streamed pipeline: results that must return to the host ------------------------------ */
 /* n_slots submissions are in flight at once: while slice k's results travel D2H, slice k+1 executes and slice k+2 travels H2D (pinned
  * staging on both sides).  Tickets are slot numbers and are reused round-robin; a slot must be released before it is submitted to again.

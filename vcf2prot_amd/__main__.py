@@ -1,4 +1,4 @@
-"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]] [--write_tryptic M,MIN,MAX] [--write_carriers] [--write_sources]] [--no-test]`: the reference's command line
+"""`python -m vcf2prot_amd -f in.vcf -r reference.fasta -o outdir [-g gpu] [-a] [-s] [-i [--device-int-map]] [--host-groups] [--device-tasks] [--device-tables] [--device-index] [--write_unique [--write_peptides K[,K...]] [--write_tryptic M,MIN,MAX] [--write_carriers] [--write_sources] [--find_peptides FILE]] [--no-test]`: the reference's command line
 (parts/cli.rs:70-140: -f/--vcf_file, -r/--fasta_ref, -o/--output_path, -g/--engine, -a/--write_all_proteins, -c/--write_compressed, -s/--stats, -i/--write_int_map) on top of
 `v2p_harness vcf`, i.e. the whole program without Rust.  --write_bgzf (long option only, not the reference's) writes <proband>.fasta.gz as BGZF
 compressed on the GPU, with bgzip's <proband>.fasta.gz.gzi beside it; -c keeps the reference's single-member gzip.  Only the gpu engine exists here: `-g st|mt` is the reference's own
@@ -28,7 +28,16 @@ its two haplotypes holds a protein the peptide occurs in; the proband rows are O
 {stem}.sources.tsv (`peptide, number of distinct proteins that have it, number of transcripts among them, every such protein as
 {transcript}_v{k}:{1-based position}`, same row order) and <outdir>/peptide_sources_summary.tsv: per distinct protein, the number of
 peptides of every file it is a source of, and of those that no other protein has.  The occurrences are grouped by peptide with a stable
-radix sort on the GPU (v2p_*_scan_sources)."""
+radix sort on the GPU (v2p_*_scan_sources).
+
+--find_peptides FILE (with --write_unique) looks a list of peptides up in the distinct proteins and in the -r proteome: one query of 1 to 64
+bytes per line of FILE, a trailing \\r dropped, empty lines and lines that begin with # skipped, only the text in front of the first tab
+counted -- so tryptic_peptides.tsv or variant_peptides_k9.tsv of an earlier run can be fed straight back in.  It writes, behind the other
+peptide files and one line per query in the file's order, <outdir>/found_peptides.tsv (`peptide, occurrences, proteins, transcripts,
+carriers, reference_occurrences, first_reference as {name}:{1-based position}, sources as {transcript}_v{k}:{1-based position}`; not
+found: zeros and empty fields) and <outdir>/found_peptides.carriers.tsv (`peptide, carriers, their names in VCF column order`).  Every
+query is matched as bytes at every position, on the GPU (v2p_find_*); the option keeps proband rows whether or not --write_carriers is
+given."""
 import argparse
 import os
 import subprocess
@@ -66,6 +75,9 @@ def main() -> int:
     ap.add_argument("--write_sources", action="store_true",
                     help="with --write_unique and --write_peptides / --write_tryptic: also write {stem}.sources.tsv beside every peptide file (every distinct protein "
                          "each peptide occurs in, grouped on the GPU) and peptide_sources_summary.tsv")
+    ap.add_argument("--find_peptides", metavar="FILE", default=None,
+                    help="with --write_unique: look the peptides of FILE (one per line, 1-64 bytes, the text in front of the first tab) up in the distinct proteins "
+                         "and in the -r proteome on the GPU; writes found_peptides.tsv and found_peptides.carriers.tsv")
     ap.add_argument("--slice-kb", type=int, default=0, help="cut the cohort into slices of about this many KiB of FASTA text (default: 256 MiB; for tests)")
     ap.add_argument("--no-test", action="store_true", help="like exporting NO_TEST=1 (cli.rs:275-335): no INSPECT_* checks")
     a = ap.parse_args()
@@ -87,6 +99,17 @@ def main() -> int:
         ap.error("--write_carriers says which probands carry the peptides of --write_peptides / --write_tryptic: give --write_unique and at least one of the two")
     if a.write_sources and not (a.write_unique and (a.write_peptides is not None or a.write_tryptic is not None)):
         ap.error("--write_sources says which proteins have the peptides of --write_peptides / --write_tryptic: give --write_unique and at least one of the two")
+    if a.find_peptides is not None:
+        if not a.write_unique:
+            ap.error("--find_peptides looks its peptides up in the distinct proteins of --write_unique: give --write_unique too")
+        try:
+            data = open(a.find_peptides, "rb").read()
+        except OSError as e:
+            ap.error("--find_peptides cannot read %s: %s" % (a.find_peptides, e.strerror))
+        for number, line in enumerate(data.split(b"\n"), 1):
+            line = line[:-1] if line.endswith(b"\r") else line
+            if line and not line.startswith(b"#") and len(line.split(b"\t")[0]) > 64:
+                ap.error("--find_peptides takes queries of 1-64 bytes: line %d of %s holds one of %d" % (number, a.find_peptides, len(line.split(b"\t")[0])))
     from .engine import Engine
     if Engine.from_str(a.engine) is not Engine.GPU:                      # engines.rs:17-29
         sys.exit("only -g gpu is implemented here; st / mt are the reference's CPU engines")
@@ -126,6 +149,8 @@ def main() -> int:
         cmd.append("--carriers")
     if a.write_sources:
         cmd.append("--sources")
+    if a.find_peptides is not None:
+        cmd += ["--find", a.find_peptides]
     if a.slice_kb > 0:
         cmd += ["--slice-kb", str(a.slice_kb)]
     return subprocess.run(cmd).returncode

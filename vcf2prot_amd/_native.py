@@ -147,6 +147,12 @@ HIP_API = {
     "v2p_tryptic_sources_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "v2p_peptides_download_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64]),
     "v2p_tryptic_download_sources": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64]),
+    "v2p_find_create": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "v2p_find_destroy": (None, [c_void_p]),
+    "v2p_find_scan": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "v2p_find_count": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "v2p_find_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64]),
+    "v2p_find_download_carriers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]),
 }
 
 _hip = None
@@ -188,6 +194,13 @@ class SourcesInfo(ctypes.Structure):
     """v2p_sources_info (include/vcf2prot_hip.h)"""
     _fields_ = [("n_entries", c_uint64), ("n_pairs", c_uint64), ("n_peptides", c_uint64), ("n_classes", c_uint64), ("max_sources", c_uint64),
                 ("sort_passes", ctypes.c_uint32), ("ms_sort", ctypes.c_float), ("ms_group", ctypes.c_float)]
+
+
+class FindInfo(ctypes.Structure):
+    """v2p_find_info (include/vcf2prot_hip.h)"""
+    _fields_ = [(k, c_uint64) for k in ("n_queries", "n_anchors", "anchor_len", "filter_bits", "filter_bits_set", "table_slots", "n_positions", "n_filter_pass",
+                                        "n_table_hits", "n_occurrences", "n_pairs", "n_classes", "max_sources", "ref_positions", "ref_filter_pass",
+                                        "ref_table_hits", "ref_occurrences")] + [(k, ctypes.c_float) for k in ("ms_ref", "ms_match", "ms_group", "ms_carry")]
 
 
 class TrypticInfo(ctypes.Structure):

@@ -22,8 +22,8 @@ ARCH = "gfx950"
 HIP_LIB = os.path.join(LIBDIR, "libvcf2prot_hip.so")
 COHORT_LIB = os.path.join(LIBDIR, "libv2p_cohort.so")
 
-HIP_SOURCES = ["stitch_kernels.hip", "stitch_wave.hip", "build_kernels.hip", "build_rows.hip", "dense_pieces.hip", "v2p_api.hip", "decode_kernels.hip", "v2p_decode_api.hip", "bgzf_kernels.hip", "bgzf_inflate.hip", "group_stats.hip", "group_csr.hip", "group_tasks.hip", "csq_tables.hip", "device_scan.hip", "device_sort.hip", "record_index.hip", "intmap_json.hip", "unique_records.hip", "variant_peptides.hip", "tryptic_digest.hip", "peptide_carriers.hip", "peptide_sources.hip"]
-HIP_DEPS = HIP_SOURCES + ["bgzf_format.hpp", "inflate_format.hpp", "bgzf_kernels.h", "rows_image.hpp", "build_rows.h", "patch_image.h", "dense_pieces.h", "patch_format.hpp", "stitch_kernels.h", "stitch_device.hpp", "build_kernels.h", "decode_kernels.h", "group_stats.h", "group_csr.h", "group_tasks.h", "csq_tables.h", "device_scan.h", "device_sort.h", "block_scan.hpp", "csq_sup_names.h", "record_index.h", "intmap_json.h", "unique_records.h", "variant_peptides.h", "tryptic_digest.h", "peptide_carriers.h", "peptide_sources.h", "set_table.hpp", os.path.join("host", "frontend_common.hpp"), os.path.join("host", "intmap_format.hpp"), "v2p_ctx_internal.h", "sir_pack.hpp", "pipe_slots.hpp",
+HIP_SOURCES = ["stitch_kernels.hip", "stitch_wave.hip", "build_kernels.hip", "build_rows.hip", "dense_pieces.hip", "v2p_api.hip", "decode_kernels.hip", "v2p_decode_api.hip", "bgzf_kernels.hip", "bgzf_inflate.hip", "group_stats.hip", "group_csr.hip", "group_tasks.hip", "csq_tables.hip", "device_scan.hip", "device_sort.hip", "record_index.hip", "intmap_json.hip", "unique_records.hip", "variant_peptides.hip", "tryptic_digest.hip", "peptide_carriers.hip", "peptide_sources.hip", "peptide_find.hip"]
+HIP_DEPS = HIP_SOURCES + ["bgzf_format.hpp", "inflate_format.hpp", "bgzf_kernels.h", "rows_image.hpp", "build_rows.h", "patch_image.h", "dense_pieces.h", "patch_format.hpp", "stitch_kernels.h", "stitch_device.hpp", "build_kernels.h", "decode_kernels.h", "group_stats.h", "group_csr.h", "group_tasks.h", "csq_tables.h", "device_scan.h", "device_sort.h", "block_scan.hpp", "csq_sup_names.h", "record_index.h", "intmap_json.h", "unique_records.h", "variant_peptides.h", "tryptic_digest.h", "peptide_carriers.h", "peptide_sources.h", "peptide_find.h", "set_table.hpp", os.path.join("host", "frontend_common.hpp"), os.path.join("host", "intmap_format.hpp"), "v2p_ctx_internal.h", "sir_pack.hpp", "pipe_slots.hpp",
                           os.path.join(ROOT, "include", "vcf2prot_hip.h"), os.path.join(ROOT, "include", "v2p_frontend.h")]
 COHORT_SOURCES = ["cohort_gen.cpp", os.path.join("host", "transcript_tasks.cpp"), os.path.join("host", "vcf_index.cpp"),
                   os.path.join("host", "group_muts.cpp"), os.path.join("host", "instructions.cpp"), os.path.join("host", "bgzf_host.cpp")]

@@ -7,7 +7,7 @@
 //   v2p_harness kat                          reference known-answer tests through the mirror
 //   v2p_harness run <preset> <haps> <threads>   e.g. run C2 64 8
 //   v2p_harness vcf <in.vcf> <reference.fasta> <outdir> [--no-test] [-a] [-c | --bgzf] [-s] [-i [--device-int-map]] [--host-groups] [--host-build] [--device-tasks]
-//                   [--device-tables] [--device-index] [--unique [--peptides K[,K...]] [--tryptic M,MIN,MAX]] [--slice-kb K]
+//                   [--device-tables] [--device-index] [--unique [--peptides K[,K...]] [--tryptic M,MIN,MAX] [--carriers] [--sources] [--find FILE]] [--slice-kb K]
 //                                            VCF -> one FASTA(.gz) per proband, no Rust anywhere: the product's command line.  The mode, its
 //                                            options and its stages are vcf_mode.hpp / vcf_mode.cpp; this file only hands argv over
 //   v2p_harness sharded <preset> <samples> --devices N [--oversubscribe] [--threads T] [--streamed [--slice-mb M]]

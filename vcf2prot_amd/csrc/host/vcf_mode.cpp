@@ -18,6 +18,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <iterator>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -54,6 +55,7 @@ using Unique = Owned<v2p_unique, v2p_unique_destroy>;
 using Peptides = Owned<v2p_peptides, v2p_peptides_destroy>;
 using Tryptic = Owned<v2p_tryptic, v2p_tryptic_destroy>;
 using Carriers = Owned<v2p_carriers, v2p_carriers_destroy>;
+using Find = Owned<v2p_find, v2p_find_destroy>;
 using Stream = Owned<v2p_stream, v2p_stream_destroy>;
 
 // the end of a run that cannot go on: the line is thrown, main() prints it and exits with 101
@@ -260,15 +262,44 @@ static bool parse_tryptic(const char* s, VcfOptions& o)
     return v[0] <= 4 && v[1] >= 1 && v[1] <= v[2] && v[2] <= 64;
 }
 
+// --find FILE: one query per line -- a trailing \r is dropped, empty lines and lines that begin with # are skipped, only the text in front of
+// the first tab counts (so a peptide file of an earlier run can be fed back in); false with the refusal in *why
+static bool read_find_queries(const char* path, std::vector<std::string>& queries, std::string* why)
+{
+    const std::string usage = "usage: --find FILE looks the peptides of FILE (one per line, 1 .. 64 bytes, the text in front of the first tab) up in the classes of --unique and "
+                              "writes found_peptides.tsv and found_peptides.carriers.tsv: ";
+    struct stat info;
+    std::ifstream f(path, std::ios::binary);
+    if (stat(path, &info) != 0 || S_ISDIR(info.st_mode) || !f) { *why = usage + "cannot read " + path; return false; }
+    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    if (f.bad()) { *why = usage + "cannot read " + path; return false; }
+    uint64_t number = 0;
+    for (size_t pos = 0; pos < text.size();) {
+        size_t e = text.find('\n', pos);
+        if (e == std::string::npos) e = text.size();
+        std::string line = text.substr(pos, e - pos);
+        pos = e + 1; ++number;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        line = line.substr(0, line.find('\t'));
+        if (line.empty()) continue;
+        if (line.size() > 64) { *why = usage + "line " + std::to_string(number) + " of " + path + " holds a query of " + std::to_string(line.size()) + " bytes"; return false; }
+        queries.push_back(line);
+    }
+    return true;
+}
+
 bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
 {
     o.vcf_path = argv[2]; o.fasta_path = argv[3]; o.outdir = argv[4];
-    const char *peptides_arg = nullptr, *tryptic_arg = nullptr;
+    const char *peptides_arg = nullptr, *tryptic_arg = nullptr, *find_arg = nullptr;
+    static std::string find_refusal;
     auto is = [&](int i, const char* a, const char* b = nullptr) { return !std::strcmp(argv[i], a) || (b && !std::strcmp(argv[i], b)); };
     for (int i = 5; i < argc; ++i) {
         if (is(i, "--slice-kb") && i + 1 < argc) { const uint64_t kb = std::strtoull(argv[++i], nullptr, 10); o.slice_bytes = kb ? kb << 10 : 1; continue; }
         if (is(i, "--peptides")) { peptides_arg = i + 1 < argc ? argv[++i] : ""; continue; }
         if (is(i, "--tryptic")) { tryptic_arg = i + 1 < argc ? argv[++i] : ""; continue; }
+        if (is(i, "--find")) { find_arg = i + 1 < argc ? argv[++i] : ""; continue; }
         o.no_test |= is(i, "--no-test");
         o.host_build |= is(i, "--host-build");
         o.host_groups |= is(i, "--host-groups");
@@ -297,7 +328,12 @@ bool parse_vcf_options(int argc, char** argv, VcfOptions& o, int* exit_code)
         refusal = "usage: --peptides K[,K...] writes variant_peptides_k{K}.tsv from the classes of --unique: it needs --unique and at most eight window lengths, each 1 .. 16";
     else if (tryptic_arg && (!o.unique || !parse_tryptic(tryptic_arg, o)))
         refusal = "usage: --tryptic M,MIN,MAX writes tryptic_peptides.tsv from the classes of --unique: it needs --unique, 0 .. 4 missed cleavages and lengths 1 <= MIN <= MAX <= 64";
+    else if (find_arg && !o.unique)
+        refusal = "usage: --find FILE looks the peptides of FILE up in the classes of --unique and writes found_peptides.tsv and found_peptides.carriers.tsv: it needs --unique";
+    else if (find_arg && !read_find_queries(find_arg, o.find_queries, &find_refusal))
+        refusal = find_refusal.c_str();
     o.tryptic = tryptic_arg && !refusal;
+    o.find = find_arg && !refusal;
     if (refusal) { std::fprintf(stderr, "%s\n", refusal); *exit_code = 2; }
     return !refusal;
 }
@@ -314,7 +350,7 @@ struct Report {
     float ims[3] = {}, xms[5] = {}, kms[4] = {}, tms[7] = {}, sms[2] = {}, gms[5] = {}, jms[5] = {};
     v2p_tables_info tinf{}; v2p_stats_info sinfo{}; v2p_groups_info ginfo{}; v2p_unique_info u_sum{};
     bool tables_on_device = false, device_groups = false, tasks_on_device = false, int_map_on_device = false;
-    std::string pep_json, tryptic_json, carriers_json, sources_json;
+    std::string pep_json, tryptic_json, carriers_json, sources_json, find_json;
     uint64_t sources_classes = 0;                                    // (of the last scan with sources)
     v2p_carriers_info k_last{};                                      // (of the last scan with carriers: the set's probands, words and class rows)
 
@@ -359,6 +395,7 @@ struct Report {
             std::printf(", \"carriers\": {\"probands\": %llu, \"words\": %llu, \"class_rows\": %llu, \"files\": {%s}}", (unsigned long long)k_last.n_probands,
                         (unsigned long long)k_last.words, (unsigned long long)k_last.n_class_rows, carriers_json.c_str());
         if (opt.sources) std::printf(", \"sources\": {\"classes\": %llu, \"files\": {%s}}", (unsigned long long)sources_classes, sources_json.c_str());
+        if (opt.find) std::printf(", \"find\": {%s}", find_json.c_str());
         std::printf(", \"tasks\": %s}\n", tasks_json.c_str());
     }
 };
@@ -846,6 +883,7 @@ static Batch execute_or_host_build(GpuContext& ctx, v2p_batch* b, v2p_stream* rs
 struct UniqueSink {
     GpuContext& ctx; v2p_unique* uq; const VcfOptions& opt; const std::vector<std::string>& samples; const Fasta& ref; const ResidentReference& rr; Report& rep;
     v2p_carriers* kq;                                                // --carriers: a proband row per class, filled add by add; else null
+    v2p_carriers* rows_q;                                            // the rows that are kept: kq, or --find's own set where --carriers made none; else null
     std::vector<uint32_t> u_class;                                   // the class of every record, slice after slice
     std::vector<uint64_t> u_hap_begin{0};                            // the first record of every haplotype
 
@@ -862,11 +900,11 @@ struct UniqueSink {
         const uint64_t hap0 = u_hap_begin.size() - 1;
         for (uint64_t h = 0; h < n_haps; ++h) u_hap_begin.push_back(u_hap_begin.back() + hap_tx[h]);
         if (u_hap_begin.back() != u_class.size()) fail("panicked: a slice's stream holds another number of records than its haplotypes");
-        if (kq) {                                                    // a record's owner: the sample of its haplotype
+        if (rows_q) {                                                // a record's owner: the sample of its haplotype
             std::vector<uint32_t> owner(n_tx + 1);
             for (uint64_t h = 0; h < n_haps; ++h)
                 for (uint64_t r = u_hap_begin[hap0 + h]; r < u_hap_begin[hap0 + h + 1]; ++r) owner[r - at] = uint32_t((hap0 + h) / 2);
-            chk(ctx, v2p_carriers_add(kq, u_class.data() + at, owner.data(), n_tx));
+            chk(ctx, v2p_carriers_add(rows_q, u_class.data() + at, owner.data(), n_tx));
         }
         v2p_unique_info& sum = rep.u_sum;
         sum.n_records += inf.n_records; sum.n_classes = inf.n_classes; sum.store_bytes = inf.store_bytes; sum.table_slots = inf.table_slots;
@@ -1077,6 +1115,67 @@ struct UniqueSink {
                       inf.ms_ref_build, inf.ms_mark, inf.ms_filter, inf.ms_insert, inf.ms_collect);
         rep.tryptic_json = buf;
     }
+    // ---- --find FILE: behind the other peptide files, the file's queries looked up at every position of the set's classes and of every
+    // sequence of the -r file (v2p_find_*): found_peptides.tsv and found_peptides.carriers.tsv, one line per query, in the file's order ----
+    void write_found(const std::vector<std::string>& class_name)
+    {
+        const auto [blob, seq_begin, seq_len] = reference_blob();
+        std::vector<const std::string*> ref_name;
+        for (const auto& kv : ref) ref_name.push_back(&kv.first);
+        const std::vector<std::string>& queries = opt.find_queries;
+        const uint64_t n = queries.size();
+        std::string text;
+        std::vector<uint64_t> q_begin(n + 1);
+        std::vector<uint32_t> q_len(n + 1);
+        for (uint64_t q = 0; q < n; ++q) { q_begin[q] = text.size(); q_len[q] = uint32_t(queries[q].size()); text += queries[q]; }
+        Find fs;
+        chk(ctx, v2p_find_create(ctx.raw(), reinterpret_cast<const uint8_t*>(text.data()), q_begin.data(), q_len.data(), n, ~0ull,
+                                 reinterpret_cast<const uint8_t*>(blob.data()), blob.size(), seq_begin.data(), seq_len.data(), ref.size(), out_ptr(fs)));
+        v2p_find_info inf{};
+        chk(ctx, v2p_find_scan(fs.get(), uq, rows_q, &inf));
+        uint64_t n_pairs = 0, nc = 0;
+        chk(ctx, v2p_find_count(fs.get(), &n_pairs, &nc));
+        const uint32_t W = uint32_t((samples.size() + 63) / 64);
+        std::vector<uint64_t> occ(n + 1), ref_occ(n + 1), begin(n + 2), bits(n * W + 1);
+        std::vector<uint32_t> rs(n + 1), ro(n + 1), cls(n_pairs + 1), off(n_pairs + 1), count(n + 1);
+        chk(ctx, v2p_find_download(fs.get(), occ.data(), ref_occ.data(), rs.data(), ro.data(), begin.data(), cls.data(), off.data(), nullptr, n, n_pairs, nc));
+        chk(ctx, v2p_find_download_carriers(fs.get(), bits.data(), count.data(), nullptr, n, W));
+        std::string tsv = "#peptide\toccurrences\tproteins\ttranscripts\tcarriers\treference_occurrences\tfirst_reference\tsources\n";
+        std::string ktsv = "#peptide\tcarriers\tprobands\n", list;
+        std::vector<std::string> tx;
+        for (uint64_t q = 0; q < n; ++q) {
+            tx.clear(); list.clear();
+            for (uint64_t j = begin[q]; j < begin[q + 1]; ++j) {
+                const std::string& name = class_name[cls[j]];
+                tx.push_back(name.substr(0, name.rfind("_v")));
+                if (!list.empty()) list += ",";
+                list += name + ":" + std::to_string(off[j] + 1u);
+            }
+            std::sort(tx.begin(), tx.end());
+            const uint64_t n_tx = uint64_t(std::unique(tx.begin(), tx.end()) - tx.begin());
+            tsv += queries[q] + "\t" + std::to_string(occ[q]) + "\t" + std::to_string(begin[q + 1] - begin[q]) + "\t" + std::to_string(n_tx) + "\t" +
+                   std::to_string(count[q]) + "\t" + std::to_string(ref_occ[q]) + "\t" +
+                   (ref_occ[q] ? *ref_name[rs[q]] + ":" + std::to_string(ro[q] + 1u) : std::string()) + "\t" + list + "\n";
+            ktsv += queries[q] + "\t" + std::to_string(count[q]) + "\t";
+            bool any = false;
+            for (uint64_t p = 0; p < samples.size(); ++p)
+                if ((bits[q * W + (p >> 6)] >> (p & 63u)) & 1u) { if (any) ktsv += ","; ktsv += samples[p]; any = true; }
+            ktsv += "\n";
+        }
+        write_tsv(std::string(opt.outdir) + "/found_peptides.tsv", tsv);
+        write_tsv(std::string(opt.outdir) + "/found_peptides.carriers.tsv", ktsv);
+        char buf[1200];
+        std::snprintf(buf, sizeof buf, "\"n_queries\": %llu, \"n_anchors\": %llu, \"anchor_len\": %llu, \"filter_bits\": %llu, \"filter_bits_set\": %llu, \"table_slots\": %llu, "
+                      "\"n_positions\": %llu, \"n_filter_pass\": %llu, \"n_table_hits\": %llu, \"n_occurrences\": %llu, \"n_pairs\": %llu, \"n_classes\": %llu, \"max_sources\": %llu, "
+                      "\"ref_positions\": %llu, \"ref_filter_pass\": %llu, \"ref_table_hits\": %llu, \"ref_occurrences\": %llu, \"tsv_bytes\": %llu, \"carriers_tsv_bytes\": %llu, "
+                      "\"ms_ref\": %.3f, \"ms_match\": %.3f, \"ms_group\": %.3f, \"ms_carry\": %.3f",
+                      (unsigned long long)inf.n_queries, (unsigned long long)inf.n_anchors, (unsigned long long)inf.anchor_len, (unsigned long long)inf.filter_bits,
+                      (unsigned long long)inf.filter_bits_set, (unsigned long long)inf.table_slots, (unsigned long long)inf.n_positions, (unsigned long long)inf.n_filter_pass,
+                      (unsigned long long)inf.n_table_hits, (unsigned long long)inf.n_occurrences, (unsigned long long)inf.n_pairs, (unsigned long long)inf.n_classes,
+                      (unsigned long long)inf.max_sources, (unsigned long long)inf.ref_positions, (unsigned long long)inf.ref_filter_pass, (unsigned long long)inf.ref_table_hits,
+                      (unsigned long long)inf.ref_occurrences, (unsigned long long)tsv.size(), (unsigned long long)ktsv.size(), inf.ms_ref, inf.ms_match, inf.ms_group, inf.ms_carry);
+        rep.find_json = buf;
+    }
     void write_files()
     {
         const Stopwatch sw;
@@ -1129,13 +1228,14 @@ struct UniqueSink {
         if (!ff || !ft) fail("Could not write %s.fasta / .tsv", base.c_str());
         rep.u_fasta_bytes = out_len; rep.u_tsv_bytes = tsv.size();
         rep.written += out_len + tsv.size();
-        if (!opt.peptide_ks.empty() || opt.tryptic) {
+        if (!opt.peptide_ks.empty() || opt.tryptic || opt.find) {
             std::vector<std::string> class_name(nc);
             for (uint64_t c = 0; c < nc; ++c) class_name[c] = *cname[c] + "_v" + std::to_string(k_of[c]);
             if (!opt.peptide_ks.empty()) write_peptides(class_name);
             if (opt.tryptic) write_tryptic(class_name);
             if (kq) write_carriers_summary();
             if (opt.sources) write_sources_summary(class_name);
+            if (opt.find) write_found(class_name);
         }
         rep.t_write_acc += sw.seconds();
     }
@@ -1382,7 +1482,7 @@ int vcf_mode(const VcfOptions& opt)
     Report rep;
     Stopwatch lap;
     std::unique_ptr<GpuContext> ctx_box;
-    Carriers kq; Unique uq; Index idx; Decode dec; Tables tb; Groups g; Batch b;
+    Carriers kq, fq; Unique uq; Index idx; Decode dec; Tables tb; Groups g; Batch b;
     std::string vcf = slurp(opt.vcf_path);
     const Fasta ref = read_fasta(slurp(opt.fasta_path));
     rep.t_read = lap.lap();
@@ -1412,7 +1512,8 @@ int vcf_mode(const VcfOptions& opt)
     if (opt.unique) chk(ctx, v2p_unique_create(ctx.raw(), 0, out_ptr(uq)));
     ProbandWriter writer{opt, samples, rep};
     if (opt.carriers) chk(ctx, v2p_carriers_create(ctx.raw(), uint32_t(samples.size()), out_ptr(kq)));
-    UniqueSink sink{ctx, uq.get(), opt, samples, ref, rr, rep, kq.get()};
+    if (opt.find && !opt.carriers) chk(ctx, v2p_carriers_create(ctx.raw(), uint32_t(samples.size()), out_ptr(fq)));     // (--find always keeps proband rows)
+    UniqueSink sink{ctx, uq.get(), opt, samples, ref, rr, rep, kq.get(), kq ? kq.get() : fq.get()};
     const Emit emit{ctx, opt, co, rr, b.get(), writer, sink, rep};
     std::string tasks_json = "{\"path\": \"host\"}";
     if (rep.tasks_on_device) tasks_json = run_device_tasks(emit, dec, tb);

@@ -1,6 +1,7 @@
 // vcf_mode.hpp -- `v2p_harness vcf`: the product's command line (python -m vcf2prot_amd forwards its flags here); vcf_mode.cpp
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 struct VcfOptions {
@@ -13,6 +14,8 @@ struct VcfOptions {
     uint32_t tryptic_missed = 0, tryptic_min = 0, tryptic_max = 0;
     bool carriers = false;                   // --carriers: {stem}.carriers.tsv beside every peptide file, and peptide_carriers_summary.tsv
     bool sources = false;                    // --sources: {stem}.sources.tsv beside every peptide file, and peptide_sources_summary.tsv
+    bool find = false;                       // --find FILE: found_peptides.tsv and found_peptides.carriers.tsv
+    std::vector<std::string> find_queries;   // the file's queries, in its order (read while the options are parsed)
 };
 
 // argv = {harness, "vcf", in.vcf, reference.fasta, outdir, flags...}; an argument that is no flag is ignored.  false: a combination that is

@@ -824,6 +824,68 @@ class TrypticSet(_DeviceSet):
         return {"text": text[:text_bytes], "text_begin": begin[:n + 1], "occ": occ[:n], "first_class": cls[:n], "first_offset": off[:n]}
 
 
+class FindSet(_DeviceSet):
+    """One ``v2p_find``: a list of queries of 1 to 64 bytes looked up at every position of a UniqueSet's classes and of the reference
+    sequences, on the device (the rule: tests/find_rule.py).  ``queries`` and ``reference``: bytes each.  ``hash_mask`` is for tests."""
+    _destroy = "v2p_find_destroy"
+
+    def __init__(self, ctx: Context, queries: Sequence[bytes], reference: Sequence[bytes] = (), hash_mask: int = 2 ** 64 - 1):
+        self.ctx, self.hash_mask, self._lib = ctx, hash_mask, ctx._lib
+        self._create(_packed(queries), _packed(reference))
+
+    def _create(self, q, r):
+        """v2p_find_create on two (blob, bytes, begin, lens, n) tuples as given (tests hand it lengths and ranges that are refused)"""
+        h = ctypes.c_void_p()
+        self._h = None
+        self.n_q = q[4]
+        self.ctx._check(self._lib.v2p_find_create(self.ctx._h, q[0].ctypes.data, q[2].ctypes.data, q[3].ctypes.data, q[4], self.hash_mask,
+                                                  r[0].ctypes.data, r[1], r[2].ctypes.data, r[3].ctypes.data, r[4], ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_arrays(cls, ctx: Context, q_blob, q_begin, q_len, blob, seq_begin, seq_len, hash_mask: int = 2 ** 64 - 1) -> "FindSet":
+        """the queries and the reference each as one uint8 array and a table of ranges"""
+        self = cls.__new__(cls)
+        self.ctx, self.hash_mask, self._lib = ctx, hash_mask, ctx._lib
+        self._create(_padded(q_blob, q_begin, q_len), _padded(blob, seq_begin, seq_len))
+        return self
+
+    def scan(self, uset: "UniqueSet", carriers: Optional["CarrierSet"] = None) -> dict:
+        """v2p_find_scan: every query against every class the set holds now; returns the info.  With ``carriers`` the queries get
+        carrier rows as well."""
+        info = N.FindInfo()
+        self.ctx._check(self._lib.v2p_find_scan(self._h, uset._h, carriers._h if carriers is not None else None, ctypes.byref(info)))
+        self._carriers = (carriers.words, carriers.n_probands) if carriers is not None else None
+        return {k: getattr(info, k) for k, _ in N.FindInfo._fields_}
+
+    def count(self) -> Tuple[int, int]:
+        """((query, source) pairs, classes of the record set at the scan)"""
+        n_pairs, n_classes = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._check(self._lib.v2p_find_count(self._h, ctypes.byref(n_pairs), ctypes.byref(n_classes)))
+        return int(n_pairs.value), int(n_classes.value)
+
+    def download(self, n_q: Optional[int] = None, n_pairs: Optional[int] = None, n_classes: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_find_download: occ, ref_occ, first_ref_seq, first_ref_offset [n_q], source_begin [n_q + 1], source_class / source_offset
+        [n_pairs], total [n_classes] of the last scan."""
+        if n_pairs is None or n_classes is None:
+            have = self.count()
+            n_pairs, n_classes = (have[0] if n_pairs is None else n_pairs), (have[1] if n_classes is None else n_classes)
+        n = self.n_q if n_q is None else n_q
+        occ, ref_occ, begin = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(n + 2, np.uint64)
+        rs, ro, cls, off = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32), np.zeros(n_pairs + 1, np.uint32), np.zeros(n_pairs + 1, np.uint32)
+        total = np.zeros(n_classes + 1, np.uint64)
+        self.ctx._check(self._lib.v2p_find_download(self._h, occ.ctypes.data, ref_occ.ctypes.data, rs.ctypes.data, ro.ctypes.data, begin.ctypes.data,
+                                                    cls.ctypes.data, off.ctypes.data, total.ctypes.data, n, n_pairs, n_classes))
+        return {"occ": occ[:n], "ref_occ": ref_occ[:n], "first_ref_seq": rs[:n], "first_ref_offset": ro[:n], "source_begin": begin[:n + 1],
+                "source_class": cls[:n_pairs], "source_offset": off[:n_pairs], "total": total[:n_classes]}
+
+    def carriers(self, n_q: Optional[int] = None, words: Optional[int] = None, n_probands: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """v2p_find_download_carriers: bits [n_q, words], n_carriers [n_q], per_proband [P] of the last scan, if it had carriers."""
+        have = getattr(self, "_carriers", None) or (1, 1)
+        return _download_carriers(self._lib.v2p_find_download_carriers, self, self.n_q if n_q is None else n_q,
+                                  have[0] if words is None else words, have[1] if n_probands is None else n_probands)
+
+
 def default_context() -> Context:
     global _default_ctx
     if _default_ctx is None or _default_ctx._h is None:
